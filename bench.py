@@ -2,9 +2,15 @@
 """bench.py -- bases/sec sketched (k=21, n=1000) on N x MI355X, with the kernel's HBM roofline fraction, the CPU baseline
 timed beside it and a self-check of the sketch against the oracle's golden fingerprint (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c5] [--gbases G]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c5] [--gbases G] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the roofline figures the timed
+steps' own HIP events give.  Everything else it can measure or check (live and committed PMC figures, the streaming-read peak, the
+CPU baselines, the golden self-check, the extras) runs only under --full.  --dump-outputs DIR writes what the last timed step
+computed -- the arrays its caller receives -- as DIR/<name>.npy in float32 / float64 (see dump_outputs); the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 
 How the N GPUs are driven.  Launched by torch.distributed.run (WORLD_SIZE in the environment): one process per GPU, rank r
 sketches read block r, rank 0 gathers the <= n-record partial sketches and merges them on the host.  Launched plainly with
@@ -25,11 +31,11 @@ A step = one full pass: reset, sketch every base of the block, finish (bottom-n 
 the host) and -- for N > 1 -- the host-side merge, which runs one step behind the sketching on a thread of its own (all K merges
 complete inside the timed region).  value = total bases of all GPUs * K / max-over-ranks time.
 
-Self-check: the seven-number fingerprint of the final sketch (+ total_kmers) is compared with
+Self-check (--full): the seven-number fingerprint of the final sketch (+ total_kmers) is compared with
 tests/golden/config_fingerprints.json, which the ORACLE produced on the CPU (tests/golden/make_config_fingerprints.py);
 "sketch_check.matches_golden" is true / false / null (no golden for a non-default size), and the exit code is 3 when false.
 
-After the timed region an N = 1 run also measures, OUTSIDE `value` (key "extras"): configs[1] (the first 10 Gbase of the same
+With --full, after the timed region an N = 1 run also measures, OUTSIDE `value` (key "extras"): configs[1] (the first 10 Gbase of the same
 stream), k=31, configs[2] (k=31, 2 M hashes, host filters), the CLI-default oversketch (n=200 000), a two-word k-mer length,
 the end-to-end rate from FASTQ text in host memory, compressed input and a batch of FASTA files.  --no-extras skips them.
 """
@@ -302,6 +308,46 @@ def fingerprint(kc, km, total_kmers):
             "total_kmers": int(total_kmers)}
 
 
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs writes at most
+
+
+def _float_columns(name, a):
+    """one integer array -> {file name: float array} that holds it exactly: uint64 (the hashes) as its two 32-bit halves in
+    float64 (<name>_hi, <name>_lo), uint8 as float32, anything else (counts, positions, lengths: all below 2^53) as float64"""
+    a = np.asarray(a)
+    if a.dtype == np.uint64:
+        return {name + "_hi": (a >> np.uint64(32)).astype(np.float64), name + "_lo": (a & np.uint64(0xFFFFFFFF)).astype(np.float64)}
+    return {name: a.astype(np.float32 if a.dtype == np.uint8 else np.float64)}
+
+
+def dump_outputs(d, records, extra=None):
+    """--dump-outputs: `records` (name -> array with one row per record, all of the same length) and `extra` (name -> small
+    array or scalar, written whole) as DIR/<name>.npy.  If the records do not fit DUMP_LIMIT, a fixed, seeded sample of their
+    rows is written instead, and record_index.npy names the rows.  -> the names written"""
+    cols, small = {}, {}
+    for name, a in records.items():
+        cols.update(_float_columns(name, a))
+    for name, a in (extra or {}).items():
+        small.update(_float_columns(name, np.atleast_1d(a)))
+    n = len(next(iter(cols.values()))) if cols else 0
+    room = DUMP_LIMIT - sum(c.nbytes for c in small.values())
+    if n and sum(c.nbytes for c in cols.values()) > room:
+        row = sum(c.nbytes for c in cols.values()) // n + 8  # (+ its record_index entry)
+        idx = np.sort(np.random.default_rng(SEED).choice(n, max(room, 0) // row, replace=False))
+        cols = {k: c[idx] for k, c in cols.items()}
+        cols["record_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, c in list(cols.items()) + list(small.items()):
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(c))
+    return sorted(cols) + sorted(small)
+
+
+def dump_sketch(d, kc, km, pos, total_kmers):
+    """--dump-outputs of a resident-stream step: the sketch a caller of to_arrays() receives, and finish()'s k-mer count"""
+    return dump_outputs(d, {"hash": kc["hash"], "count": kc["count"], "extra_count": kc["extra_count"], "kmer": km,
+                            "first_pos": np.asarray(pos).astype(np.int64)}, {"total_kmers": np.int64(total_kmers)})
+
+
 def check_golden(fp, key):
     """-> (fingerprint + matches_golden, ok) ; matches_golden is None when the golden file has no entry for this workload"""
     g = _golden(key)
@@ -406,7 +452,16 @@ def main():
                          "moves the same gather onto the GPUs.")
     ap.add_argument("--share-gpu", action="store_true",
                     help="debug: map every rank / thread to device 0 to exercise the N > 1 flow on a 1-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: live and committed PMC figures, the "
+                         "streaming-read peak, the CPU baselines, the golden self-check and the extras (off: a plain run only sets "
+                         "up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     launched = "WORLD_SIZE" in os.environ  # torch.distributed.run: one process per GPU
     rank = int(os.environ.get("RANK", "0"))
@@ -541,6 +596,8 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return 0
+    if args.dump_outputs:
+        dump_sketch(args.dump_outputs, *gathered)
 
     n_reads = shards[0].n_reads
     dr, dg = shards[0].dr, shards[0].dg
@@ -562,7 +619,7 @@ def main():
     # how each was collected); they are attached to the workload they were measured on and to no other
     is_default = (workload, gbases, args.k, args.n, world) == ("c4", 50.0, 21, 1000, 1)
     std_size = (workload, gbases) in (("c2", 10.0), ("c4", 50.0))
-    pmc = _pmc_derived("%s_k%d_n%d" % (workload, args.k, args.n)) if (std_size and world == 1) else None
+    pmc = _pmc_derived("%s_k%d_n%d" % (workload, args.k, args.n)) if (args.full and std_size and world == 1) else None
     if pmc:
         # HBM bytes the counters saw per algorithmic byte, applied to this run's launch size
         roofline["traffic"] = int(pmc["hbm_bytes_per_position"] * roofline["alg_bytes_per_launch"])
@@ -573,7 +630,7 @@ def main():
 
     # ... unless this run can collect them itself: the sketch launches' HBM bytes from PMC counters taken NOW (two profiled child
     # runs of this command, ~10 s each; not in the timed region), so that the traffic figure is this box's and this library's
-    if world == 1 and std_size and not args.no_live_pmc:
+    if args.full and world == 1 and std_size and not args.no_live_pmc:
         live = _live_pmc(["--workload", workload, "--gbases", repr(gbases), "--k", str(args.k), "--n", str(args.n)] +
                          (["--max-launch", str(args.max_launch)] if args.max_launch else []))
         if live:
@@ -592,14 +649,15 @@ def main():
             roofline["traffic_source"] = (roofline.get("traffic_source") or "") + " [live collection failed: %s]" % LIVE_PMC_WHY
 
     # measured streaming-read peak of this box next to the spec peak; not in the timed region
-    try:
-        roofline["measured_stream_read_GBps"] = round(S.measure_read_bandwidth(dr, min(shards[0].nbytes, 4 << 30) // 16 * 16), 1)
-    except Exception:
-        roofline["measured_stream_read_GBps"] = None
+    if args.full:
+        try:
+            roofline["measured_stream_read_GBps"] = round(S.measure_read_bandwidth(dr, min(shards[0].nbytes, 4 << 30) // 16 * 16), 1)
+        except Exception:
+            roofline["measured_stream_read_GBps"] = None
 
     cpu = None
     cpu_all = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O  # the checker, timed as the reported CPU baseline ("port")
         flags = O.use_native()  # compiled on this box with -march=native
         ns = min(n_reads, int(args.cpu_sample_mbases * 1e6 / READ_LEN))
@@ -632,7 +690,7 @@ def main():
                                      "reference does for a single file)" % (ncpu, per)}
 
     extras = None
-    if world == 1 and not args.no_extras and is_default:
+    if args.full and world == 1 and not args.no_extras and is_default:
         global LIVE_PMC_EXTRAS
         LIVE_PMC_EXTRAS = not args.no_live_pmc
         extras = measure_extras(F, S, dr, dg, min(n_reads, int(np.ceil(10e9 / READ_LEN))), my_devices[0])
@@ -651,8 +709,10 @@ def main():
                  "size/sketch", world, "" if world == 1 else "s", args.k, args.n))
         gkey = "c4_k%d_n%d" % (args.k, args.n) if gbases == 50.0 else None  # the same sketch whatever N
     # fingerprint of the final (merged) sketch: N GPUs over their read blocks must give what the oracle gives on the union
-    check, ok = check_golden(fingerprint(gathered[0], gathered[1], gathered[3]), gkey) if gkey else \
-        (dict(fingerprint(gathered[0], gathered[1], gathered[3]), golden=None, matches_golden=None), True)
+    check, ok = None, True
+    if args.full:
+        check, ok = check_golden(fingerprint(gathered[0], gathered[1], gathered[3]), gkey) if gkey else \
+            (dict(fingerprint(gathered[0], gathered[1], gathered[3]), golden=None, matches_golden=None), True)
     out = {
         "metric": "bases/sec sketched (k=%d, n=%d)" % (args.k, args.n),
         "value": round(value, 1), "unit": "bases/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -726,9 +786,9 @@ def run_c5(args, F, S, dist, barrier, rank, world, my_devices, launched, gather_
         elapsed = time.perf_counter() - t0
         k_ms, k_launches, k_pos = H.debug_kernel_times(0)
         fb1 = H.debug_file_batch()
-        # fingerprint of the sample: files 0..255 (each rank contributes the ones it sketched)
+        # fingerprint of the sample (--full): files 0..255 (each rank contributes the ones it sketched)
         fx, tk, cs = 0, 0, 0
-        for j, i in enumerate(mine):
+        for j, i in enumerate(mine if args.full else []):
             if i < C5_SAMPLE:
                 sk = res.sketch(j)
                 fx ^= int(np.bitwise_xor.reduce(sk.arrays[0]["hash"]))
@@ -745,11 +805,15 @@ def run_c5(args, F, S, dist, barrier, rank, world, my_devices, launched, gather_
                 fx ^= a; tk += b; cs += c; k_ms += d1; k_launches += d2; k_pos += d3
         if rank != 0:
             return 0
+        if args.dump_outputs:
+            dump_files(args.dump_outputs, res, mine)
         tot = sum(lens)
-        g = _golden("c5_files_0_255") if nf >= C5_SAMPLE else None
-        fp = {"sample_files": min(nf, C5_SAMPLE), "hash_xor": fx, "count_sum": cs, "total_kmers": tk,
-              "golden": "tests/golden/config_fingerprints.json[c5_files_0_255] (oracle, CPU)" if g else None,
-              "matches_golden": None if g is None else all(g[k] == v for k, v in (("hash_xor", fx), ("count_sum", cs), ("total_kmers", tk)))}
+        fp = None
+        if args.full:
+            g = _golden("c5_files_0_255") if nf >= C5_SAMPLE else None
+            fp = {"sample_files": min(nf, C5_SAMPLE), "hash_xor": fx, "count_sum": cs, "total_kmers": tk,
+                  "golden": "tests/golden/config_fingerprints.json[c5_files_0_255] (oracle, CPU)" if g else None,
+                  "matches_golden": None if g is None else all(g[k] == v for k, v in (("hash_xor", fx), ("count_sum", cs), ("total_kmers", tk)))}
         out = {"metric": "bases/sec sketched (k=21, n=1000)", "value": round(tot * args.steps / elapsed, 1), "unit": "bases/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
@@ -760,12 +824,13 @@ def run_c5(args, F, S, dist, barrier, rank, world, my_devices, launched, gather_
                           "files": nf, "files_per_s": round(nf * args.steps / elapsed, 1),
                           "parallelism": "file -> GPU mapping x%d (%s)" % (world, "one call per rank" if launched and world > 1 else "one call, devices=[0..%d]" % (world - 1))},
                "roofline": c5_roofline(k_ms, k_launches, k_pos, elapsed * 1e3, world, batch=(fb1[0] - fb0[0], fb1[1] - fb0[1]),
-                                       live=None if (args.no_live_pmc or world != 1) else
+                                       live=None if (not args.full or args.no_live_pmc or world != 1) else
                                        _live_pmc(["--workload", "c5", "--files", str(min(nf, 256)), "--c5-dir", d], timeout_s=240, kernels=("k2_batch", "k2_sketch")),
-                                       h2d=_h2d_peak_gbs(my_devices[0]), text_bytes=sum(os.path.getsize(p) for p in paths) * args.steps),
-               "cpu_baseline": None if args.no_cpu_baseline else c5_cpu_baseline(paths, lens), "sketch_check": fp}
+                                       h2d=_h2d_peak_gbs(my_devices[0]) if args.full else None,
+                                       text_bytes=sum(os.path.getsize(p) for p in paths) * args.steps),
+               "cpu_baseline": c5_cpu_baseline(paths, lens) if args.full and not args.no_cpu_baseline else None, "sketch_check": fp}
         print(json.dumps(out), flush=True)
-        return 0 if fp["matches_golden"] is not False else 3
+        return 0 if fp is None or fp["matches_golden"] is not False else 3
     finally:
         res = None
         if dist is not None:
@@ -774,6 +839,26 @@ def run_c5(args, F, S, dist, barrier, rank, world, my_devices, launched, gather_
             shutil.rmtree(d, ignore_errors=True)
         if dist is not None:
             dist.destroy_process_group()
+
+
+def dump_files(d, res, mine):
+    """--dump-outputs of a batch step (`res` = what sketch_files returned for the files numbered `mine`): every file's lengths
+    and hash count, and the sketches of the golden sample, files 0..C5_SAMPLE-1 (all of them: 10 000 x 1000 records)"""
+    from finch_rs_amd import host as H
+    L = H.lib()
+    rec = {"file": [], "hash": [], "count": [], "extra_count": [], "kmer": []}
+    for j, i in enumerate(mine):
+        if i < C5_SAMPLE:
+            kc, km = res.sketch(j).arrays
+            rec["file"].append(np.full(len(kc), i, np.int64))
+            for k in ("hash", "count", "extra_count"):
+                rec[k].append(kc[k])
+            rec["kmer"].append(km)
+    per_file = {"file_index": np.asarray(mine, np.int64),
+                "file_seq_length": np.array([L.finch_sketch_seq_length(res._p, j) for j in range(len(mine))], np.int64),
+                "file_num_valid_kmers": np.array([L.finch_sketch_num_valid_kmers(res._p, j) for j in range(len(mine))], np.int64),
+                "file_n_hashes": np.array([L.finch_sketch_n_hashes(res._p, j) for j in range(len(mine))], np.int64)}
+    return dump_outputs(d, {k: np.concatenate(v) for k, v in rec.items()} if rec["file"] else {}, per_file)
 
 
 LIVE_PMC_EXTRAS = True  # main() clears it under --no-live-pmc

@@ -11,6 +11,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,8 @@ def _free_port():
     return p
 
 
-def _bench(args, world=1, launcher=True, rc=0):
+def _bench(args, world=1, launcher=True, rc=0, full=True):
+    """one bench.py line; full: with --full (the self-check, CPU baselines and counters the tests read are not in a plain run)"""
     env = dict(os.environ)
     if world > 1 and launcher:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
@@ -35,7 +37,7 @@ def _bench(args, world=1, launcher=True, rc=0):
         cmd = [sys.executable, "bench.py"] + (["--gpus", str(world), "--share-gpu"] if world > 1 else [])
         for v in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):  # a plain launch: nothing of a launcher in the environment
             env.pop(v, None)
-    r = subprocess.run(cmd + args, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
+    r = subprocess.run(cmd + (["--full"] if full else []) + args, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
     assert r.returncode == rc, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout  # ONE JSON line, from rank 0
@@ -118,10 +120,10 @@ def test_single_gpu_default_is_configs3_and_checks_itself():
     assert out["per_rank"] == [{"rank": 0, "reads": 333333334, "kernel_ms_per_pass": out["roofline"]["kernel_ms_per_pass"]}]
 
 
-def test_c5_workload_two_handles_one_call():
+def test_c5_workload_two_handles_one_call(tmp_path):
     """--workload c5 on a cut-down batch (300 files: the 256 golden ones + a tail), devices = [0, 0] in ONE finch_sketch_files
-    call: per-file sketches of the sample must give the oracle's fingerprint"""
-    out = _bench(["--workload", "c5", "--files", "300", "--steps", "1", "--warmup", "0"], 2, launcher=False)
+    call: per-file sketches of the sample must give the oracle's fingerprint -- and so must what --dump-outputs wrote"""
+    out = _bench(["--workload", "c5", "--files", "300", "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path)], 2, launcher=False)
     assert out["config"]["files"] == 300 and out["n_gpus"] == 2
     assert out["sketch_check"]["sample_files"] == 256 and out["sketch_check"]["matches_golden"] is True
     assert out["value"] > 0 and out["config"]["files_per_s"] > 0
@@ -132,6 +134,12 @@ def test_c5_workload_two_handles_one_call():
     assert r["files_taken_many_per_launch"] + r["files_through_own_sketcher"] == 300 and r["files_taken_many_per_launch"] >= 290
     assert r["pcie"]["achieved_gbs"] > 0
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "one file per task" in c["sample"]
+    d = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert list(d["file_index"]) == list(range(300)) and set(d["file"]) == set(range(256))
+    assert int(d["file_num_valid_kmers"][:256].sum()) == out["sketch_check"]["total_kmers"]
+    h = (d["hash_hi"].astype(np.uint64) << np.uint64(32)) | d["hash_lo"].astype(np.uint64)
+    assert int(np.bitwise_xor.reduce(h)) == out["sketch_check"]["hash_xor"] and int(d["count"].sum()) == out["sketch_check"]["count_sum"]
 
 
 def test_multi_rank_line_names_every_ranks_kernel_time():
@@ -188,3 +196,32 @@ def test_the_bench_line_collects_its_own_counters():
     assert r["traffic"] == int(live["hbm_bytes_per_position"] * r["alg_bytes_per_launch"])
     committed = _bench(["--workload", "c2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--no-live-pmc"], 1)
     assert committed["roofline"]["traffic_source"].startswith("committed")
+
+
+def test_plain_line_is_lean_and_dumps_what_the_last_step_computed(tmp_path):
+    """a plain run (no --full) times --steps steps and prints the headline line without the self-check, CPU baselines, extras
+    or counter figures; --dump-outputs writes the last step's sketch exactly (the fingerprint the --full line's self-check
+    reports) and the same arguments give the same outputs"""
+    common = ["--workload", "c2", "--gbases", "0.2", "--steps", "3", "--warmup", "1"]
+    plain = _bench(common + ["--dump-outputs", str(tmp_path / "plain")], full=False)
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert plain["metric"] == "bases/sec sketched (k=21, n=1000)" and plain["unit"] == "bases/s" and plain["higher_is_better"] is True
+    assert plain["dtype"] == "u64"
+    bases = plain["config"]["reads_total"] * 150
+    assert abs(plain["value"] * plain["ms_per_step"] / 1e3 - bases) < 1e-3 * bases
+    assert plain["sketch_check"] is None and plain["cpu_baseline"] is None and plain["cpu_baseline_allcores"] is None
+    assert "extras" not in plain and "measured_stream_read_GBps" not in plain["roofline"] and plain["roofline"]["traffic"] is None
+    assert plain["roofline"]["launches"] > 0 and plain["roofline"]["kernel_ms_per_pass"] > 0
+    full = _bench(common + ["--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full"))
+    d = {f[:-4]: np.load(tmp_path / "plain" / f) for f in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    for f in names:
+        assert np.array_equal(d[f[:-4]], np.load(tmp_path / "full" / f)), f
+    fp = full["sketch_check"]
+    h = (d["hash_hi"].astype(np.uint64) << np.uint64(32)) | d["hash_lo"].astype(np.uint64)
+    assert len(h) == fp["n_hashes"] == 1000 and int(h[0]) == fp["min_hash"] and int(h[-1]) == fp["max_hash"]
+    assert int(np.bitwise_xor.reduce(h)) == fp["hash_xor"] and int(d["total_kmers"][0]) == fp["total_kmers"]
+    assert int(d["count"].sum()) == fp["count_sum"] and int(d["extra_count"].sum()) == fp["extra_sum"]
+    assert int(d["kmer"].astype(np.int64).sum()) == fp["kmer_byte_sum"] and d["kmer"].shape == (1000, 21)

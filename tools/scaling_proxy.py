@@ -27,7 +27,7 @@ for n in (2, 4, 8):
     if 1 in t and n in t:
         print("predicted efficiency at N = %d: %.3f" % (n, t[1] / (n * t[n])))
 for n in (2, 4, 8):
-    d = run(["--gpus", str(n), "--share-gpu", "--steps", "5", "--warmup", "2", "--no-extras", "--no-cpu-baseline"])
+    d = run(["--gpus", str(n), "--share-gpu", "--steps", "5", "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline"])
     if d:
         print("N = %d handles on the one GPU (one fh_sketch_device_blocks call per step): %8.3f ms per step  golden %s  per-rank kernel ms %s" %
               (n, d["ms_per_step"], d["sketch_check"]["matches_golden"], [p["kernel_ms_per_pass"] for p in d["per_rank"]]), flush=True)
