@@ -1,0 +1,36 @@
+// fh_dist.h -- what fh_host.cpp's finch_dist (include/finch_host.h) asks of the device: the merge walk of distance.rs:66-126 for
+// many (query, reference) pairs at once, reduced to integer counts.  Defined in fh_dist.hip; no HIP types here,
+// fh_host.cpp is plain C++.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace fh {
+
+// One side of a call: n sketches in CSR form (hashes[offsets[s] .. offsets[s + 1]) strictly ascending, fewer than 2^32 each),
+// and per sketch the scale data of distance.rs:16-29: flags bit 0 = a Scaled sketch, bit 1 = its scale is > 0; scale = the
+// f64 the pair's min_scale is chosen by (std::min, as finch_distance has it); max_hash = u64::MAX / ((1 / scale) as u64)
+// where bit 1 is set.
+struct DistSide {
+    const uint64_t *hashes;
+    const uint64_t *offsets; // n + 1
+    uint32_t n;
+    const uint64_t *max_hash;
+    const uint32_t *flags;
+    const double *scale;
+};
+
+constexpr uint32_t DIST_MAX_SLICE = 8192; // query hashes one LDS slice holds at most (64 KiB)
+
+struct DistDevice;
+// uploads both sides to `device` once and allocates two result buffers of max_pairs pairs (device + pinned host)
+int dist_open(int device, const DistSide &queries, const DistSide &refs, uint32_t slice, uint64_t max_pairs, DistDevice **out);
+// async on the handle's stream: the counts of every pair (q, r), r in [r0, r1), into buffer `buf` (0 / 1) and back to the host.
+// (r1 - r0) * n_queries <= max_pairs.
+int dist_launch(DistDevice *d, int buf, uint32_t r0, uint32_t r1);
+// waits for buffer `buf`: *out = 3 u32 per pair at ((r - r0) * n_queries + q) * 3: c = |Q n R|, then i and j of the walk (the
+// scale step included); *kernel_ms = the kernel's time (HIP events)
+int dist_wait(DistDevice *d, int buf, const uint32_t **out, double *kernel_ms);
+void dist_close(DistDevice *d);
+
+} // namespace fh

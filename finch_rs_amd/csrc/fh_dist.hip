@@ -1,0 +1,277 @@
+// fh_dist.hip -- many-vs-many sketch comparison (finch dist, cli/src/main.rs:85-125 / 315-333) on the device: for every
+// (query, reference) pair the integer counts that distance.rs:66-126's merge walk ends with; the host (fh_host.cpp, finch_dist)
+// turns them into the doubles with the same function finch_distance uses.  DESIGN.md §3.7 has the reduction.
+//
+// For strictly ascending Q (query) and R (reference) the walk stops with c = |Q n R|, i0 = #{q <= max R}, j0 = #{r <= max Q}
+// (both 0 if either list is empty); the scale step makes i = max(i0, #{q < M}), j = max(j0, #{r < M}).  None of that depends on
+// visiting pairs in order:
+//   * a workgroup holds a slice of one query's hashes in LDS; its four waves take the references of its block one at a time,
+//     each lane looks up the reference hashes t = lane, lane + 64, ... with a branchless binary search in the slice;
+//   * #{r <= max Q} and #{r < M} are counted by the same lanes on the way (every reference hash is read anyway), #{q <= max R}
+//     and #{q < M} are one wave-uniform binary search each in the slice;
+//   * a query longer than a slice is walked slice by slice: the slices hold disjoint value ranges, so every count adds.
+// The per-reference sums live in LDS until the last slice; the result is 3 u32 per pair, written with plain stores.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+
+#include "../../include/finch_hip.h"
+#include "fh_dist.h"
+#include "fh_internal.h"
+
+using namespace fh;
+
+namespace {
+
+#define DHIP_TRY(expr)                                                                                      \
+    do {                                                                                                    \
+        hipError_t _e = (expr);                                                                             \
+        if (_e != hipSuccess) return api_fail(FH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+constexpr uint32_t THREADS = 256; // four waves
+constexpr uint32_t WAVES = THREADS / 64;
+constexpr uint32_t RB = 64;       // references per workgroup
+
+struct DistArgs {
+    const uint64_t *qh, *qoff, *rh, *roff, *qmax, *rmax;
+    const uint32_t *qflag, *rflag;
+    const double *qscale, *rscale;
+    uint32_t nq, r0, r1, slice;
+    uint32_t *out;
+};
+
+// the pair's scale step (distance.rs:16-29 + raw_distance's `scale > 0` test): min_scale = std::min(q, r) = r < q ? r : q --
+// an exact comparison -- and M of the chosen sketch as the host computed it
+__device__ inline bool pair_max_hash(const DistArgs &a, uint32_t q, uint32_t r, uint64_t &m) {
+    const uint32_t fq = a.qflag[q], fr = a.rflag[r];
+    if (!(fq & 1) || !(fr & 1)) return false;
+    const bool pick_r = a.rscale[r] < a.qscale[q];
+    if (!((pick_r ? fr : fq) & 2)) return false;
+    m = pick_r ? a.rmax[r] : a.qmax[q];
+    return true;
+}
+
+// #{s[0..n) < x} (LE: <= x) over ascending s; top = the largest power of two <= n (0 for n = 0).  The same number of steps in
+// every lane (the wave's n is uniform), no branch; the index is clamped so that no read leaves s[0..n).
+template <bool LE>
+__device__ inline uint32_t count_below(const uint64_t *s, uint32_t n, uint32_t top, uint64_t x) {
+    uint32_t pos = 0;
+    for (uint32_t step = top; step; step >>= 1) {
+        const uint32_t p = pos + step;
+        const uint64_t v = s[min(p, n) - 1];
+        const bool take = p <= n && (LE ? v <= x : v < x);
+        pos = take ? p : pos;
+    }
+    return pos;
+}
+
+__device__ inline uint32_t wave_sum(uint32_t v) {
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// grid: x = query, y = block of RB references from a.r0; dynamic LDS: a.slice u64
+__global__ void __launch_bounds__(THREADS) k_dist_counts(DistArgs a) {
+    extern __shared__ uint64_t s_q[];
+    __shared__ uint32_t s_acc[RB][5]; // c, #{q <= max R}, #{q < M}, #{r <= max Q}, #{r < M}
+    const uint32_t q = blockIdx.x;
+    const uint32_t rb0 = a.r0 + blockIdx.y * RB, rb1 = min(rb0 + RB, a.r1);
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t qa = a.qoff[q];
+    const uint32_t nqh = (uint32_t)(a.qoff[q + 1] - qa);
+    const uint64_t *Q = a.qh + qa;
+    const uint64_t max_q = nqh ? Q[nqh - 1] : 0;
+    for (uint32_t i = threadIdx.x; i < RB * 5; i += THREADS) (&s_acc[0][0])[i] = 0;
+    for (uint32_t s0 = 0; s0 == 0 || s0 < nqh; s0 += a.slice) { // (one pass for an empty query: the reference-side counts)
+        const uint32_t ns = nqh ? min(a.slice, nqh - s0) : 0;
+        const uint32_t top = ns ? 1u << (31 - __clz(ns)) : 0;
+        __syncthreads(); // the previous slice is no longer read
+        for (uint32_t i = threadIdx.x; i < ns; i += THREADS) s_q[i] = Q[s0 + i];
+        __syncthreads();
+        for (uint32_t r = rb0 + wave; r < rb1; r += WAVES) {
+            const uint64_t ra = a.roff[r];
+            const uint32_t nrh = (uint32_t)(a.roff[r + 1] - ra);
+            const uint64_t *R = a.rh + ra;
+            uint64_t m = 0;
+            const bool has_m = pair_max_hash(a, q, r, m);
+            uint32_t c = 0, rle = 0, rlt = 0;
+            if (ns) {
+                for (uint32_t t = lane; t < nrh; t += 64) {
+                    const uint64_t x = R[t];
+                    const uint32_t p = count_below<true>(s_q, ns, top, x);
+                    const uint64_t v = s_q[p ? p - 1 : 0];
+                    c += p && v == x;
+                    rle += x <= max_q;
+                    rlt += has_m && x < m;
+                }
+            } else {
+                for (uint32_t t = lane; t < nrh; t += 64) rlt += has_m && R[t] < m;
+            }
+            c = wave_sum(c);
+            if (s0 == 0) {
+                rle = wave_sum(rle);
+                rlt = wave_sum(rlt);
+            }
+            const uint32_t qle = nrh ? count_below<true>(s_q, ns, top, R[nrh - 1]) : 0;
+            const uint32_t qlt = has_m ? count_below<false>(s_q, ns, top, m) : 0;
+            if (lane == 0) {
+                uint32_t *acc = s_acc[r - rb0];
+                acc[0] += c;
+                acc[1] += qle;
+                acc[2] += qlt;
+                if (s0 == 0) {
+                    acc[3] = rle;
+                    acc[4] = rlt;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t r = rb0 + threadIdx.x; r < rb1; r += THREADS) {
+        const uint32_t *acc = s_acc[r - rb0];
+        const uint32_t nrh = (uint32_t)(a.roff[r + 1] - a.roff[r]);
+        const bool both = nqh && nrh;
+        uint32_t i = both ? acc[1] : 0, j = both ? acc[3] : 0;
+        uint64_t m = 0;
+        if (pair_max_hash(a, q, r, m)) {
+            i = max(i, acc[2]);
+            j = max(j, acc[4]);
+        }
+        uint32_t *o = a.out + ((uint64_t)(r - a.r0) * a.nq + q) * 3;
+        o[0] = acc[0];
+        o[1] = i;
+        o[2] = j;
+    }
+}
+
+} // namespace
+
+namespace fh {
+
+struct DistDevice {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint32_t nq = 0, slice = 0, lds_slice = 0;
+    uint64_t max_pairs = 0;
+    void *dev[10] = {}; // qh qoff qmax qflag qscale rh roff rmax rflag rscale
+    uint32_t *out_d[2] = {}, *out_h[2] = {};
+    hipEvent_t ev0[2] = {}, ev1[2] = {}, done[2] = {};
+    uint32_t launched_pairs[2] = {};
+};
+
+static int upload(void **dst, const void *src, size_t bytes) {
+    const size_t b = std::max<size_t>(bytes, 8); // (an empty side still gets a valid pointer)
+    DHIP_TRY(api_dev_malloc(dst, b));
+    if (bytes) DHIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return FH_OK;
+}
+
+void dist_close(DistDevice *d) {
+    if (!d) return;
+    if (hipSetDevice(d->device) == hipSuccess) {
+        if (d->stream) (void)hipStreamSynchronize(d->stream);
+        for (void *p : d->dev)
+            if (p) (void)hipFree(p);
+        for (int b = 0; b < 2; ++b) {
+            if (d->out_d[b]) (void)hipFree(d->out_d[b]);
+            if (d->out_h[b]) (void)hipHostFree(d->out_h[b]);
+            if (d->ev0[b]) (void)hipEventDestroy(d->ev0[b]);
+            if (d->ev1[b]) (void)hipEventDestroy(d->ev1[b]);
+            if (d->done[b]) (void)hipEventDestroy(d->done[b]);
+        }
+        if (d->stream) (void)hipStreamDestroy(d->stream);
+    }
+    (void)hipGetLastError();
+    delete d;
+}
+
+static int open_into(DistDevice *d, const DistSide &q, const DistSide &r) {
+    DHIP_TRY(hipSetDevice(d->device));
+    DHIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    const DistSide *side[2] = {&q, &r};
+    for (int s = 0; s < 2; ++s) {
+        const DistSide &x = *side[s];
+        void **p = d->dev + 5 * s;
+        if (int rc = upload(&p[0], x.hashes, x.offsets[x.n] * sizeof(uint64_t))) return rc;
+        if (int rc = upload(&p[1], x.offsets, (x.n + 1) * sizeof(uint64_t))) return rc;
+        if (int rc = upload(&p[2], x.max_hash, x.n * sizeof(uint64_t))) return rc;
+        if (int rc = upload(&p[3], x.flags, x.n * sizeof(uint32_t))) return rc;
+        if (int rc = upload(&p[4], x.scale, x.n * sizeof(double))) return rc;
+    }
+    for (int b = 0; b < 2; ++b) {
+        const size_t bytes = std::max<uint64_t>(d->max_pairs, 1) * 3 * sizeof(uint32_t);
+        DHIP_TRY(api_dev_malloc((void **)&d->out_d[b], bytes));
+        DHIP_TRY(api_host_malloc((void **)&d->out_h[b], bytes));
+        DHIP_TRY(hipEventCreate(&d->ev0[b]));
+        DHIP_TRY(hipEventCreate(&d->ev1[b]));
+        DHIP_TRY(hipEventCreateWithFlags(&d->done[b], hipEventDisableTiming));
+    }
+    return FH_OK;
+}
+
+int dist_open(int device, const DistSide &q, const DistSide &r, uint32_t slice, uint64_t max_pairs, DistDevice **out) {
+    DistDevice *d = new (std::nothrow) DistDevice;
+    if (!d) return api_fail(FH_ERR_CAPACITY, "out of host memory");
+    d->device = device;
+    d->nq = q.n;
+    d->slice = std::min(std::max(slice, 1u), DIST_MAX_SLICE);
+    uint64_t longest = 1;
+    for (uint32_t s = 0; s < q.n; ++s) longest = std::max<uint64_t>(longest, q.offsets[s + 1] - q.offsets[s]);
+    d->lds_slice = (uint32_t)std::min<uint64_t>(d->slice, longest); // LDS the launch asks for: no more than the longest query
+    d->slice = d->lds_slice;
+    d->max_pairs = max_pairs;
+    if (int rc = open_into(d, q, r)) {
+        dist_close(d);
+        return rc;
+    }
+    *out = d;
+    return FH_OK;
+}
+
+int dist_launch(DistDevice *d, int buf, uint32_t r0, uint32_t r1) {
+    if (r1 < r0 || (uint64_t)(r1 - r0) * d->nq > d->max_pairs || (r1 - r0 + RB - 1) / RB > 65535u)
+        return api_fail(FH_ERR_INVALID, "dist_launch: %u references do not fit the result buffer", r1 - r0);
+    DHIP_TRY(hipSetDevice(d->device));
+    DistArgs a;
+    a.qh = (const uint64_t *)d->dev[0];
+    a.qoff = (const uint64_t *)d->dev[1];
+    a.qmax = (const uint64_t *)d->dev[2];
+    a.qflag = (const uint32_t *)d->dev[3];
+    a.qscale = (const double *)d->dev[4];
+    a.rh = (const uint64_t *)d->dev[5];
+    a.roff = (const uint64_t *)d->dev[6];
+    a.rmax = (const uint64_t *)d->dev[7];
+    a.rflag = (const uint32_t *)d->dev[8];
+    a.rscale = (const double *)d->dev[9];
+    a.nq = d->nq;
+    a.r0 = r0;
+    a.r1 = r1;
+    a.slice = d->slice;
+    a.out = d->out_d[buf];
+    const uint64_t pairs = (uint64_t)(r1 - r0) * d->nq;
+    d->launched_pairs[buf] = (uint32_t)pairs;
+    DHIP_TRY(hipEventRecord(d->ev0[buf], d->stream));
+    if (pairs) {
+        const dim3 grid(d->nq, (r1 - r0 + RB - 1) / RB);
+        hipLaunchKernelGGL(k_dist_counts, grid, dim3(THREADS), d->lds_slice * sizeof(uint64_t), d->stream, a);
+        DHIP_TRY(hipGetLastError());
+    }
+    DHIP_TRY(hipEventRecord(d->ev1[buf], d->stream));
+    if (pairs) DHIP_TRY(hipMemcpyAsync(d->out_h[buf], d->out_d[buf], pairs * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    DHIP_TRY(hipEventRecord(d->done[buf], d->stream));
+    return FH_OK;
+}
+
+int dist_wait(DistDevice *d, int buf, const uint32_t **out, double *kernel_ms) {
+    DHIP_TRY(hipSetDevice(d->device));
+    DHIP_TRY(hipEventSynchronize(d->done[buf]));
+    float ms = 0.f;
+    DHIP_TRY(hipEventElapsedTime(&ms, d->ev0[buf], d->ev1[buf]));
+    *out = d->out_h[buf];
+    if (kernel_ms) *kernel_ms = ms;
+    return FH_OK;
+}
+
+} // namespace fh

@@ -28,6 +28,7 @@
 #include <functional>
 #include <future>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "fh_host_model.h"
@@ -37,6 +38,7 @@
 #include "fh_strip.h"
 #include "fh_fqstrip.h"
 #include "fh_pack2.h"
+#include "fh_dist.h"
 
 // job(t) for t = 0 .. n - 1, one thread each (the caller's runs job(0)).  A thread that cannot be created (EAGAIN under a
 // thread limit) must not take the process down -- a vector of joinable threads that unwinds calls std::terminate -- so its
@@ -249,9 +251,18 @@ static int process_post_filter(const finch_sketch_params &sp, std::vector<KC> &k
     return FH_OK;
 }
 
-// distance.rs:66-126 (raw_distance)
-static void raw_distance(const uint64_t *q, size_t nq, const uint64_t *r, size_t nr, double scale, double &containment,
-                         double &jaccard, uint64_t &common_out, uint64_t &total_out) {
+// u64::MAX / scale.recip() as u64 (saturating float->int cast): the hash a Scaled comparison stops below (raw_distance's
+// `scale > 0` branch; finch_dist computes it once per sketch)
+static uint64_t scale_max_hash(double scale) {
+    const double rec = 1.0 / scale;
+    uint64_t irec = rec >= 18446744073709551616.0 ? UINT64_MAX : (rec <= 0.0 || rec != rec ? 0 : (uint64_t)rec);
+    return irec ? UINT64_MAX / irec : UINT64_MAX;
+}
+
+// distance.rs:66-126 (raw_distance) up to its divisions: c = common hashes, *i / *j = where the walk and the scale step left
+// the two cursors
+static void raw_counts(const uint64_t *q, size_t nq, const uint64_t *r, size_t nr, double scale, uint64_t &c, uint64_t &i_out,
+                       uint64_t &j_out) {
     size_t i = 0, j = 0;
     uint64_t common = 0;
     while (i < nq && j < nr) {
@@ -264,23 +275,17 @@ static void raw_distance(const uint64_t *q, size_t nq, const uint64_t *r, size_t
         }
     }
     if (scale > 0.) {
-        // u64::MAX / scale.recip() as u64   (saturating float->int cast)
-        const double rec = 1.0 / scale;
-        uint64_t irec = rec >= 18446744073709551616.0 ? UINT64_MAX : (rec <= 0.0 || rec != rec ? 0 : (uint64_t)rec);
-        const uint64_t max_hash = irec ? UINT64_MAX / irec : UINT64_MAX;
+        const uint64_t max_hash = scale_max_hash(scale);
         while (i < nq && q[i] < max_hash) i++;
         while (j < nr && r[j] < max_hash) j++;
     }
-    containment = j == 0 ? 0. : (double)common / (double)j;
-    const uint64_t total = (uint64_t)i - common + (uint64_t)j;
-    jaccard = total == 0 ? 1. : (double)common / (double)total;
-    common_out = common;
-    total_out = total;
+    c = common;
+    i_out = i;
+    j_out = j;
 }
 
-// distance.rs:136-157 (old_distance); the reference indexes query_sketch[0] unconditionally
-static int old_distance(const uint64_t *q, size_t nq, const uint64_t *r, size_t nr, double &containment, double &jaccard,
-                        uint64_t &common_out, uint64_t &total_out) {
+// distance.rs:136-157 (old_distance) up to its divisions; the reference indexes query_sketch[0] unconditionally
+static int old_counts(const uint64_t *q, size_t nq, const uint64_t *r, size_t nr, uint64_t &common_out, uint64_t &total_out) {
     if (nq == 0 && nr > 0) return hfail(FH_ERR_INVALID, "old_distance: empty query sketch");
     size_t i = 0;
     uint64_t common = 0, total = 0;
@@ -289,11 +294,35 @@ static int old_distance(const uint64_t *q, size_t nq, const uint64_t *r, size_t 
         if (q[i] == r[t]) common++;
         total++;
     }
-    containment = (double)common / (double)total;
-    jaccard = (double)common / (double)(common + 2 * (total - common));
     common_out = common;
     total_out = total;
     return FH_OK;
+}
+
+// The floating-point tail of distance() (distance.rs:9-47) from the integer counts: raw mode (c, i, j) of raw_counts, old mode
+// (c, total) of old_counts (j unused).  finch_distance and finch_dist both end here, so that their doubles are the same bits.
+static void distance_from_counts(bool old_mode, uint64_t c, uint64_t i, uint64_t j, uint32_t kmer_length, bool with_mash,
+                                 finch_distance_out *out) {
+    if (old_mode) {
+        const uint64_t total = i;
+        out->containment = (double)c / (double)total;
+        out->jaccard = (double)c / (double)(c + 2 * (total - c));
+        out->common_hashes = c;
+        out->total_hashes = total;
+    } else {
+        out->containment = j == 0 ? 0. : (double)c / (double)j;
+        const uint64_t total = i - c + j;
+        out->jaccard = total == 0 ? 1. : (double)c / (double)total;
+        out->common_hashes = c;
+        out->total_hashes = total;
+    }
+    if (!with_mash) {
+        out->mash_distance = 0.;
+        return;
+    }
+    const double k = (double)kmer_length;
+    const double md = -1.0 * std::log((2.0 * out->jaccard) / (1.0 + out->jaccard)) / k; // distance.rs:37
+    out->mash_distance = std::min(1.0, std::max(0.0, md));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4543,10 +4572,16 @@ int finch_apply_filters(finch_sketches *s, uint32_t i, finch_filter_params *filt
 int finch_raw_distance(const uint64_t *query, uint64_t nq, const uint64_t *ref, uint64_t nr, double scale,
                        finch_distance_out *out) try {
     if (!out || (nq && !query) || (nr && !ref)) return hfail(FH_ERR_INVALID, "null argument");
-    raw_distance(query, nq, ref, nr, scale, out->containment, out->jaccard, out->common_hashes, out->total_hashes);
-    out->mash_distance = 0.;
+    uint64_t c, i, j;
+    raw_counts(query, nq, ref, nr, scale, c, i, j);
+    distance_from_counts(false, c, i, j, 0, false, out);
     return FH_OK;
 } FINCH_CATCH
+
+// distance.rs:16-29: a scale only if both sketches are scaled
+static double pair_min_scale(const Sketch &qs, const Sketch &rs) {
+    return qs.sketch_params.kind == 1 && rs.sketch_params.kind == 1 ? std::min(qs.sketch_params.scale, rs.sketch_params.scale) : 0.;
+}
 
 int finch_distance(const finch_sketches *a, uint32_t ia, const finch_sketches *b, uint32_t ib, int old_mode,
                    finch_distance_out *out) try {
@@ -4555,20 +4590,13 @@ int finch_distance(const finch_sketches *a, uint32_t ia, const finch_sketches *b
     std::vector<uint64_t> q(qs.hashes.size()), r(rs.hashes.size());
     for (size_t i = 0; i < q.size(); ++i) q[i] = qs.hashes[i].hash;
     for (size_t i = 0; i < r.size(); ++i) r[i] = rs.hashes[i].hash;
+    uint64_t c = 0, i = 0, j = 0;
     if (old_mode) {
-        if (int rc = old_distance(q.data(), q.size(), r.data(), r.size(), out->containment, out->jaccard, out->common_hashes,
-                                  out->total_hashes))
-            return rc;
+        if (int rc = old_counts(q.data(), q.size(), r.data(), r.size(), c, i)) return rc;
     } else {
-        // distance.rs:16-29: a scale only if both sketches are scaled
-        double min_scale = 0.;
-        if (qs.sketch_params.kind == 1 && rs.sketch_params.kind == 1) min_scale = std::min(qs.sketch_params.scale, rs.sketch_params.scale);
-        raw_distance(q.data(), q.size(), r.data(), r.size(), min_scale, out->containment, out->jaccard, out->common_hashes,
-                     out->total_hashes);
+        raw_counts(q.data(), q.size(), r.data(), r.size(), pair_min_scale(qs, rs), c, i, j);
     }
-    const double k = (double)qs.sketch_params.kmer_length;
-    const double md = -1.0 * std::log((2.0 * out->jaccard) / (1.0 + out->jaccard)) / k; // distance.rs:37
-    out->mash_distance = std::min(1.0, std::max(0.0, md));
+    distance_from_counts(old_mode != 0, c, i, j, qs.sketch_params.kmer_length, true, out);
     return FH_OK;
 } FINCH_CATCH
 
@@ -4735,6 +4763,280 @@ int finch_fasta_count_chunked(const uint8_t *data, uint64_t len, uint64_t chunk,
                      (unsigned long long)fc2.total_bases);
     if (n_records) *n_records = fc.n_records;
     if (total_bases) *total_bases = fc.total_bases;
+    return FH_OK;
+} FINCH_CATCH
+
+// ---------------------------------------------------------------------------------------------
+// finch dist (cli/src/main.rs:85-125, calc_sketch_distances main.rs:315-333): every (query, reference) pair, reference-major.
+// The device computes each pair's integer counts (fh_dist.hip); distance_from_counts turns them into the doubles, as it does
+// for finch_distance.  DESIGN.md §3.7.
+// ---------------------------------------------------------------------------------------------
+} // extern "C"
+
+struct finch_dist_result {
+    struct Row {
+        uint32_t q, r;
+        finch_distance_out d;
+    };
+    std::vector<std::vector<Row>> parts; // in reference-major order
+    uint64_t n = 0;
+    std::vector<std::string> qnames, rnames;
+    double kernel_ms = 0.;
+    uint64_t launches = 0;
+};
+
+namespace {
+
+bool opt_u32_equal(uint32_t has_a, uint32_t a, uint32_t has_b, uint32_t b) { return (has_a != 0) == (has_b != 0) && (!has_a || a == b); }
+
+// Sketch's derived PartialEq (serialization/mod.rs:45): every field by value; the f64s by ==, so a NaN is not equal to itself;
+// Option<u32> by its flag, then the value; SketchParams on its own variant's fields only (padding and unused fields ignored)
+bool sketch_equal(const Sketch &a, const Sketch &b) {
+    if (a.name != b.name || a.seq_length != b.seq_length || a.num_valid_kmers != b.num_valid_kmers || a.comment != b.comment ||
+        a.hashes.size() != b.hashes.size())
+        return false;
+    const finch_filter_params &fa = a.filter_params, &fb = b.filter_params;
+    if (fa.filter_on != fb.filter_on || !opt_u32_equal(fa.has_abun_lo, fa.abun_lo, fb.has_abun_lo, fb.abun_lo) ||
+        !opt_u32_equal(fa.has_abun_hi, fa.abun_hi, fb.has_abun_hi, fb.abun_hi) || !(fa.err_filter == fb.err_filter) ||
+        !(fa.strand_filter == fb.strand_filter))
+        return false;
+    const finch_sketch_params &pa = a.sketch_params, &pb = b.sketch_params;
+    if (pa.kind != pb.kind || pa.kmer_length != pb.kmer_length) return false;
+    if (pa.kind == 0 && (pa.kmers_to_sketch != pb.kmers_to_sketch || pa.final_size != pb.final_size ||
+                         (pa.no_strict != 0) != (pb.no_strict != 0) || pa.hash_seed != pb.hash_seed))
+        return false;
+    if (pa.kind == 1 && (pa.kmers_to_sketch != pb.kmers_to_sketch || !(pa.scale == pb.scale) || pa.hash_seed != pb.hash_seed))
+        return false;
+    for (size_t i = 0; i < a.hashes.size(); ++i) {
+        const KmerCount &x = a.hashes[i], &y = b.hashes[i];
+        if (x.hash != y.hash || x.count != y.count || x.extra_count != y.extra_count || !(x.kmer == y.kmer)) return false;
+        if ((x.label != nullptr) != (y.label != nullptr) || (x.label && *x.label != *y.label)) return false;
+    }
+    return true;
+}
+
+// one side of a call in the device's form (fh_dist.h)
+struct DistCsr {
+    std::vector<uint64_t> hashes, offsets, max_hash;
+    std::vector<uint32_t> flags;
+    std::vector<double> scale;
+    void build(const std::vector<Sketch> &v, bool old_mode) {
+        offsets.assign(1, 0);
+        size_t total = 0;
+        for (const Sketch &s : v) total += s.hashes.size();
+        hashes.reserve(total);
+        for (const Sketch &s : v) {
+            for (const KmerCount &h : s.hashes) hashes.push_back(h.hash);
+            offsets.push_back(hashes.size());
+            const bool scaled = !old_mode && s.sketch_params.kind == 1, positive = scaled && s.sketch_params.scale > 0.;
+            flags.push_back((scaled ? 1u : 0u) | (positive ? 2u : 0u));
+            scale.push_back(scaled ? s.sketch_params.scale : 0.);
+            max_hash.push_back(positive ? scale_max_hash(s.sketch_params.scale) : 0);
+        }
+    }
+    fh::DistSide view() const { return fh::DistSide{hashes.data(), offsets.data(), (uint32_t)(offsets.size() - 1), max_hash.data(), flags.data(), scale.data()}; }
+};
+
+int check_ascending(const std::vector<Sketch> &v, const char *what) {
+    for (size_t s = 0; s < v.size(); ++s) {
+        const std::vector<KmerCount> &h = v[s].hashes;
+        if (h.size() >= UINT32_MAX)
+            return hfail(FH_ERR_UNSUPPORTED, "%s sketch %zu (%s) has %zu hashes (at most 2^32 - 2)", what, s, v[s].name.c_str(), h.size());
+        for (size_t j = 1; j < h.size(); ++j)
+            if (!(h[j - 1].hash < h[j].hash))
+                return hfail(FH_ERR_INVALID, "%s sketch %zu (%s): hashes not strictly ascending at %zu", what, s, v[s].name.c_str(), j);
+    }
+    return FH_OK;
+}
+
+constexpr uint32_t DIST_MAX_ENTRIES = 16; // device entries of one call, and host threads of its epilogue
+constexpr uint64_t DIST_CHUNK_PAIRS = 4u << 20; // pairs per launch: 48 MiB of counts per result buffer
+
+} // namespace
+
+extern "C" {
+
+int finch_dist(const finch_sketches *queries, const finch_sketches *refs, int old_mode, double max_distance, const int *devices,
+               uint32_t n_devices, finch_dist_result **out) try {
+    if (!queries || !refs || !out || (n_devices && !devices)) return hfail(FH_ERR_INVALID, "null argument");
+    if (n_devices > DIST_MAX_ENTRIES) return hfail(FH_ERR_INVALID, "at most %u device entries (got %u)", DIST_MAX_ENTRIES, n_devices);
+    const std::vector<Sketch> &Qs = queries->v, &Rs = refs->v;
+    if (int rc = check_ascending(Qs, "query")) return rc;
+    if (int rc = check_ascending(Rs, "reference")) return rc;
+    if (old_mode) { // old_distance refuses an empty query against a non-empty reference (no such pair is ever self-skipped)
+        bool empty_q = false, full_r = false;
+        for (const Sketch &s : Qs) empty_q = empty_q || s.hashes.empty();
+        for (const Sketch &s : Rs) full_r = full_r || !s.hashes.empty();
+        if (empty_q && full_r) return hfail(FH_ERR_INVALID, "old_distance: empty query sketch");
+    }
+    const int ndev = fh_device_count();
+    if (ndev <= 0) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
+    std::vector<int> devs = n_devices ? std::vector<int>(devices, devices + n_devices) : std::vector<int>{0};
+    for (int d : devs)
+        if (d < 0 || d >= ndev) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device: device %d requested, %d visible", d, ndev);
+
+    auto res = std::make_unique<finch_dist_result>();
+    for (const Sketch &s : Qs) res->qnames.push_back(s.name);
+    for (const Sketch &s : Rs) res->rnames.push_back(s.name);
+    const uint32_t nq = (uint32_t)Qs.size(), nr = (uint32_t)Rs.size();
+    if (nq == 0 || nr == 0) {
+        *out = res.release();
+        return FH_OK;
+    }
+    // the self-skip's first test: equal names (an id per distinct name)
+    std::unordered_map<std::string, uint32_t> ids;
+    std::vector<uint32_t> qid(nq), rid(nr);
+    for (uint32_t q = 0; q < nq; ++q) qid[q] = ids.emplace(Qs[q].name, (uint32_t)ids.size()).first->second;
+    for (uint32_t r = 0; r < nr; ++r) rid[r] = ids.emplace(Rs[r].name, (uint32_t)ids.size()).first->second;
+
+    DistCsr qc, rc_;
+    qc.build(Qs, old_mode != 0);
+    rc_.build(Rs, old_mode != 0);
+    const uint64_t chunk_pairs = std::max<uint64_t>(1, cfg_u64("dist_chunk_pairs", DIST_CHUNK_PAIRS));
+    const uint32_t per_chunk = (uint32_t)std::min<uint64_t>({std::max<uint64_t>(1, chunk_pairs / nq), nr, 65535ull * 64});
+    const uint32_t n_chunks = (nr + per_chunk - 1) / per_chunk;
+    const uint32_t n_entries = (uint32_t)devs.size();
+    const unsigned T = std::max(1u, DIST_MAX_ENTRIES / n_entries);
+    const uint32_t slice = (uint32_t)cfg_u64("dist_slice", 4096);
+    res->parts.resize((size_t)n_chunks * T);
+
+    std::mutex err_mu;
+    int err_rc = FH_OK;
+    std::string err_msg;
+    std::atomic<bool> failed{false};
+    auto fail_with = [&](int rc, const std::string &msg) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (err_rc == FH_OK) err_rc = rc, err_msg = msg;
+        failed = true;
+    };
+    std::mutex stat_mu;
+
+    // chunk k's rows: its references split over T threads
+    auto epilogue = [&](uint32_t k, const uint32_t *cnt) {
+        const uint32_t r0 = k * per_chunk, r1 = std::min(nr, r0 + per_chunk), per = (r1 - r0 + T - 1) / T;
+        fork_join(T, [&](unsigned t) {
+            try {
+                std::vector<finch_dist_result::Row> &rows = res->parts[(size_t)k * T + t];
+                const uint32_t lo = std::min(r1, r0 + t * per), hi = std::min(r1, lo + per);
+                for (uint32_t r = lo; r < hi; ++r)
+                    for (uint32_t q = 0; q < nq; ++q) {
+                        if (qid[q] == rid[r] && sketch_equal(Qs[q], Rs[r])) continue; // main.rs:324
+                        const uint32_t *x = cnt + ((size_t)(r - r0) * nq + q) * 3;
+                        finch_dist_result::Row row{q, r, {}};
+                        distance_from_counts(old_mode != 0, x[0], old_mode ? Rs[r].hashes.size() : x[1], x[2],
+                                             Qs[q].sketch_params.kmer_length, true, &row.d);
+                        if (row.d.mash_distance <= max_distance) rows.push_back(row);
+                    }
+            } catch (const std::bad_alloc &) {
+                fail_with(FH_ERR_CAPACITY, "out of host memory");
+            }
+        });
+    };
+    // one thread per device entry: chunks e, e + n_entries, ...; chunk m + 1's kernel runs while chunk m's rows are made
+    fork_join(n_entries, [&](unsigned e) {
+        fh::DistDevice *dd = nullptr;
+        try {
+            if (int rc = fh::dist_open(devs[e], qc.view(), rc_.view(), slice, (uint64_t)per_chunk * nq, &dd)) {
+                fail_with(rc, fh_last_error());
+                return;
+            }
+            std::vector<uint32_t> mine;
+            for (uint32_t k = e; k < n_chunks; k += n_entries) mine.push_back(k);
+            auto launch = [&](size_t m) {
+                const uint32_t k = mine[m], r0 = k * per_chunk;
+                return fh::dist_launch(dd, (int)(m & 1), r0, std::min(nr, r0 + per_chunk));
+            };
+            double ms_sum = 0.;
+            int rc = mine.empty() ? FH_OK : launch(0);
+            for (size_t m = 0; rc == FH_OK && m < mine.size() && !failed; ++m) {
+                if (m + 1 < mine.size() && (rc = launch(m + 1)) != FH_OK) break;
+                const uint32_t *cnt = nullptr;
+                double ms = 0.;
+                if ((rc = fh::dist_wait(dd, (int)(m & 1), &cnt, &ms)) != FH_OK) break;
+                ms_sum += ms;
+                epilogue(mine[m], cnt);
+            }
+            if (rc != FH_OK) fail_with(rc, fh_last_error());
+            std::lock_guard<std::mutex> g(stat_mu);
+            res->kernel_ms += ms_sum;
+            res->launches += mine.size();
+        } catch (const std::bad_alloc &) {
+            fail_with(FH_ERR_CAPACITY, "out of host memory");
+        }
+        fh::dist_close(dd);
+    });
+    if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
+    for (const auto &p : res->parts) res->n += p.size();
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+uint64_t finch_dist_len(const finch_dist_result *r) { return r ? r->n : 0; }
+
+int finch_dist_copy(const finch_dist_result *r, uint32_t *query_idx, uint32_t *ref_idx, finch_distance_out *rows) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    size_t o = 0;
+    for (const auto &p : r->parts)
+        for (const finch_dist_result::Row &x : p) {
+            if (query_idx) query_idx[o] = x.q;
+            if (ref_idx) ref_idx[o] = x.r;
+            if (rows) rows[o] = x.d;
+            ++o;
+        }
+    return FH_OK;
+} FINCH_CATCH
+
+// serde_json::to_writer(&Vec<SketchDistance>) (main.rs:117-121; field order serialization/mod.rs:31-43); a NaN is null
+int finch_dist_to_json(const finch_dist_result *r, char **out, uint64_t *len) try {
+    if (!r || !out) return hfail(FH_ERR_INVALID, "null argument");
+    auto f64 = [](std::string &o, double v) { o += std::isfinite(v) ? json_f64(v) : std::string("null"); };
+    std::string o = "[";
+    bool first = true;
+    for (const auto &p : r->parts)
+        for (const finch_dist_result::Row &x : p) {
+            if (!first) o.push_back(',');
+            first = false;
+            o += "{\"containment\":";
+            f64(o, x.d.containment);
+            o += ",\"jaccard\":";
+            f64(o, x.d.jaccard);
+            o += ",\"mashDistance\":";
+            f64(o, x.d.mash_distance);
+            o += ",\"commonHashes\":" + std::to_string(x.d.common_hashes);
+            o += ",\"totalHashes\":" + std::to_string(x.d.total_hashes);
+            o += ",\"query\":";
+            json_escape(o, r->qnames[x.q]);
+            o += ",\"reference\":";
+            json_escape(o, r->rnames[x.r]);
+            o.push_back('}');
+        }
+    o.push_back(']');
+    char *p = (char *)malloc(o.size() + 1);
+    if (!p) return hfail(FH_ERR_CAPACITY, "out of host memory");
+    memcpy(p, o.data(), o.size() + 1);
+    *out = p;
+    if (len) *len = o.size();
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_dist_stats(const finch_dist_result *r, double *kernel_ms, uint64_t *launches) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    if (kernel_ms) *kernel_ms = r->kernel_ms;
+    if (launches) *launches = r->launches;
+    return FH_OK;
+} FINCH_CATCH
+
+void finch_dist_free(finch_dist_result *r) { delete r; }
+
+int finch_sketches_select(const finch_sketches *s, const uint32_t *idx, uint32_t n, finch_sketches **out) try {
+    if (!s || !out || (n && !idx)) return hfail(FH_ERR_INVALID, "null argument");
+    auto res = std::make_unique<finch_sketches>();
+    res->v.reserve(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (idx[i] >= s->v.size()) return hfail(FH_ERR_INVALID, "index %u of %zu sketches", idx[i], s->v.size());
+        res->v.push_back(s->v[idx[i]]);
+    }
+    *out = res.release();
     return FH_OK;
 } FINCH_CATCH
 

@@ -81,6 +81,9 @@ const OptDef DEFS[] = {
     // --- FASTQ text in host memory ---
     {"fastq_host_strip", "0 = FASTQ text always goes to the device-side splitter; 1 = stripped on the host whatever the read threads (default: from 8 read threads on)"},
     {"fastq_strip_chunk", "bytes of text per chunk of the host-side FASTQ strip (tests: many chunks)"},
+    // --- finch_dist ---
+    {"dist_slice", "query hashes per LDS slice of the distance kernel, 1..8192 (default 4096; tests: many slices per query)"},
+    {"dist_chunk_pairs", "pairs per distance launch (default 4 M; tests: many reference chunks)"},
 };
 constexpr int N_OPTS = (int)(sizeof(DEFS) / sizeof(DEFS[0]));
 

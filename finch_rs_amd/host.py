@@ -127,6 +127,13 @@ class CDistance(C.Structure):
 
 _SYMS["finch_distance"] = (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.c_int, C.POINTER(CDistance)])
 _SYMS["finch_raw_distance"] = (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.c_double, C.POINTER(CDistance)])
+_SYMS["finch_dist"] = (C.c_int, [_P, _P, C.c_int, C.c_double, C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P)])
+_SYMS["finch_dist_len"] = (C.c_uint64, [_P])
+_SYMS["finch_dist_copy"] = (C.c_int, [_P, _P, _P, _P])
+_SYMS["finch_dist_to_json"] = (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64)])
+_SYMS["finch_dist_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)])
+_SYMS["finch_dist_free"] = (None, [_P])
+_SYMS["finch_sketches_select"] = (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)])
 _bound = None
 
 
@@ -509,3 +516,91 @@ def distance(a: Sketches, ia: int, b: Sketches, ib: int, old_mode: bool = False)
     _check(lib().finch_distance(a._p, ia, b._p, ib, int(old_mode), C.byref(d)))
     return {"containment": d.containment, "jaccard": d.jaccard, "mash_distance": d.mash_distance,
             "common_hashes": d.common_hashes, "total_hashes": d.total_hashes}
+
+
+# one row of finch_dist: the indices of the pair, then finch_distance_out's fields
+DIST_DTYPE = np.dtype([("query", np.uint32), ("reference", np.uint32), ("containment", np.float64), ("jaccard", np.float64),
+                       ("mash_distance", np.float64), ("common_hashes", np.uint64), ("total_hashes", np.uint64)])
+_CDIST_DTYPE = np.dtype([("containment", np.float64), ("jaccard", np.float64), ("mash_distance", np.float64),
+                         ("common_hashes", np.uint64), ("total_hashes", np.uint64)])
+
+
+def _dist_result(queries: Sketches, refs: Sketches, max_distance: float, old_mode: bool, devices: Sequence[int]):
+    devs = list(devices) if devices else [0]
+    darr = (C.c_int * len(devs))(*devs)
+    out = _P()
+    _check(lib().finch_dist(queries._p, refs._p, int(old_mode), float(max_distance), darr, len(devs), C.byref(out)))
+    return out
+
+
+def dist(queries: Sketches, refs: Sketches, max_distance: float = 1.0, old_mode: bool = False, devices: Sequence[int] = (0,),
+         stats: Optional[dict] = None) -> np.ndarray:
+    """calc_sketch_distances (cli/src/main.rs:315-333) on the GPU: one DIST_DTYPE row per (query, reference) pair kept, in the
+    reference's order (for each reference, for each query); `stats`, if given, receives the kernels' time and launches"""
+    L = lib()
+    p = _dist_result(queries, refs, max_distance, old_mode, devices)
+    try:
+        n = L.finch_dist_len(p)
+        qi, ri, d = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, _CDIST_DTYPE)
+        _check(L.finch_dist_copy(p, qi.ctypes.data, ri.ctypes.data, d.ctypes.data))
+        if stats is not None:
+            ms, nl = C.c_double(), C.c_uint64()
+            _check(L.finch_dist_stats(p, C.byref(ms), C.byref(nl)))
+            stats.update(kernel_ms=ms.value, launches=nl.value)
+    finally:
+        L.finch_dist_free(p)
+    rows = np.empty(n, DIST_DTYPE)
+    rows["query"], rows["reference"] = qi, ri
+    for f in _CDIST_DTYPE.names:
+        rows[f] = d[f]
+    return rows
+
+
+def dist_json(queries: Sketches, refs: Sketches, max_distance: float = 1.0, old_mode: bool = False,
+              devices: Sequence[int] = (0,)) -> str:
+    """the same rows as serde_json::to_writer(&Vec<SketchDistance>) writes them (main.rs:117-121)"""
+    L = lib()
+    p = _dist_result(queries, refs, max_distance, old_mode, devices)
+    try:
+        s, n = _P(), C.c_uint64()
+        _check(L.finch_dist_to_json(p, C.byref(s), C.byref(n)))
+        try:
+            return C.string_at(s, n.value).decode()
+        finally:
+            L.finch_free_string(s)
+    finally:
+        L.finch_dist_free(p)
+
+
+def select(sketches: Sketches, idx: Sequence[int]) -> Sketches:
+    """the sketches idx, in that order, as a collection of their own"""
+    a = np.ascontiguousarray(idx, np.uint32)
+    out = _P()
+    _check(lib().finch_sketches_select(sketches._p, a.ctypes.data if len(a) else None, len(a), C.byref(out)))
+    return Sketches(out, sketches.params)
+
+
+def dist_queries(names: Sequence[str], pairwise: bool = False, queries=None) -> Optional[List[int]]:
+    """the query selection of the `dist` subcommand (main.rs:90-113): None = every sketch (--pairwise), else the indices of
+    the sketches whose name is in `queries` (--queries), else the first sketch"""
+    if pairwise:
+        return None
+    if queries is not None:
+        wanted = set(queries)
+        return [i for i, n in enumerate(names) if n in wanted]
+    if not names:
+        raise FinchError("No sketches present!")
+    return [0]
+
+
+def dist_command(sketches: Sketches, pairwise: bool = False, queries=None, max_distance: float = 1.0, old_mode: bool = False,
+                 devices: Sequence[int] = (0,)) -> np.ndarray:
+    """`finch dist` over already opened sketches (main.rs:85-125): DIST_DTYPE rows whose query and reference both index
+    `sketches`"""
+    names = [lib().finch_sketch_name(sketches._p, i).decode(errors="surrogateescape") for i in range(len(sketches))]
+    idx = dist_queries(names, pairwise, queries)
+    if idx is None:
+        return dist(sketches, sketches, max_distance, old_mode, devices)
+    rows = dist(select(sketches, idx), sketches, max_distance, old_mode, devices)
+    rows["query"] = np.asarray(idx, np.uint32)[rows["query"]] if len(idx) else rows["query"]
+    return rows

@@ -143,6 +143,27 @@ int finch_distance(const finch_sketches *a, uint32_t ia, const finch_sketches *b
 int finch_raw_distance(const uint64_t *query, uint64_t nq, const uint64_t *ref, uint64_t nr, double scale,
                        finch_distance_out *out);
 
+/* finch dist (cli/src/main.rs:85-125, calc_sketch_distances main.rs:315-333): every (query, reference) pair in the
+ * reference's loop order -- for each reference, for each query --, skipping a pair whose two sketches are equal field by
+ * field (Sketch's derived PartialEq), keeping the rows with mash_distance <= max_distance.  Each row is bit for bit what
+ * finch_distance(queries, q, refs, r, old_mode) returns.  The set intersections run on the devices (reference ranges dealt
+ * round-robin over `devices`, NULL/0 = device 0; an entry may repeat, at most 16 entries).  FH_ERR_INVALID for a null
+ * argument, a sketch whose hashes are not strictly ascending (named in finch_last_error) and, in old_mode, an empty query
+ * next to a non-empty reference (finch_distance's error; no rows); FH_ERR_NO_DEVICE without a usable device. */
+typedef struct finch_dist_result finch_dist_result;
+int finch_dist(const finch_sketches *queries, const finch_sketches *refs, int old_mode, double max_distance, const int *devices,
+               uint32_t n_devices, finch_dist_result **out);
+uint64_t finch_dist_len(const finch_dist_result *r);
+/* row i: query index, reference index, the distance; any pointer may be NULL */
+int finch_dist_copy(const finch_dist_result *r, uint32_t *query_idx, uint32_t *ref_idx, finch_distance_out *rows);
+/* serde_json::to_writer(&Vec<SketchDistance>) (main.rs:117-121); *out is malloc'ed: finch_free_string */
+int finch_dist_to_json(const finch_dist_result *r, char **out, uint64_t *len);
+/* measurement: the kernels' time (HIP events, summed over the launches of every device entry) and the launch count */
+int finch_dist_stats(const finch_dist_result *r, double *kernel_ms, uint64_t *launches);
+void finch_dist_free(finch_dist_result *r);
+/* the sketches idx[0..n) of s, in that order (the `--queries` selection of main.rs:97-108) */
+int finch_sketches_select(const finch_sketches *s, const uint32_t *idx, uint32_t n, finch_sketches **out);
+
 /* ---- pieces that need no GPU (unit-testable on the host) ---- */
 /* Build a one-sketch result from arrays (to exercise filtering / serialisation without a device).  FH_ERR_INVALID for
  * records no sketcher can emit: count == 0 or extra_count > count (mash.rs:45-56). */
