@@ -42,12 +42,14 @@ struct DistArgs {
     uint32_t *out;
 };
 
-// the pair's scale step (distance.rs:16-29 + raw_distance's `scale > 0` test): min_scale = std::min(q, r) = r < q ? r : q --
-// an exact comparison -- and M of the chosen sketch as the host computed it
+// the pair's scale step (distance.rs:16-29 + raw_distance's `scale > 0` test): min_scale = f64::min(q, r), which ignores a NaN
+// argument (std::fmin): the reference's scale if r < q or q is NaN -- exact comparisons; both NaN picks r, which has no step --
+// and M of the chosen sketch as the host computed it
 __device__ inline bool pair_max_hash(const DistArgs &a, uint32_t q, uint32_t r, uint64_t &m) {
     const uint32_t fq = a.qflag[q], fr = a.rflag[r];
     if (!(fq & 1) || !(fr & 1)) return false;
-    const bool pick_r = a.rscale[r] < a.qscale[q];
+    const double qs = a.qscale[q], rs = a.rscale[r];
+    const bool pick_r = rs < qs || qs != qs;
     if (!((pick_r ? fr : fq) & 2)) return false;
     m = pick_r ? a.rmax[r] : a.qmax[q];
     return true;

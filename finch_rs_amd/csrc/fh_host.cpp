@@ -4578,9 +4578,9 @@ int finch_raw_distance(const uint64_t *query, uint64_t nq, const uint64_t *ref, 
     return FH_OK;
 } FINCH_CATCH
 
-// distance.rs:16-29: a scale only if both sketches are scaled
+// distance.rs:16-29: a scale only if both sketches are scaled; Rust's f64::min ignores a NaN argument, as std::fmin does
 static double pair_min_scale(const Sketch &qs, const Sketch &rs) {
-    return qs.sketch_params.kind == 1 && rs.sketch_params.kind == 1 ? std::min(qs.sketch_params.scale, rs.sketch_params.scale) : 0.;
+    return qs.sketch_params.kind == 1 && rs.sketch_params.kind == 1 ? std::fmin(qs.sketch_params.scale, rs.sketch_params.scale) : 0.;
 }
 
 int finch_distance(const finch_sketches *a, uint32_t ia, const finch_sketches *b, uint32_t ib, int old_mode,

@@ -1,6 +1,8 @@
-"""finch_dist on the GPU against the reference's loop (cli/src/main.rs:315-333) run pair by pair through finch_distance:
-the same rows in the same order, every double the same bits."""
+"""finch_dist on the GPU against the reference's loop (cli/src/main.rs:315-333) run pair by pair through finch_distance,
+and against the independent model of distance.rs (tests/dist_model.py): the same rows in the same order, every double the
+same bits."""
 import json
+import math
 import os
 import struct
 import tempfile
@@ -8,7 +10,9 @@ import tempfile
 import numpy as np
 import pytest
 
+import dist_model as M
 import finch_rs_amd as F
+from dist_model import rust_eq
 from finch_rs_amd import host as H
 from finch_rs_amd.sketch_schemes import KC_DTYPE, SketchParams
 
@@ -44,27 +48,6 @@ def collect(parts):
     return out
 
 
-def rust_eq(a, b):
-    """Sketch's derived PartialEq (serialization/mod.rs:45) on two Sketch records (Sketches._sketch_loaded)"""
-    if (a.name, a.seq_length, a.num_valid_kmers, a.comment) != (b.name, b.seq_length, b.num_valid_kmers, b.comment):
-        return False
-    fa, fb = a.filter_params, b.filter_params
-    if fa.filter_on != fb.filter_on or fa.abun_filter != fb.abun_filter:
-        return False
-    if not (fa.err_filter == fb.err_filter and fa.strand_filter == fb.strand_filter):  # f64 ==: NaN is not equal to itself
-        return False
-    pa, pb = a.sketch_params, b.sketch_params
-    if pa.kind != pb.kind or pa.kmer_length != pb.kmer_length:
-        return False
-    if pa.kind == "mash" and (pa.kmers_to_sketch, pa.final_size, pa.no_strict, pa.hash_seed) != \
-            (pb.kmers_to_sketch, pb.final_size, pb.no_strict, pb.hash_seed):
-        return False
-    if pa.kind == "scaled" and not (pa.kmers_to_sketch == pb.kmers_to_sketch and pa.scale == pb.scale and pa.hash_seed == pb.hash_seed):
-        return False
-    ka, kb = a.arrays, b.arrays
-    return np.array_equal(ka[0], kb[0]) and np.array_equal(ka[1], kb[1])
-
-
 def loop(qs, rs, old_mode=False, pairs=None):
     """the reference's loop, every pair kept (no max_distance yet): list of (q, r, dict)"""
     qsk = [qs._sketch_loaded(i) for i in range(len(qs))]
@@ -78,15 +61,55 @@ def loop(qs, rs, old_mode=False, pairs=None):
     return out
 
 
+def model_sketches(sk):
+    """the sketches as the model sees them: hashes, variant, scale, k"""
+    L = H.lib()
+    out = []
+    for i in range(len(sk)):
+        hs = np.zeros(L.finch_sketch_n_hashes(sk._p, i), np.uint64)
+        assert L.finch_sketch_copy(sk._p, i, hs.ctypes.data, None, None, None) == 0
+        p = sk.params_of(i)
+        out.append(M.Sk(hs, p.kind, p.scale if p.kind == "scaled" else 0.0, p.kmer_length))
+    return out
+
+
+def model_loop(qs, rs, old_mode=False, pairs=None, pinned=False):
+    """the model's calc_sketch_distances, every pair kept: list of (q, r, dict)"""
+    mq = model_sketches(qs)
+    mr = mq if rs is qs else model_sketches(rs)
+    L = H.lib()
+    qn = [L.finch_sketch_name(qs._p, i) for i in range(len(qs))]
+    rn = [L.finch_sketch_name(rs._p, i) for i in range(len(rs))]
+    equal = lambda q, r: qn[q] == rn[r] and rust_eq(qs._sketch_loaded(q), rs._sketch_loaded(r))  # noqa: E731
+    return M.calc_sketch_distances(mq, mr, old_mode, math.inf, equal, pairs, pinned)
+
+
+def expected(qs, rs, old_mode=False, pairs=None, pinned=False):
+    """(finch_distance's rows, the model's rows) of the reference's loop, every pair kept"""
+    return loop(qs, rs, old_mode, pairs), model_loop(qs, rs, old_mode, pairs, pinned)
+
+
+def only(want, keep):
+    return tuple([w for w in ws if keep(w)] for ws in want)
+
+
+def same_double(a, b):
+    """the same bits; any NaN matches any NaN (the model's 0 / 0 has Python's sign, the library's the hardware's)"""
+    return (a != a and b != b) or bits(a) == bits(b)
+
+
 def same_rows(rows, want, max_distance):
-    want = [w for w in want if w[2]["mash_distance"] <= max_distance]
-    assert len(rows) == len(want)
-    assert np.array_equal(rows["query"], np.array([w[0] for w in want], np.uint32))
-    assert np.array_equal(rows["reference"], np.array([w[1] for w in want], np.uint32))
-    for row, (_, _, d) in zip(rows, want):
-        for f in ("containment", "jaccard", "mash_distance"):
-            assert bits(row[f]) == bits(d[f]), (f, row, d)
-        assert int(row["common_hashes"]) == d["common_hashes"] and int(row["total_hashes"]) == d["total_hashes"], (row, d)
+    """rows = finch_distance's rows (bit for bit) and the model's rows (bit for bit, NaN for NaN), filtered by max_distance"""
+    lib_rows, model_rows = want
+    for ws, eq in ((lib_rows, lambda a, b: bits(a) == bits(b)), (model_rows, same_double)):
+        ws = [w for w in ws if w[2]["mash_distance"] <= max_distance]
+        assert len(rows) == len(ws)
+        assert np.array_equal(rows["query"], np.array([w[0] for w in ws], np.uint32))
+        assert np.array_equal(rows["reference"], np.array([w[1] for w in ws], np.uint32))
+        for row, (_, _, d) in zip(rows, ws):
+            for f in ("containment", "jaccard", "mash_distance"):
+                assert eq(row[f], d[f]), (f, row, d)
+            assert int(row["common_hashes"]) == d["common_hashes"] and int(row["total_hashes"]) == d["total_hashes"], (row, d)
 
 
 def pool_sketches(n, rng, size=1000, groups=12, prefix="s"):
@@ -106,16 +129,16 @@ def pool_sketches(n, rng, size=1000, groups=12, prefix="s"):
 @pytest.fixture(scope="module")
 def mixed():
     sk = pool_sketches(400, np.random.default_rng(11))
-    return sk, loop(sk, sk)
+    return sk, expected(sk, sk)
 
 
 @pytest.mark.parametrize("which", ["1.0", "0.05", "0.0", "pair"])
 def test_mixed_overlaps(mixed, which):
     sk, want = mixed
-    js = np.array([w[2]["jaccard"] for w in want])
+    js = np.array([w[2]["jaccard"] for w in want[0]])
     assert js.min() == 0.0 and js.max() > 0.9
     if which == "pair":  # exactly one pair's distance: the comparison is <=
-        mids = sorted(w[2]["mash_distance"] for w in want if 0 < w[2]["mash_distance"] < 1)
+        mids = sorted(w[2]["mash_distance"] for w in want[0] if 0 < w[2]["mash_distance"] < 1)
         assert len(mids) > 100
         md = mids[len(mids) // 2]
     else:
@@ -156,13 +179,13 @@ def shape_sketches():
 @pytest.fixture(scope="module")
 def shapes():
     sk = shape_sketches()
-    return sk, loop(sk, sk)
+    return sk, expected(sk, sk)
 
 
 @pytest.mark.parametrize("slice_, chunk", [(None, None), ("7", "5"), ("64", None)])
 def test_sketch_shapes(shapes, slice_, chunk):
     sk, want = shapes
-    assert any(w[2]["total_hashes"] != 0 and w[2]["containment"] not in (0.0, 1.0) for w in want)
+    assert any(w[2]["total_hashes"] != 0 and w[2]["containment"] not in (0.0, 1.0) for w in want[0])
     try:
         F.set_option("dist_slice", slice_)
         F.set_option("dist_chunk_pairs", chunk)
@@ -176,13 +199,13 @@ def test_sketch_shapes_old_mode(shapes):
     sk, _ = shapes
     full = [i for i in range(len(sk)) if H.lib().finch_sketch_n_hashes(sk._p, i) > 0]
     qs = H.select(sk, full)
-    same_rows(H.dist(qs, sk, old_mode=True), loop(qs, sk, old_mode=True), 1.0)
+    same_rows(H.dist(qs, sk, old_mode=True), expected(qs, sk, old_mode=True), 1.0)
     # empty against empty is 0 / 0 in old mode
     empties = [i for i in range(len(sk)) if H.lib().finch_sketch_n_hashes(sk._p, i) == 0]
     e = H.select(sk, empties)
     rows = H.dist(e, e, old_mode=True)
-    want = loop(e, e, old_mode=True)
-    assert len(want) == 2 and np.isnan(want[0][2]["containment"])
+    want = expected(e, e, old_mode=True)
+    assert len(want[0]) == 2 and np.isnan(want[0][0][2]["containment"]) and np.isnan(want[1][0][2]["containment"])
     same_rows(rows, want, 1.0)
 
 
@@ -210,7 +233,7 @@ def test_self_skip():
     for a, b in [(0, 2), (2, 0), (0, 3), (3, 0), (4, 4), (0, 4), (0, 5), (5, 0), (3, 3), (2, 2)]:
         assert ((a, b) in got) == (a == b == 4 or a != b), (a, b)
     assert (4, 4) in got and (3, 3) not in got and (2, 2) not in got
-    same_rows(rows, loop(sk, sk), 1.0)
+    same_rows(rows, expected(sk, sk), 1.0)
 
 
 def test_end_to_end_files():
@@ -229,7 +252,8 @@ def test_end_to_end_files():
             paths.append(p)
         sk = H.sketch_files(paths, SketchParams.mash(), H.FilterParams(False))
     rows = H.dist_command(sk, pairwise=True)
-    same_rows(rows, loop(sk, sk), 1.0)
+    want = expected(sk, sk)
+    same_rows(rows, want, 1.0)
     text = H.dist_json(sk, sk)
     parsed = json.loads(text, object_pairs_hook=lambda kv: kv)
     assert len(parsed) == len(rows)
@@ -243,7 +267,7 @@ def test_end_to_end_files():
         assert v["query"] == names[row["query"]] and v["reference"] == names[row["reference"]]
     # --queries and the default (the first sketch only)
     qrows = H.dist_command(sk, queries={names[3], names[100]}, max_distance=0.02)
-    same_rows(qrows, [w for w in loop(sk, sk) if w[0] in (3, 100)], 0.02)
+    same_rows(qrows, only(want, lambda w: w[0] in (3, 100)), 0.02)
     frows = H.dist_command(sk)
     assert set(frows["query"].tolist()) == {0} and len(frows) == len(sk) - 1
 
@@ -276,9 +300,189 @@ def test_size_3000_pairwise():
     q = q[q != np.repeat(np.arange(n, dtype=np.uint32), n)]
     assert np.array_equal(rows["reference"], r) and np.array_equal(rows["query"], q)
     pick = np.sort(rng.choice(len(rows), 50000, replace=False))
+    ms = model_sketches(sk)
     for i in pick:
         row = rows[i]
-        d = H.distance(sk, int(row["query"]), sk, int(row["reference"]))
-        for f in FIELDS[:3]:
-            assert bits(row[f]) == bits(d[f])
-        assert int(row["common_hashes"]) == d["common_hashes"] and int(row["total_hashes"]) == d["total_hashes"]
+        q, r = int(row["query"]), int(row["reference"])
+        for d in (H.distance(sk, q, sk, r), M.distance(ms[q], ms[r])):
+            for f in FIELDS[:3]:
+                assert bits(row[f]) == bits(d[f]), (f, row, d)
+            assert int(row["common_hashes"]) == d["common_hashes"] and int(row["total_hashes"]) == d["total_hashes"]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Scaled sketches over many scales: 1 / scale not an integer, no scale step, saturation (M = 1), NaN on either side
+# ----------------------------------------------------------------------------------------------------------------------
+
+SCALES = [0.001, 0.01, 0.3, 1.0, 0.0, -0.5, 1e-20, 5e-324, float("nan")]
+
+
+def scaled_set():
+    """about 300 sketches: ~30 Scaled per scale, hashes clustered around every M (and 0, u64::MAX), and some Mash ones;
+    k mixed (k comes from the query); two sketches repeated under the same name (one with a NaN scale, never equal)"""
+    rng = np.random.default_rng(17)
+    centres = sorted({M.max_hash(s) for s in SCALES if s > 0} | {0, U64_MAX})
+    pool = [np.array([0, 1, 2, U64_MAX - 1, U64_MAX], np.uint64)]
+    for c in centres:
+        lo, hi = max(0, c - 3000), min(U64_MAX, c + 3000)
+        pool.append(rng.integers(lo, hi, 2000, dtype=np.uint64, endpoint=True))
+        pool.append(np.array([x for x in (c - 1, c, c + 1) if 0 <= x <= U64_MAX], np.uint64))
+    pool.append(rng.integers(0, U64_MAX, 3000, dtype=np.uint64))
+    pool = np.unique(np.concatenate(pool))
+    out, n = [], 0
+    for s in SCALES:
+        for _ in range(30):
+            size = [0, 1, 2, 40, 150, 400][rng.integers(0, 6)]
+            hs = np.sort(rng.choice(pool, size, replace=False))
+            k = [21, 15, 31][rng.integers(0, 3)]
+            out.append(mk("sc%d" % n, hs, SketchParams.scaled(max(1, len(hs)), k, s)))
+            n += 1
+    for _ in range(30):
+        hs = np.sort(rng.choice(pool, [0, 5, 200][rng.integers(0, 3)], replace=False))
+        out.append(mk("mash%d" % n, hs, SketchParams.mash(kmer_length=[21, 17][rng.integers(0, 2)], no_strict=True)))
+        n += 1
+    nan_one = next(i for i, s in enumerate(out) if s.params.scale != s.params.scale and H.lib().finch_sketch_n_hashes(s._p, 0) > 1)
+    out.append(mk("sc%d" % nan_one, out[nan_one].sketch(0).arrays[0]["hash"], out[nan_one].params))
+    out.append(mk("sc1", out[1].sketch(0).arrays[0]["hash"], out[1].params))
+    return collect(out)
+
+
+@pytest.fixture(scope="module")
+def scaled():
+    sk = scaled_set()
+    return sk, expected(sk, sk)
+
+
+def test_scaled_set_pairwise(scaled):
+    sk, want = scaled
+    ms = model_sketches(sk)
+    n, n_nan = len(sk), sum(s.scale != s.scale for s in ms)
+    # every sketch skips itself but those with a NaN scale (f64 ==); "sc1" and its copy are equal both ways, the NaN-scale
+    # copy is not equal to its original
+    assert n_nan == 31 and len(want[0]) == n * n - (n - n_nan) - 2
+    rows = H.dist(sk, sk)
+    same_rows(rows, want, 1.0)
+    # a NaN query against a Scaled reference with a step takes the reference's M, and that changes counts
+    nan_q = [(ms[q].hashes, ms[r].hashes, M.max_hash(ms[r].scale)) for q, r, _ in want[1]
+             if ms[q].scale != ms[q].scale and ms[r].kind == "scaled" and ms[r].scale > 0]
+    assert sum(M.counts(a, b) != M.counts(a, b, m) for a, b, m in nan_q) > 100
+
+
+def test_scaled_set_max_distance_on_one_row(scaled):
+    sk, want = scaled
+    vals = [w[2]["mash_distance"] for w in want[1]]
+    once = sorted(v for v, c in zip(*np.unique(vals, return_counts=True)) if c == 1 and 0 < v < 1)
+    assert len(once) > 10
+    md = float(once[len(once) // 2])
+    rows = H.dist(sk, sk, max_distance=md)
+    same_rows(rows, want, md)
+    assert np.sum(rows["mash_distance"] == md) == 1
+
+
+def test_scaled_set_old_mode(scaled):
+    sk, _ = scaled
+    full = [i for i in range(len(sk)) if H.lib().finch_sketch_n_hashes(sk._p, i) > 0]
+    qs = H.select(sk, full)
+    same_rows(H.dist(qs, sk, old_mode=True), expected(qs, sk, old_mode=True), 1.0)
+
+
+def test_scales_where_the_reference_panics():
+    """scale > 1 or +inf: the reference divides by zero; the library's documented M = u64::MAX, on both paths"""
+    rng = np.random.default_rng(8)
+    out = []
+    for n, s in enumerate([2.0, 1.5, float("inf"), 3.0, 0.5]):
+        hs = np.unique(np.concatenate([rng.integers(0, U64_MAX, 50, dtype=np.uint64),
+                                       np.array([0, M.max_hash(0.5), U64_MAX - 1, U64_MAX][: 1 + n % 4], np.uint64)]))
+        out.append(mk("p%d" % n, hs, SketchParams.scaled(len(hs), 21, s)))
+    sk = collect(out)
+    same_rows(H.dist(sk, sk), expected(sk, sk, pinned=True), 1.0)
+
+
+def test_json_zero_distance():
+    hs = [3, 9, 27]
+    sk = collect([mk("a", hs), mk("b", hs)])
+    rows = H.dist(sk, sk)
+    assert len(rows) == 2 and all(bits(x) == bits(0.0) for x in rows["mash_distance"])
+    assert H.dist_json(sk, sk).count('"mashDistance":0.0,') == 2
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# LDS slices, grid and chunk edges
+# ----------------------------------------------------------------------------------------------------------------------
+
+QUERY_LENGTHS = [1, 2, 63, 64, 65, 4095, 4096, 4097, 8191, 8192, 8193, 20000]
+
+
+@pytest.fixture(scope="module")
+def slice_edges():
+    """queries of lengths around powers of two and the slice cap; references of 0..200 hashes, partly from the queries'
+    pool; two thirds Scaled at 0.01 with the hashes around its M, so that the scale step's counts cross slices too"""
+    rng = np.random.default_rng(23)
+    m = M.max_hash(0.01)
+    pool = np.unique(np.concatenate([rng.integers(0, 2 * m, 60000, dtype=np.uint64), np.array([m - 1, m, m + 1], np.uint64)]))
+
+    def params(i, n):
+        return SketchParams.scaled(max(1, n), [21, 15][i % 2], 0.01) if i % 3 else SketchParams.mash(kmer_length=21, no_strict=True)
+    qs = collect([mk("q%d" % i, np.sort(rng.choice(pool, n, replace=False)), params(i, n)) for i, n in enumerate(QUERY_LENGTHS)])
+    refs = []
+    for n in range(201):
+        own = rng.choice(pool, n, replace=False)
+        fresh = rng.integers(0, U64_MAX, n // 4, dtype=np.uint64)
+        hs = np.unique(np.concatenate([own, fresh]))[:n] if n % 5 else np.sort(own)
+        refs.append(mk("r%d" % n, hs, params(n + 1, n)))
+    rs = collect(refs)
+    return qs, rs, expected(qs, rs)
+
+
+@pytest.mark.parametrize("slice_", [None, "1", "8192", "100000"])
+def test_slice_edges(slice_edges, slice_):
+    qs, rs, want = slice_edges
+    try:
+        F.set_option("dist_slice", slice_)
+        same_rows(H.dist(qs, rs), want, 1.0)
+    finally:
+        F.set_option("dist_slice", None)
+
+
+@pytest.fixture(scope="module")
+def grid_set():
+    rng = np.random.default_rng(31)
+    return pool_sketches(7, rng, size=300, groups=3, prefix="q"), pool_sketches(257, rng, size=200, groups=3, prefix="r")
+
+
+@pytest.mark.parametrize("nr", [1, 63, 64, 65, 257])
+def test_reference_counts(grid_set, nr):
+    qs, refs = grid_set
+    rs = H.select(refs, list(range(nr)))
+    same_rows(H.dist(qs, rs), expected(qs, rs), 1.0)
+
+
+def test_one_query_many_references():
+    """the default `finch dist` shape: the first sketch against all of them"""
+    sk = pool_sketches(5001, np.random.default_rng(37), size=100, groups=8)
+    rows = H.dist_command(sk)
+    assert len(rows) == 5000
+    same_rows(rows, expected(sk, sk, pairs=[(0, r) for r in range(5001)]), 1.0)
+
+
+def test_many_queries_few_references():
+    rng = np.random.default_rng(41)
+    qs = pool_sketches(2000, rng, size=60, groups=4, prefix="q")
+    rs = pool_sketches(3, rng, size=60, groups=4, prefix="r")
+    same_rows(H.dist(qs, rs), expected(qs, rs), 1.0)
+
+
+@pytest.mark.parametrize("devices, chunk, launches", [([0], "10", 20), ([0, 0, 0], "10", 20), ([0, 0, 0], "80", 10)])
+def test_chunks_below_the_query_count(devices, chunk, launches):
+    """dist_chunk_pairs < queries: one reference per launch; three entries on one device with 20 or 10 chunks"""
+    rng = np.random.default_rng(43)
+    qs = pool_sketches(40, rng, size=150, groups=4, prefix="q")
+    rs = pool_sketches(20, rng, size=150, groups=4, prefix="r")
+    st = {}
+    try:
+        F.set_option("dist_chunk_pairs", chunk)
+        rows = H.dist(qs, rs, devices=devices, stats=st)
+    finally:
+        F.set_option("dist_chunk_pairs", None)
+    assert st["launches"] == launches
+    same_rows(rows, expected(qs, rs), 1.0)
