@@ -10,7 +10,7 @@ SO_PATH = os.environ.get("FH_LIB", os.path.join(_HERE, "libfinch_hip.so"))
 
 FH_OK = 0
 FH_ERR_INVALID, FH_ERR_NO_DEVICE, FH_ERR_HIP, FH_ERR_STATE, FH_ERR_CAPACITY, FH_ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
-KIND_MASH, KIND_SCALED = 0, 1
+KIND_MASH, KIND_SCALED, KIND_ALL_COUNTS = 0, 1, 2
 
 
 class FhParams(C.Structure):

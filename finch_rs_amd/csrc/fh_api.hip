@@ -23,6 +23,7 @@
 
 #include "../../include/finch_hip.h"
 #include "fh_core.h"
+#include "fh_counts.h"
 #include "fh_strip.h"
 #include "fh_device.h"
 #include "fh_kernels.h"
@@ -316,6 +317,15 @@ struct fh_sketcher {
     bool res_built = false;
     std::vector<ResultRec> res;
     uint64_t total_kmers = 0;
+
+    // AllCounts (FH_KIND_ALL_COUNTS, fh_counts.hip): the 4^k forward counts, one wrap bit per bin, the finishing passes'
+    // block counts and offsets, [rows, num_valid_kmers] (device and pinned), the rows (hash, count, extra; ac_out_cap each)
+    uint32_t *ac_table = nullptr, *ac_sat = nullptr, *ac_blk_cnt = nullptr;
+    uint64_t *ac_blk_off = nullptr, *ac_tot = nullptr, *h_ac_tot = nullptr, *ac_out = nullptr;
+    uint64_t ac_out_cap = 0;
+    uint64_t ac_windows = 0; // windows counted since the reset: below 2^32 in all, no bin can wrap (non-returning atomics)
+    bool ac_check = false;   // a merge or fh_debug_add_counts has moved the counts: every add checks for the wrap
+    bool ac_dirty = false;   // the table holds counts (fh_reset clears it)
 };
 
 namespace {
@@ -988,9 +998,50 @@ int sampled_first_block(fh_sketcher *s, const uint8_t *d_seq, uint64_t len, uint
     return FH_OK;
 }
 
+// AllCounts: windows [0, len - k + 1) of the block into the histogram (fh_counts.hip), in launches of at most 2^30 windows (a
+// workgroup's LDS counters cannot wrap).  No stride probe, speculation or sampling: they serve the hash path.
+int ac_count_block(fh_sketcher *s, const uint8_t *d_seq, uint64_t len) {
+    const uint64_t n_pos = len - s->p.k + 1;
+    constexpr uint64_t LAUNCH_WINDOWS = 1ull << 30;
+    for (uint64_t p = 0; p < n_pos; p += LAUNCH_WINDOWS) {
+        AcCountArgs a{};
+        a.seq = d_seq;
+        a.len = len;
+        a.p_begin = p;
+        a.p_end = std::min(n_pos, p + LAUNCH_WINDOWS);
+        a.table = s->ac_table;
+        a.sat = s->ac_sat;
+        s->ac_windows += a.p_end - a.p_begin;
+        a.check = (s->ac_check || s->ac_windows >= (1ull << 32)) ? 1u : 0u;
+        hipEvent_t e1 = nullptr;
+        if (s->profiling) {
+            if (s->prof_used == s->prof_events.size()) {
+                hipEvent_t a0, a1;
+                HIP_TRY(hipEventCreate(&a0));
+                HIP_TRY(hipEventCreate(&a1));
+                s->prof_events.emplace_back(a0, a1);
+            }
+            e1 = s->prof_events[s->prof_used].second;
+            HIP_TRY(hipEventRecord(s->prof_events[s->prof_used].first, s->stream));
+            s->prof_used++;
+        }
+        HIP_TRY(launch_ac_count((int)s->p.k, a, s->stream));
+        if (e1) {
+            HIP_TRY(hipEventRecord(e1, s->stream));
+            s->prof_launches++;
+            s->prof_positions += a.p_end - a.p_begin;
+        }
+        s->n_launches++;
+    }
+    s->positions_done += n_pos;
+    s->ac_dirty = true;
+    return FH_OK;
+}
+
 int sketch_device_range(fh_sketcher *s, const uint8_t *d_seq, uint64_t len, uint64_t base_pos) {
     if (int rc = drain(s)) return rc;
     if (len < s->p.k) return FH_OK;
+    if (s->p.kind == FH_KIND_ALL_COUNTS) return ac_count_block(s, d_seq, len);
     const uint64_t n_pos = len - s->p.k + 1; // windows that fit
     // Records of one length?  Then the segment kernel skips what every record's last k positions cannot hold (fh_k2s.hip).  The
     // caller may have said so (fh_set_record_stride); a large block is asked itself -- one wavefront, one round trip (~20 us:
@@ -1546,6 +1597,7 @@ uint64_t handle_bytes(const fh_sketcher *s) {
     for (int i = 0; i < N_STAGE; ++i) b += 2 * s->stage_cap[i];
     if (s->bz_text_cap) b += s->bz_comp_cap + 4 * s->bz_text_cap + s->bz_text_cap / 2;
     b += 2 * s->gz_sym_elems + (uint64_t)s->gz_chunks_cap * (GZ_WINDOW + 48) + (s->gz_summary ? (uint64_t)GZ_GROUPS * GZ_WINDOW * 3 : 0);
+    if (s->ac_table) b += ac_bins((int)s->p.k) * 4 + ac_bins((int)s->p.k) / 8 + ac_fin_blocks((int)s->p.k) * 12 + s->ac_out_cap * 16;
     return b + (uint64_t)s->out_cap * 32 + (uint64_t)s->big_cap * 24;
 }
 bool same_params(const fh_params &a, const fh_params &b) {
@@ -1569,6 +1621,13 @@ void fh_release_cached(void) {
 static fh_sketcher *new_handle(const fh_params *params, int device);
 
 fh_sketcher *fh_new(const fh_params *params, int device) {
+    fh_params ac_params;
+    if (params && params->kind == FH_KIND_ALL_COUNTS) { // (size, seed and scale mean nothing to AllCounts: any values pool together)
+        ac_params = *params;
+        ac_params.size = ac_params.seed = 0;
+        ac_params.scale = 0.0;
+        params = &ac_params;
+    }
     if (params && pool_max()) {
         std::lock_guard<std::mutex> g(g_pool_mu);
         for (size_t i = 0; i < g_pool.size(); ++i) {
@@ -1628,11 +1687,20 @@ static fh_sketcher *new_handle(const fh_params *params, int device) {
         fail(FH_ERR_INVALID, "params is NULL");
         return nullptr;
     }
+    if (params->kind == FH_KIND_ALL_COUNTS && params->k > (uint32_t)AC_MAX_K) {
+        fail(FH_ERR_UNSUPPORTED, "AllCounts sketches take kmer_length 1..%d (a table of 4^k u32 counts: 16 GiB at k = %d), not %u",
+             AC_MAX_K, AC_MAX_K, params->k);
+        return nullptr;
+    }
+    if (params->kind == FH_KIND_ALL_COUNTS && params->hash_mask) {
+        fail(FH_ERR_INVALID, "hash_mask is a test hook of the hashing sketchers: AllCounts sketches have no hash to mask");
+        return nullptr;
+    }
     if (params->k < 1 || params->k > (uint32_t)FH_MAX_K) {
         fail(FH_ERR_UNSUPPORTED, "kmer_length %u outside the device range 1..%d", params->k, FH_MAX_K);
         return nullptr;
     }
-    if (params->kind != FH_KIND_MASH && params->kind != FH_KIND_SCALED) {
+    if (params->kind != FH_KIND_MASH && params->kind != FH_KIND_SCALED && params->kind != FH_KIND_ALL_COUNTS) {
         fail(FH_ERR_INVALID, "unknown sketch kind %u", params->kind);
         return nullptr;
     }
@@ -1726,6 +1794,17 @@ static fh_sketcher *new_handle(const fh_params *params, int device) {
         destroy_handle(s);
         return nullptr;
     }
+    if (params->kind == FH_KIND_ALL_COUNTS) { // (the pushes, staging and text paths above are shared; the histogram is its own)
+        const uint64_t bins = ac_bins((int)params->k), sat_bytes = std::max<uint64_t>(bins / 8, 4);
+        if ((e = dev_malloc(&s->ac_table, bins * 4)) != hipSuccess) return bail("hipMalloc(AllCounts table)", e);
+        if ((e = dev_malloc(&s->ac_sat, sat_bytes)) != hipSuccess) return bail("hipMalloc(AllCounts wrap bits)", e);
+        if ((e = dev_malloc(&s->ac_blk_cnt, ac_fin_blocks((int)params->k) * 4)) != hipSuccess) return bail("hipMalloc(AllCounts blocks)", e);
+        if ((e = dev_malloc(&s->ac_blk_off, ac_fin_blocks((int)params->k) * 8)) != hipSuccess) return bail("hipMalloc(AllCounts offsets)", e);
+        if ((e = dev_malloc(&s->ac_tot, 16)) != hipSuccess) return bail("hipMalloc(AllCounts totals)", e);
+        if ((e = host_malloc(&s->h_ac_tot, 16)) != hipSuccess) return bail("hipHostMalloc(AllCounts totals)", e);
+        if ((e = hipMemsetAsync(s->ac_table, 0, bins * 4, s->stream)) != hipSuccess) return bail("hipMemset(AllCounts table)", e);
+        if ((e = hipMemsetAsync(s->ac_sat, 0, sat_bytes, s->stream)) != hipSuccess) return bail("hipMemset(AllCounts wrap bits)", e);
+    }
     if ((e = hipStreamSynchronize(s->stream)) != hipSuccess) return bail("hipStreamSynchronize", e);
     return s;
 }
@@ -1807,6 +1886,13 @@ void destroy_handle(fh_sketcher *s) {
     if (s->h_rows) (void)hipHostFree(s->h_rows);
     if (s->h_rows_out) (void)hipHostFree(s->h_rows_out);
     (void)hipFree(s->kmer_hi);
+    (void)hipFree(s->ac_table);
+    (void)hipFree(s->ac_sat);
+    (void)hipFree(s->ac_blk_cnt);
+    (void)hipFree(s->ac_blk_off);
+    (void)hipFree(s->ac_tot);
+    (void)hipFree(s->ac_out);
+    if (s->h_ac_tot) (void)hipHostFree(s->h_ac_tot);
     (void)hipFree(s->smp_list);
     (void)hipFree(s->smp_hist);
     if (s->h_smp_hist) (void)hipHostFree(s->h_smp_hist);
@@ -1825,6 +1911,13 @@ int fh_reset(fh_sketcher *s) {
     if (!s) return fail(FH_ERR_INVALID, "null handle");
     if (int rc = set_device(s)) return rc;
     gzip_quiesce(s); // (a launch that waits for the rest of an abandoned batch holds the stream until it is told to give up)
+    if (s->ac_table && (s->ac_dirty || s->ac_check)) {
+        const uint64_t bins = ac_bins((int)s->p.k);
+        HIP_TRY(hipMemsetAsync(s->ac_table, 0, bins * 4, s->stream));
+        HIP_TRY(hipMemsetAsync(s->ac_sat, 0, std::max<uint64_t>(bins / 8, 4), s->stream));
+    }
+    s->ac_dirty = s->ac_check = false;
+    s->ac_windows = 0;
     if (s->device_clean && s->finished && !s->pend.active && !s->epi_pending) { // fh_finish's epilogue has done the device side
         s->device_clean = false;
         return init_state(s, false);
@@ -2859,9 +2952,86 @@ static int ensure_records(fh_sketcher *s) {
     return FH_OK;
 }
 
+// AllCounts to_vec (counts.rs:43-64) on the device: fold, mark, scan, compact; the rows then cross in three copies.  The
+// result arrays are the hashing sketchers' (r_*): the k-mer of a row IS its hash (the m-form index), first_pos is 0.
+static int ac_finish(fh_sketcher *s) {
+    const int k = (int)s->p.k;
+    if (int rc = check_ctl(s)) return rc; // (everything queued has run; the text packers' base count is final)
+    HIP_TRY(launch_ac_mark(s->ac_table, s->ac_sat, k, s->ac_blk_cnt, s->ac_blk_off, s->ac_tot, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_ac_tot, s->ac_tot, 16, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const uint64_t n = s->h_ac_tot[0];
+    if (n > s->ac_out_cap) {
+        (void)hipFree(s->ac_out);
+        s->ac_out = nullptr;
+        s->ac_out_cap = 0;
+        HIP_TRY(dev_malloc(&s->ac_out, n * 16 + 64));
+        s->ac_out_cap = n;
+    }
+    uint64_t *o_hash = s->ac_out;
+    uint32_t *o_count = (uint32_t *)(o_hash + s->ac_out_cap), *o_extra = o_count + s->ac_out_cap;
+    if (n) HIP_TRY(launch_ac_compact(s->ac_table, k, s->ac_blk_off, o_hash, o_count, o_extra, s->stream));
+    const size_t need = n * 24 + 64;
+    if (need > s->h_out_bytes) {
+        if (s->h_out) (void)hipHostFree(s->h_out);
+        s->h_out = nullptr;
+        s->h_out_bytes = 0;
+        HIP_TRY(host_malloc(&s->h_out, need + need / 4));
+        s->h_out_bytes = need + need / 4;
+    }
+    uint64_t *hh = (uint64_t *)s->h_out, *pp = hh + n;
+    uint32_t *cc = (uint32_t *)(pp + n), *ee = cc + n;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(hh, o_hash, n * 8, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(cc, o_count, n * 4, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(ee, o_extra, n * 4, hipMemcpyDeviceToHost, s->stream));
+    }
+    memset(pp, 0, n * 8);
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (int rc = collect_profile(s)) return rc;
+    s->r_hash = hh; s->r_kmer = hh; s->r_pos = pp; s->r_count = cc; s->r_extra = ee;
+    s->r_kmer_hi = nullptr;
+    s->r_n = n;
+    s->res.clear();
+    s->res_built = false;
+    s->wide_pending = false;
+    s->total_kmers = s->h_ac_tot[1];
+    s->final_text_bases = s->h_ctl->text_bases;
+    s->finished = true;
+    return FH_OK;
+}
+
+// fh_merge of two AllCounts handles: dst's forward counts += src's (saturating), then to_vec again
+static int ac_merge(fh_sketcher *dst, const fh_sketcher *src) {
+    if (!dst->finished) return fail(FH_ERR_STATE, "fh_merge: dst not finished");
+    if (int rc = set_device(dst)) return rc;
+    const uint64_t bytes = ac_bins((int)dst->p.k) * 4;
+    uint32_t *from = src->ac_table, *tmp = nullptr;
+    if (src->device != dst->device) { // (src is finished: its stream is idle)
+        HIP_TRY(dev_malloc(&tmp, bytes));
+        HIP_TRY(hipMemcpyPeerAsync(tmp, dst->device, src->ac_table, src->device, bytes, dst->stream));
+        from = tmp;
+    }
+    hipError_t e = launch_ac_add(dst->ac_table, from, ac_bins((int)dst->p.k), dst->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(dst->stream);
+    (void)hipFree(tmp);
+    if (e != hipSuccess) return fail(FH_ERR_HIP, "fh_merge (AllCounts): %s", hipGetErrorString(e));
+    dst->ac_check = dst->ac_dirty = true;
+    return ac_finish(dst);
+}
+
 int fh_finish(fh_sketcher *s, uint64_t *n_out, uint64_t *total_kmers) {
     if (!s) return fail(FH_ERR_INVALID, "null handle");
     if (int rc = set_device(s)) return rc;
+    if (s->p.kind == FH_KIND_ALL_COUNTS) {
+        if (!s->finished) {
+            if (int rc = proc_flush(s)) return rc;
+            if (int rc = ac_finish(s)) return rc;
+        }
+        if (n_out) *n_out = s->r_n;
+        if (total_kmers) *total_kmers = s->total_kmers;
+        return FH_OK;
+    }
     static const bool trace = cfg("trace") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -3162,6 +3332,8 @@ int fh_merge_arrays(fh_sketcher *dst, uint64_t n, const uint64_t *hashes, const 
     if (!dst || (n && (!hashes || !counts || !extra_counts || !kmers || !first_pos)))
         return fail(FH_ERR_INVALID, "null argument");
     if (!dst->finished) return fail(FH_ERR_STATE, "fh_merge: dst not finished");
+    if (dst->p.kind == FH_KIND_ALL_COUNTS)
+        return fail(FH_ERR_UNSUPPORTED, "fh_merge_arrays: AllCounts sketches are merged as forward tables (fh_merge), not as to_vec rows");
     const int k = (int)dst->p.k;
     std::vector<ResultRec> src(n), out;
     for (uint64_t j = 0; j < n; ++j)
@@ -3179,6 +3351,8 @@ int fh_merge_partials(uint32_t kind, uint64_t size, double scale, uint32_t k, ui
                       uint64_t nB, const uint64_t *hashesB, const uint32_t *countsB, const uint32_t *extraB,
                       const uint8_t *kmersB, const uint64_t *posB, uint64_t *n_out, uint64_t *out_hashes,
                       uint32_t *out_counts, uint32_t *out_extra, uint8_t *out_kmers, uint64_t *out_pos) {
+    if (kind == FH_KIND_ALL_COUNTS)
+        return fail(FH_ERR_UNSUPPORTED, "fh_merge_partials: AllCounts sketches are merged as forward tables (fh_merge), not as to_vec rows");
     if (!n_out || k < 1 || k > (uint32_t)FH_MAX_K || (kind != FH_KIND_MASH && kind != FH_KIND_SCALED))
         return fail(FH_ERR_INVALID, "bad argument");
     if ((nA && (!hashesA || !countsA || !extraA || !kmersA || !posA)) || (nB && (!hashesB || !countsB || !extraB || !kmersB || !posB)))
@@ -3207,6 +3381,8 @@ int fh_merge_partials(uint32_t kind, uint64_t size, double scale, uint32_t k, ui
 int fh_merge_wire(uint32_t kind, uint64_t size, double scale, uint32_t k, uint64_t pad_n, uint32_t n_parts,
                   const int64_t *const *bufs, uint64_t *n_out, uint64_t *out_hashes, uint32_t *out_counts,
                   uint32_t *out_extra, uint8_t *out_kmers, uint64_t *out_pos, uint64_t *total_kmers) {
+    if (kind == FH_KIND_ALL_COUNTS)
+        return fail(FH_ERR_UNSUPPORTED, "fh_merge_wire: AllCounts sketches are merged as forward tables (fh_merge), not as to_vec rows");
     if (!bufs || !n_out || !out_hashes || !out_counts || !out_extra || !out_kmers || !out_pos || k < 1 || k > (uint32_t)FH_MAX_K ||
         (kind != FH_KIND_MASH && kind != FH_KIND_SCALED))
         return fail(FH_ERR_INVALID, "bad argument");
@@ -3278,6 +3454,7 @@ int fh_merge(fh_sketcher *dst, const fh_sketcher *src) {
     if (!src->finished) return fail(FH_ERR_STATE, "fh_merge: src not finished");
     if (dst->p.k != src->p.k || dst->p.kind != src->p.kind || dst->p.seed != src->p.seed || dst->p.size != src->p.size)
         return fail(FH_ERR_INVALID, "fh_merge: incompatible sketch parameters");
+    if (dst->p.kind == FH_KIND_ALL_COUNTS) return ac_merge(dst, src);
     if (int rc = ensure_records(const_cast<fh_sketcher *>(src))) return rc;
     const size_t n = src->res.size();
     const int k = (int)src->p.k;
@@ -3483,6 +3660,11 @@ int fh_sketch_device_blocks(fh_sketcher *const *handles, const void *const *dev_
     // the host-side merge: union of the ascending partial sketches, counts summed (saturating), k-mer of
     // the smallest first position, re-selection -- on the records, without the detour through ASCII k-mers fh_merge takes
     fh_sketcher *dst = handles[0];
+    if (dst->p.kind == FH_KIND_ALL_COUNTS) { // (the forward tables added up, to_vec once more)
+        for (uint32_t i = 1; i < n; ++i)
+            if (int r = ac_merge(dst, handles[i])) return r;
+        return FH_OK;
+    }
     if (int r = ensure_records(dst)) return r;
     std::vector<ResultRec> out;
     for (uint32_t i = 1; i < n; ++i) {
@@ -3516,6 +3698,16 @@ int fh_kernel_time(fh_sketcher *s, double *total_ms, uint64_t *launches, uint64_
 int fh_debug_add_counts(fh_sketcher *s, uint64_t add_count, uint64_t add_extra) {
     if (!s) return fail(FH_ERR_INVALID, "null handle");
     if (s->finished) return fail(FH_ERR_STATE, "sketcher already finished; call fh_reset");
+    if (s->p.kind == FH_KIND_ALL_COUNTS) { // add_count to every nonzero forward bin, saturating; there is no reverse counter
+        if (add_extra) return fail(FH_ERR_INVALID, "AllCounts sketches keep forward counts only: add_extra must be 0");
+        if (int rc = proc_flush(s)) return rc;
+        if (int rc = set_device(s)) return rc;
+        // (the fold first: a bin that wrapped is u32::MAX before anything is added to it)
+        HIP_TRY(launch_ac_mark(s->ac_table, s->ac_sat, (int)s->p.k, s->ac_blk_cnt, s->ac_blk_off, s->ac_tot, s->stream));
+        HIP_TRY(launch_ac_debug_add(s->ac_table, ac_bins((int)s->p.k), add_count, s->stream));
+        s->ac_check = s->ac_dirty = true;
+        return FH_OK;
+    }
     if (int rc = proc_flush(s)) return rc;
     if (int rc = set_device(s)) return rc;
     if (int rc = drain(s)) return rc; // (everything pushed so far is in the table, its new entries on the live list)

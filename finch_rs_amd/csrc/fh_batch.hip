@@ -211,6 +211,10 @@ fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, 
         api_fail(FH_ERR_INVALID, "null params");
         return nullptr;
     }
+    if (params->kind == FH_KIND_ALL_COUNTS) {
+        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher serves Mash sketches only: AllCounts sketches go through an fh_sketcher");
+        return nullptr;
+    }
     if (params->kind != FH_KIND_MASH || params->k < 1 || params->k > 32 || params->size < 1 || params->size > BATCH_MAX_N ||
         params->hash_mask != 0) {
         api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher serves Mash sketches of 1..%llu hashes, k = 1..32, no test mask",

@@ -2709,7 +2709,7 @@ static int finish_sketch(fh_sketcher *h, const std::string &name, const finch_sk
     std::unique_ptr<uint8_t[]> km(new uint8_t[filtered.size() * (size_t)k + 1]);
     if (int rc = fh_copy_out_kmers(h, rows.data(), rows.size(), km.get())) return hfail(rc, "%s", fh_last_error());
     out.name = name;
-    out.seq_length = st.total_bases;
+    out.seq_length = sp.kind == 2 ? 0 : st.total_bases; // (AllCountsSketcher never counts its bases: counts.rs:9, 36-37)
     out.num_valid_kmers = total_kmers;
     out.comment = "";
     out.hashes.resize(filtered.size());
@@ -4068,6 +4068,11 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     // and more workers than cores granted run slower than fewer (24 on a 16-core grant: 5500 files/s, profiles/r04_c5_threads.txt)
     if (n_threads == 0) n_threads = std::min<uint32_t>(16u, std::max<uint32_t>(4u, usable_cpus() / (uint32_t)devs.size())) * (uint32_t)devs.size();
     n_threads = std::max<uint32_t>(1, std::min<uint32_t>(n_threads, std::max<uint32_t>(n_files, 1)));
+    if (sp->kind == 2 && sp->kmer_length >= 1 && sp->kmer_length <= 16) {
+        // every worker's sketcher holds a table of 4^k u32 (4 GiB at k = 15, 16 at k = 16): at most 32 GiB of them per device
+        const uint64_t table = (4ull << (2 * sp->kmer_length)), per_dev = std::max<uint64_t>(1, (32ull << 30) / table);
+        n_threads = (uint32_t)std::min<uint64_t>(n_threads, per_dev * devs.size());
+    }
     static const bool trace_call = cfg("trace") != nullptr;
     const auto call_t0 = std::chrono::steady_clock::now();
     auto res = std::make_unique<finch_sketches>();
@@ -4383,6 +4388,7 @@ static int sharded_devices(const int *devices, uint32_t n_devices, std::vector<i
 int finch_sketch_file_sharded(const char *filename, const finch_sketch_params *sp, const finch_filter_params *filters,
                               const int *devices, uint32_t n_devices, uint64_t chunk_bytes, finch_sketches **out) try {
     if (!filename || !sp || !filters || !out) return hfail(FH_ERR_INVALID, "null argument");
+    if (sp->kind == 2) return hfail(FH_ERR_UNSUPPORTED, "finch_sketch_file_sharded: AllCounts sketches are not sharded (finch_sketch_files)");
     std::vector<int> devs;
     if (int rc = sharded_devices(devices, n_devices, devs)) return rc;
     const std::string fn = filename;
@@ -4415,6 +4421,7 @@ int finch_sketch_buffer_sharded(const uint8_t *data, uint64_t len, const char *n
                                 const finch_filter_params *filters, const int *devices, uint32_t n_devices, uint64_t chunk_bytes,
                                 finch_sketches **out) try {
     if ((!data && len) || !sp || !filters || !out) return hfail(FH_ERR_INVALID, "null argument");
+    if (sp->kind == 2) return hfail(FH_ERR_UNSUPPORTED, "finch_sketch_buffer_sharded: AllCounts sketches are not sharded (finch_sketch_buffer)");
     std::vector<int> devs;
     if (int rc = sharded_devices(devices, n_devices, devs)) return rc;
     auto res = std::make_unique<finch_sketches>();

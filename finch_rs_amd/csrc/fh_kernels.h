@@ -236,4 +236,24 @@ hipError_t launch_synth_reads(uint8_t *out, const uint8_t *genome, uint64_t geno
                               uint64_t n_reads, uint32_t read_len, uint64_t seed, uint32_t sub_ppm, uint32_t n_ppm,
                               hipStream_t st);
 
+// fh_counts.hip: the AllCounts sketcher (FH_KIND_ALL_COUNTS, k = 1..16).  table: 4^k u32 forward counts; sat: one bit per bin,
+// set when the bin's counter wrapped (folded into u32::MAX by launch_ac_mark)
+constexpr int AC_LDS_MAX_K = 7; // k <= 7: histogram in LDS per workgroup (64 KiB at k = 7), larger k: global atomics per window
+struct AcCountArgs {
+    const uint8_t *seq; // the packed block; window starts [p_begin, p_end) are counted (p_begin a multiple of 32)
+    uint64_t len, p_begin, p_end;
+    uint32_t *table, *sat;
+    uint32_t check; // global form: 0 = no bin can reach 2^32 in this launch (non-returning atomics)
+};
+hipError_t launch_ac_count(int k, const AcCountArgs &a, hipStream_t st);
+uint64_t ac_fin_blocks(int k); // workgroups of the finishing passes (4096 bins each): blk_cnt / blk_off entries
+// fold the wrapped bins, count the emitted rows per block (blk_cnt) and their offsets (blk_off); tot[0] = rows, tot[1] =
+// num_valid_kmers (the u64 sum of the saturated forward counts, counts.rs:35-41)
+hipError_t launch_ac_mark(uint32_t *table, uint32_t *sat, int k, uint32_t *blk_cnt, uint64_t *blk_off, uint64_t *tot, hipStream_t st);
+// to_vec's rows (counts.rs:43-64) in ascending ix: hash = ix, count = c[ix] + c[rc] (wrapping), extra = c[rc]
+hipError_t launch_ac_compact(const uint32_t *table, int k, const uint64_t *blk_off, uint64_t *o_hash, uint32_t *o_count,
+                             uint32_t *o_extra, hipStream_t st);
+hipError_t launch_ac_add(uint32_t *dst, const uint32_t *src, uint64_t n, hipStream_t st);  // saturating, element-wise
+hipError_t launch_ac_debug_add(uint32_t *table, uint64_t n, uint64_t add, hipStream_t st); // every nonzero bin, saturating
+
 } // namespace fh

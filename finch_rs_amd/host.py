@@ -157,7 +157,7 @@ def _check(rc):
 
 
 def _params_c(p: SketchParams) -> CSketchParams:
-    kind = {"mash": 0, "scaled": 1}[p.kind]
+    kind = {"mash": 0, "scaled": 1, "allcounts": 2}[p.kind]
     return CSketchParams(kind, p.kmer_length, p.kmers_to_sketch, p.final_size, int(p.no_strict), 0, p.hash_seed, p.scale)
 
 

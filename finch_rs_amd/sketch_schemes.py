@@ -12,7 +12,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import FhParams, FinchHipError, KIND_MASH, KIND_SCALED, check
+from ._lib import FhParams, FinchHipError, KIND_ALL_COUNTS, KIND_MASH, KIND_SCALED, check
 
 KC_DTYPE = np.dtype([("hash", "<u8"), ("count", "<u4"), ("extra_count", "<u4")])
 
@@ -33,7 +33,7 @@ class KmerCount:
 
 @dataclass
 class SketchParams:
-    """mod.rs:54-71.  kind: 'mash' | 'scaled' (AllCounts is not on the accelerated path)."""
+    """mod.rs:54-71.  kind: 'mash' | 'scaled' | 'allcounts' (AllCounts: kmer_length only, 1..16 on the device)."""
     kind: str = "mash"
     kmers_to_sketch: int = 1000
     final_size: int = 1000
@@ -54,13 +54,22 @@ class SketchParams:
     def scaled(kmers_to_sketch, kmer_length, scale, hash_seed=0):
         return SketchParams("scaled", kmers_to_sketch, kmers_to_sketch, False, kmer_length, hash_seed, scale)
 
+    @staticmethod
+    def all_counts(kmer_length=4):
+        """SketchParams::AllCounts (cli.rs: `--sketch-type none`, default -k 4): an exact count of every k-mer"""
+        return SketchParams("allcounts", 0, 0, False, kmer_length, 0)
+
     def k(self) -> int:
         return self.kmer_length
 
     def hash_info(self):  # mod.rs:138-146
+        if self.kind == "allcounts":
+            return ("None", 0, 0, None)
         return ("MurmurHash3_x64_128", 64, self.hash_seed, self.scale if self.kind == "scaled" else None)
 
     def expected_size(self) -> int:  # mod.rs:148-156
+        if self.kind == "allcounts":
+            return 4 ** self.kmer_length
         return self.final_size if self.kind == "mash" else self.kmers_to_sketch
 
     def create_sketcher(self, device: int = 0, **kw) -> "HipSketcher":
@@ -70,6 +79,8 @@ class SketchParams:
         if self.kind == "scaled":
             return HipSketcher(KIND_SCALED, self.kmers_to_sketch, self.kmer_length, self.hash_seed, self.scale,
                                device=device, **kw)
+        if self.kind == "allcounts":
+            return HipSketcher(KIND_ALL_COUNTS, 0, self.kmer_length, 0, device=device, **kw)
         raise FinchError("sketch type %r is not on the accelerated path" % self.kind)
 
     def process_post_filter(self, kmers: List[KmerCount], name: str) -> List[KmerCount]:
@@ -82,7 +93,8 @@ class SketchParams:
 
 
 class HipSketcher:
-    """`impl SketchScheme` over the C ABI: MashSketcher (mash.rs) / ScaledSketcher (scaled.rs) on the GPU."""
+    """`impl SketchScheme` over the C ABI: MashSketcher (mash.rs) / ScaledSketcher (scaled.rs) / AllCountsSketcher (counts.rs)
+    on the GPU."""
 
     def __init__(self, kind: int, size: int, kmer_length: int, seed: int, scale: float = 0.001, device: int = 0,
                  max_launch: int = 0, hash_mask: int = 0, stage_bytes: int = 0):
@@ -161,8 +173,9 @@ class HipSketcher:
         return n.value, tk.value
 
     def total_bases_and_kmers(self) -> Tuple[int, int]:
-        """mash.rs:82-84 (total_bases is a host counter; see include/finch_hip.h)"""
-        return self.total_bases, self.finish()[1]
+        """mash.rs:82-84 (total_bases is a host counter; see include/finch_hip.h).  AllCounts never counts its bases
+        (counts.rs:35-40): (0, num_valid_kmers)."""
+        return (0 if self.kind == KIND_ALL_COUNTS else self.total_bases), self.finish()[1]
 
     def to_arrays(self, out=None):
         """-> (structured [hash,count,extra_count], kmers uint8 [n,k], first_pos uint64 [n]) ascending by hash.
@@ -193,6 +206,8 @@ class HipSketcher:
         """mash.rs:104-112 / scaled.rs:102-109"""
         if self.kind == KIND_MASH:
             return SketchParams("mash", self.size, self.size, False, self.kmer_length, self.seed)
+        if self.kind == KIND_ALL_COUNTS:
+            return SketchParams.all_counts(self.kmer_length)
         return SketchParams("scaled", self.size, self.size, False, self.kmer_length, self.seed, self.scale)
 
     def merge(self, other: "HipSketcher") -> None:

@@ -46,10 +46,20 @@ extern "C" {
 
 #define FH_KIND_MASH 0   /* SketchParams::Mash   (mod.rs:55-61)  -> MashSketcher::new(size, k, seed)          */
 #define FH_KIND_SCALED 1 /* SketchParams::Scaled (mod.rs:62-67)  -> ScaledSketcher::new(size, scale, k, seed) */
+/* SketchParams::AllCounts (mod.rs:68-70) -> AllCountsSketcher::new(k) (counts.rs): an exact count of every forward k-mer,
+ * k = 1..16 (beyond: FH_ERR_UNSUPPORTED -- a 4^k table of u32, 16 GiB at k = 16); size, seed and scale are ignored,
+ * hash_mask must be 0 (FH_ERR_INVALID).  Every push route of an fh_sketcher takes it.  fh_finish: n_out = to_vec's rows,
+ * total_kmers = num_valid_kmers (the u64 sum of the saturated forward counts, counts.rs:35-41).  The copy-outs deliver
+ * to_vec's rows in ascending order: hash = the forward m-form index ix (A 0, C 1, G 2, T 3, first base most significant),
+ * count = c[ix] + c[rc(ix)] (a WRAPPING u32 add, as a release build of the reference computes it), extra_count = c[rc(ix)],
+ * the k-mer = the text of ix; first_pos is undefined (0).  fh_merge adds the forward tables (saturating) and runs to_vec
+ * again; fh_debug_add_counts adds add_count (saturating) to every nonzero forward count and takes add_extra = 0 only.
+ * Refused with FH_ERR_UNSUPPORTED: fh_batch_new, fh_merge_partials, fh_merge_wire, fh_merge_arrays. */
+#define FH_KIND_ALL_COUNTS 2
 
 /* POD mirror of the sketcher constructor arguments (mash.rs:21, scaled.rs:22). */
 typedef struct fh_params {
-    uint32_t kind;        /* FH_KIND_MASH | FH_KIND_SCALED */
+    uint32_t kind;        /* FH_KIND_MASH | FH_KIND_SCALED | FH_KIND_ALL_COUNTS */
     uint32_t k;           /* kmer_length, 1..64 on the device (FH_MAX_KMER_LENGTH; beyond: FH_ERR_UNSUPPORTED).  k <= 32 runs the
                              single-word kernels the roofline is quoted on, 33..64 the two-word ones (fh_k2w.hip) */
     uint64_t size;        /* kmers_to_sketch */
@@ -67,8 +77,9 @@ typedef struct fh_sketcher fh_sketcher;
 int fh_device_count(void);
 const char *fh_last_error(void);
 /* library/ABI version, bumped on any change of this header's functions (5: the batch sketcher with its two-bit input form, fh_set_option; the round-5
- * additions fh_set_record_stride, fh_debug_segments, fh_process_records_in, fh_debug_add_counts, fh_debug_gzip_feed_timeouts) */
-#define FH_ABI_VERSION 5
+ * additions fh_set_record_stride, fh_debug_segments, fh_process_records_in, fh_debug_add_counts, fh_debug_gzip_feed_timeouts;
+ * 6: FH_KIND_ALL_COUNTS, the AllCounts sketcher) */
+#define FH_ABI_VERSION 6
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---

@@ -27,9 +27,9 @@
 extern "C" {
 #endif
 
-/* SketchParams (mod.rs:54-71); AllCounts is not on the accelerated path */
+/* SketchParams (mod.rs:54-71); all three kinds are sketched on the device (AllCounts: k = 1..16, FH_KIND_ALL_COUNTS) */
 typedef struct finch_sketch_params {
-    uint32_t kind;            /* 0 = Mash, 1 = Scaled (2 = AllCounts: serialisation only) */
+    uint32_t kind;            /* 0 = Mash, 1 = Scaled, 2 = AllCounts (kmer_length only; seq_length is 0, as counts.rs reports it) */
     uint32_t kmer_length;
     uint64_t kmers_to_sketch;
     uint64_t final_size;      /* Mash only */
@@ -75,7 +75,8 @@ int finch_sketch_buffer(const uint8_t *data, uint64_t len, const char *name, con
  * merged on the host (fh_merge), then filters / post filter as in sketch_stream.  The result is the Sketch
  * finch_sketch_files returns for the same file.  FASTQ the device-side splitter refuses (not plain 4-line FASTQ: blank
  * lines between records, a record longer than a chunk, ...) is read again through ONE handle and the host parser, which is
- * the judge of what needletail accepts (stdin, which cannot be read twice: FH_ERR_INVALID). */
+ * the judge of what needletail accepts (stdin, which cannot be read twice: FH_ERR_INVALID).  AllCounts (kind 2):
+ * FH_ERR_UNSUPPORTED -- finch_sketch_files / finch_sketch_buffer sketch it. */
 int finch_sketch_file_sharded(const char *filename, const finch_sketch_params *sketch_params, const finch_filter_params *filters,
                               const int *devices, uint32_t n_devices, uint64_t chunk_bytes, finch_sketches **out);
 int finch_sketch_buffer_sharded(const uint8_t *data, uint64_t len, const char *name, const finch_sketch_params *sketch_params,
@@ -121,7 +122,7 @@ int finch_sketches_from_json(const uint8_t *data, uint64_t len, finch_sketches *
 int finch_open_sketch_file(const char *path, finch_sketches **out);
 /* the `sketch` subcommand's output step (cli/src/main.rs:53-70): format by file name */
 int finch_write_sketch_file(const finch_sketches *s, const char *path);
-/* SketchParams of sketch i; kind 2 = AllCounts (only ever seen in files that were read: it is not on the accelerated path) */
+/* SketchParams of sketch i; kind 2 = AllCounts */
 int finch_sketch_params_of(const finch_sketches *s, uint32_t i, finch_sketch_params *out);
 const char *finch_sketch_comment(const finch_sketches *s, uint32_t i);
 int finch_sketch_set_comment(finch_sketches *s, uint32_t i, const char *comment);
