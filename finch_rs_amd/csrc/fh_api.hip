@@ -1536,6 +1536,7 @@ int api_fail(int code, const char *fmt, ...) {
 hipError_t api_dev_malloc(void **p, size_t bytes) { return dev_malloc(p, bytes); }
 hipError_t api_host_malloc(void **p, size_t bytes) { return host_malloc(p, bytes); }
 void api_kmer_ascii(uint64_t m, uint64_t mhi, int k, uint8_t *out) { kmer_ascii(m, mhi, k, out); }
+uint64_t api_scaled_max_hash(double scale) { return scaled_max_hash(scale); }
 } // namespace fh
 
 extern "C" {

@@ -15,6 +15,14 @@
 // threshold -- or the threshold admitted everything -- and nothing overflowed and no two k-mers shared a 64-bit hash; in
 // every other case the file is reported as not taken (status 1) and the caller sketches it through an fh_sketcher.  There
 // is no other outcome: the batch path never returns an approximate sketch.
+//
+// Scaled sketches (FH_KIND_SCALED): the threshold is no guess but max_hash (scaled.rs:22-34), known before the file is read.
+// Reading scaled.rs:37-61: a hash <= max_hash is always admitted and never evicted (the pop fires only when the heap's top is
+// above max_hash); a hash above it is admitted only while len <= size, and popped after any push that leaves len > size with
+// such a hash on top.  So with D = the file's distinct hashes <= max_hash: if D >= size (or size == 0) the sketch is exactly
+// those D hashes, ascending, with their exact counts -- a function of the multiset of k-mers -- and the file is taken iff
+// additionally D <= FH_BATCH_SCALED_MAX, nothing overflowed and no two k-mers shared a hash.  If D < size the reference's
+// sketch also holds hashes above max_hash whose counts depend on the order of the input: not taken.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,6 +54,12 @@ constexpr uint32_t PART_LIVE = 16384;     // live / dead list entries per file (
 constexpr uint32_t PART_SHARD_CAP = 512;  // entries per shard list (inserts are dealt over the 256 lists drain by drain)
 constexpr uint32_t PART_CLOG = 64;        // collision records per file (any collision sends the file the long way)
 constexpr uint64_t BATCH_MAX_N = 3000;    // kmers_to_sketch the in-LDS selection serves (fh_api.hip SMALL_N_MAX)
+// rows of a Scaled sketch: what the epilogue's workgroup holds the keys of in LDS.  The partition does not bind it: its table is
+// 37 % full at that many entries, its live and dropped-slot lists hold PART_LIVE, and the 256 shard lists take 512 each of
+// inserts that are dealt over them drain by drain (48 on average).
+constexpr uint64_t BATCH_SCALED_MAX = FH_BATCH_SCALED_MAX;
+static_assert(BATCH_SCALED_MAX == (uint64_t)SMALL_MAX && BATCH_SCALED_MAX <= PART_LIVE && 2 * BATCH_SCALED_MAX <= PART_CAP,
+              "a Scaled batch sketch fits the epilogue's LDS block and the partition");
 constexpr uint32_t BATCH_MAX_FILES = 4096;
 constexpr uint64_t BATCH_MAX_WAVES = 4096; // 16 per CU x 256 CUs
 
@@ -55,6 +69,7 @@ uint64_t expected_below(uint64_t n) { return n <= 2000 ? 4 * n : 3 * n; }
 
 struct fh_batch {
     fh_params p{};
+    uint64_t max_hash = 0; // FH_KIND_SCALED: the threshold of every file (EMPTY64 at scale 1: everything is admitted)
     int device = 0;
     hipStream_t stream = nullptr;
     uint32_t max_files = 0;
@@ -140,9 +155,12 @@ int build(fh_batch *b) {
         q.shard_cap = PART_SHARD_CAP;
     }
     BHIP_TRY(hipMemcpyAsync(b->d_parts, parts.data(), (size_t)F * sizeof(BatchPartition), hipMemcpyHostToDevice, b->stream));
-    BHIP_TRY(launch_batch_init(b->d_parts, F, b->p.size, 1u, b->stream));
+    const bool scaled = b->p.kind == FH_KIND_SCALED;
+    BHIP_TRY(launch_batch_init(b->d_parts, F, b->p.size, scaled ? b->max_hash : EMPTY64, scaled ? b->max_hash : 0ull, 1u, b->stream));
     // a sketch's columns as fh_finish lays them out: hash | k-mer | first position | count | extra, out_stride entries apart
-    b->out_stride = (uint32_t)(((size_t)std::min<uint64_t>(b->p.size + 1, (uint64_t)SMALL_MAX) + 2) & ~(size_t)1);
+    // (a Scaled sketch has up to BATCH_SCALED_MAX rows whatever its size)
+    const uint64_t rows = scaled ? BATCH_SCALED_MAX : std::min<uint64_t>(b->p.size + 1, (uint64_t)SMALL_MAX);
+    b->out_stride = (uint32_t)(((size_t)rows + 2) & ~(size_t)1);
     b->out_words = (size_t)b->out_stride * 4; // 3 x 8 + 2 x 4 bytes per entry
     b->header_bytes = (((uint64_t)F * sizeof(BatchFile)) + 4095) & ~4095ull;
     for (auto &s : b->slot) {
@@ -163,14 +181,14 @@ int build(fh_batch *b) {
             e.dead = b->dead + (size_t)f * PART_LIVE;
             e.dead_cap = PART_LIVE;
             e.ctl = parts[f].ctl;
-            e.kind = FH_KIND_MASH;
+            e.kind = b->p.kind;
             e.size = b->p.size;
-            e.max_hash = 0;
+            e.max_hash = b->max_hash;
             e.trigger = 0;
-            e.flags = EPI_FLATTEN | EPI_PRUNE_FORCE | EPI_SORT | EPI_GATHER | EPI_RESET;
+            e.flags = EPI_FLATTEN | EPI_PRUNE_FORCE | EPI_SORT | EPI_GATHER | EPI_RESET | (scaled ? EPI_KEEP_ALL : 0u);
             e.n_units = 0;
             e.check_units = 0;
-            e.tau0 = EMPTY64;
+            e.tau0 = scaled ? b->max_hash : EMPTY64;
             e.hist_on = 0;
             e.out = s.h_out + (size_t)f * b->out_words;
             e.out_stride = b->out_stride;
@@ -215,10 +233,20 @@ fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, 
         api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher serves Mash sketches only: AllCounts sketches go through an fh_sketcher");
         return nullptr;
     }
-    if (params->kind != FH_KIND_MASH || params->k < 1 || params->k > 32 || params->size < 1 || params->size > BATCH_MAX_N ||
-        params->hash_mask != 0) {
-        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher serves Mash sketches of 1..%llu hashes, k = 1..32, no test mask",
-                 (unsigned long long)BATCH_MAX_N);
+    if (params->kind != FH_KIND_MASH && params->kind != FH_KIND_SCALED) {
+        api_fail(FH_ERR_INVALID, "unknown sketch kind %u", params->kind);
+        return nullptr;
+    }
+    const bool scaled = params->kind == FH_KIND_SCALED;
+    if (params->k < 1 || params->k > 32 || params->hash_mask != 0 ||
+        (scaled ? params->size > BATCH_SCALED_MAX : (params->size < 1 || params->size > BATCH_MAX_N))) {
+        api_fail(FH_ERR_UNSUPPORTED,
+                 "the batch sketcher serves Mash sketches of 1..%llu hashes and Scaled sketches of size 0..%llu, k = 1..32, no test mask",
+                 (unsigned long long)BATCH_MAX_N, (unsigned long long)BATCH_SCALED_MAX);
+        return nullptr;
+    }
+    if (scaled && !(params->scale > 0.0 && params->scale <= 1.0)) { // (as fh_new)
+        api_fail(FH_ERR_INVALID, "scale must be in (0, 1]");
         return nullptr;
     }
     if (max_files < 1 || max_files > BATCH_MAX_FILES || stage_bytes < 4096 || stage_bytes > (1ull << 36)) {
@@ -240,7 +268,8 @@ fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, 
         for (size_t i = 0; i < g_pool.size(); ++i) {
             fh_batch *c = g_pool[i];
             if (c->device == device && c->max_files == max_files && c->data_bytes == ((stage_bytes + 4095) & ~4095ull) &&
-                c->p.k == params->k && c->p.size == params->size && c->p.seed == params->seed) {
+                c->p.k == params->k && c->p.size == params->size && c->p.seed == params->seed && c->p.kind == params->kind &&
+                (!scaled || c->p.scale == params->scale)) {
                 g_pool.erase(g_pool.begin() + (long)i);
                 return c;
             }
@@ -252,6 +281,7 @@ fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, 
         return nullptr;
     }
     b->p = *params;
+    b->max_hash = scaled ? api_scaled_max_hash(params->scale) : 0;
     b->device = device;
     b->max_files = max_files;
     b->data_bytes = (stage_bytes + 4095) & ~4095ull;
@@ -324,7 +354,10 @@ static int batch_submit(fh_batch *b, int slot, const uint64_t *offsets, const ui
         // the threshold below which E of the file's positions' hashes are expected (every position a distinct k-mer, hashes uniform)
         const uint64_t E = expected_below(b->p.size);
         uint64_t tau = EMPTY64;
-        if (lens[f] > E) {
+        if (b->p.kind == FH_KIND_SCALED) {
+            tau = b->max_hash; // (u64::MAX at scale 1 is EMPTY64: everything is admitted, and the one hash that cannot be a
+                               // table key is counted in sp_count, which sends the file the long way)
+        } else if (lens[f] > E) {
             tau = (uint64_t)((((unsigned __int128)E) << 64) / lens[f]);
             if (tau >= EMPTY64 - 1) tau = EMPTY64;
         }
@@ -426,8 +459,11 @@ int fh_batch_wait(fh_batch *b, int slot, uint8_t *status) {
             // taken iff the epilogue finished the sketch and left the partition reset, the guess held (or admitted everything),
             // no two k-mers shared a hash and the one hash value that cannot be a table key did not occur
             const bool fin = c.sorted == FIN_OK_RESET && c.overflow == 0 && c.need_big == 0;
-            const bool full = s.tau[f] == EMPTY64 || c.inserted_total >= b->p.size;
-            const bool ok = fin && full && c.n_coll == 0 && c.sp_count == 0 && (uint64_t)c.n_live <= b->p.size;
+            // Scaled: every live entry is <= max_hash by construction; they are the sketch iff there are at least `size` of them
+            const bool scaled = b->p.kind == FH_KIND_SCALED;
+            const bool full = scaled ? (uint64_t)c.n_live >= b->p.size : (s.tau[f] == EMPTY64 || c.inserted_total >= b->p.size);
+            const bool rows = scaled ? (uint64_t)c.n_live <= BATCH_SCALED_MAX : (uint64_t)c.n_live <= b->p.size;
+            const bool ok = fin && full && c.n_coll == 0 && c.sp_count == 0 && rows;
             s.status[f] = ok ? 0 : 1;
             if (ok) b->n_taken++;
             else b->n_not_taken++;

@@ -40,6 +40,10 @@
 #include "fh_pack2.h"
 #include "fh_dist.h"
 
+namespace fh {
+uint64_t api_scaled_max_hash(double scale); // fh_internal.h (which needs the HIP headers): a ScaledSketcher's max_hash, scaled.rs:23,31
+}
+
 // job(t) for t = 0 .. n - 1, one thread each (the caller's runs job(0)).  A thread that cannot be created (EAGAIN under a
 // thread limit) must not take the process down -- a vector of joinable threads that unwinds calls std::terminate -- so its
 // share runs on the calling thread instead.
@@ -4107,9 +4111,20 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     // what a batch of genomes is: Mash sketches of <= 3000 hashes (after the cut to final_size the small sketcher makes),
     // k <= 32, no filtering (the default for FASTA, lib.rs:70-76), regular uncompressed files that begin with '>'.
     // Anything else, and every file the batch path reports as not taken, goes through sketch_stream as before.
-    const uint64_t group_n = (sp->final_size >= 1 && sp->final_size < sp->kmers_to_sketch) ? sp->final_size : sp->kmers_to_sketch;
-    const bool group_ok = batch && sp->kind == 0 && sp->kmer_length >= 1 && sp->kmer_length <= 32 && group_n >= 1 && group_n <= 3000 &&
-                          filters->filter_on <= 0 && file_batch_enabled();
+    // Scaled sketches (kind 1) likewise: a file is sketched at max_hash and taken iff it holds between kmers_to_sketch and
+    // FH_BATCH_SCALED_MAX distinct hashes at or below it (fh_batch.hip); process_post_filter leaves a Scaled sketch as it is.
+    const bool group_scaled = sp->kind == 1;
+    const uint64_t group_n = group_scaled ? sp->kmers_to_sketch
+                                          : ((sp->final_size >= 1 && sp->final_size < sp->kmers_to_sketch) ? sp->final_size : sp->kmers_to_sketch);
+    const bool group_ok = batch && (group_scaled ? (group_n <= FH_BATCH_SCALED_MAX && sp->scale > 0.0 && sp->scale <= 1.0) : (sp->kind == 0 && group_n >= 1 && group_n <= 3000)) &&
+                          sp->kmer_length >= 1 && sp->kmer_length <= 32 && filters->filter_on <= 0 && file_batch_enabled();
+    // A Scaled file whose size says it cannot fit is not staged at all (sending it would cost a wasted pass): if every byte began
+    // a distinct k-mer, st_size x max_hash / 2^64 hashes would lie at or below max_hash.  Margin: staged up to 5/4 of the cap --
+    // headers, line ends, N and repeated k-mers make the true number smaller than that estimate, never larger, so a file up to a
+    // quarter above the cap may still fit; one further above is all but certain not to (the count is a sum of ~independent
+    // draws: at 12 288 its standard deviation is ~110, the margin 28 of them).
+    const uint64_t group_max_hash = group_scaled && group_ok ? fh::api_scaled_max_hash(sp->scale) : 0;
+    const uint64_t group_max_expect = (uint64_t)FH_BATCH_SCALED_MAX + FH_BATCH_SCALED_MAX / 4;
     constexpr uint64_t GROUP_STAGE = 32ull << 20;
     constexpr uint32_t GROUP_FILES = 64;
     const size_t READ_PIECE = std::max<uint64_t>(4096, cfg_u64("batch_read_piece", 256u << 10)); // bytes of a file read and packed at a time
@@ -4178,7 +4193,7 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
                 }
                 uint64_t n = 0, tk = 0;
                 int r2 = fh_batch_result(bt, slot, (uint32_t)j, &n, &tk);
-                const size_t keep = (size_t)std::min<uint64_t>(n, sp->final_size); // process_post_filter (mod.rs:115-128)
+                const size_t keep = group_scaled ? (size_t)n : (size_t)std::min<uint64_t>(n, sp->final_size); // process_post_filter (mod.rs:115-128)
                 const uint32_t k = sp->kmer_length;
                 std::unique_ptr<fh_kmer_count[]> recs(new fh_kmer_count[n + 1]);
                 std::unique_ptr<uint8_t[]> km(new uint8_t[n * (size_t)k + 1]);
@@ -4188,7 +4203,7 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
                     continue;
                 }
                 const std::string name = filenames[i];
-                if (!sp->no_strict && keep < sp->final_size) {
+                if (!group_scaled && !sp->no_strict && keep < sp->final_size) {
                     char buf[512];
                     snprintf(buf, sizeof buf, "%s had too few kmers (%zu) to sketch", name.c_str(), keep);
                     record_error(i, FH_ERR_INVALID, buf);
@@ -4238,6 +4253,10 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
             if (fd < 0) return false; // (sketch_stream reports it)
             struct stat sb;
             if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size < 1 || (uint64_t)sb.st_size + 4096 > GROUP_STAGE) {
+                close(fd);
+                return false;
+            }
+            if (group_scaled && (uint64_t)(((unsigned __int128)(uint64_t)sb.st_size * group_max_hash) >> 64) > group_max_expect) {
                 close(fd);
                 return false;
             }

@@ -13,6 +13,8 @@ hipError_t api_dev_malloc(void **p, size_t bytes);
 hipError_t api_host_malloc(void **p, size_t bytes);
 // the m-form k-mer word (first base most significant; mhi: the first k - 32 bases of a k-mer longer than 32) as k ASCII bytes
 void api_kmer_ascii(uint64_t m, uint64_t mhi, int k, uint8_t *out);
+// max_hash of a Scaled sketch (scaled.rs:23,31): the one restatement, shared by fh_sketcher and the batch sketcher
+uint64_t api_scaled_max_hash(double scale);
 // fh_batch.hip: free the parked batch handles (fh_release_cached)
 void batch_release_cached();
 

@@ -64,6 +64,8 @@ constexpr uint32_t EPI_GATHER = 64u;       // write the sorted sketch's columns 
 constexpr uint32_t EPI_NEED_SPEC = 128u;   // EPI_GATHER: a speculation is unverified -- the sketch only counts if ctl->spec_ok
 constexpr uint32_t EPI_RESET = 256u;       // EPI_GATHER: if the sketch counts, leave the handle as fh_reset would (slots cleared,
                                            // control block re-initialised) behind the mirror of the final control block
+constexpr uint32_t EPI_KEEP_ALL = 512u;    // a Scaled file of a batch (kind 1, every live entry <= max_hash): all of them are rows, up to
+                                           // SMALL_MAX (above SMALL_SORT_MAX sorted chunk by chunk, needs room in `dead`), whatever `size`
 // what the gather epilogue reports in the mirrored control block's `sorted` word
 constexpr uint32_t FIN_OK_RESET = 2u;      // everything queued did what it was queued for, the sketch is in `out`, the handle is reset
 constexpr uint32_t FIN_OK = 3u;            // ... the handle is not reset (dropped-slot list overflowed: fh_reset sweeps the table)
@@ -97,7 +99,9 @@ struct BatchPartition {
     CollRec *clog;
     uint32_t cap, live_cap, clog_cap, shard_cap;
 };
-hipError_t launch_batch_init(const BatchPartition *parts, uint32_t n_files, uint64_t size, uint32_t read_first, hipStream_t st);
+// (tau0 / tau_floor: the control block's threshold and its floor -- EMPTY64 / 0 for Mash, max_hash twice for Scaled)
+hipError_t launch_batch_init(const BatchPartition *parts, uint32_t n_files, uint64_t size, uint64_t tau0, uint64_t tau_floor,
+                             uint32_t read_first, hipStream_t st);
 hipError_t launch_reset_small(Entry *table, const uint32_t *live, const uint32_t *dead, Ctl *ctl, uint64_t tau0, uint64_t sel_size,
                               uint64_t tau_floor, uint32_t hist_on, hipStream_t st);
 hipError_t launch_clear_slots(Entry *table, uint64_t cap, const uint32_t *live, const uint32_t *dead, const Ctl *ctl,

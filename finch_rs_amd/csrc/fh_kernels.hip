@@ -212,8 +212,85 @@ struct SmallLds {
 constexpr size_t SMALL_LDS_BYTES = (size_t)SMALL_MAX * 8 + (size_t)SMALL_SORT_MAX * 12;
 constexpr u32 PRUNE_DECLINED = 0xFFFFFFFFu;
 
+// The all-LDS bitonic network over N (a power of two, <= SMALL_SORT_MAX) (key, slot) pairs, ascending; the caller has padded
+// [n, N) with EMPTY64 keys and put a barrier behind its writes.  Ends on a barrier.
+__device__ __forceinline__ void bitonic_lds(u64 *skeys, u32 *sslots, u32 N) {
+    const u32 tid = threadIdx.x, nthr = blockDim.x;
+    for (u32 kk = 2; kk <= N; kk <<= 1) {
+        for (u32 jj = kk >> 1; jj > 0; jj >>= 1) {
+            for (u32 i = tid; i < N; i += nthr) {
+                const u32 ixj = i ^ jj;
+                if (ixj > i) {
+                    const bool up = (i & kk) == 0;
+                    const u64 a = skeys[i], b = skeys[ixj];
+                    if ((a > b) == up) {
+                        skeys[i] = b;
+                        skeys[ixj] = a;
+                        const u32 sa = sslots[i];
+                        sslots[i] = sslots[ixj];
+                        sslots[ixj] = sa;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// More rows than the network holds (a Scaled file of a batch: SMALL_SORT_MAX < M <= SMALL_MAX, every live entry a row, nothing
+// to select).  keys[0, M) are the hashes in live-list order and fill the LDS block's first 96 KiB; the 48 KiB behind them hold
+// ONE chunk of SMALL_SORT_MAX pairs, so a padded 16 K network does not fit.  Instead: each chunk of SMALL_SORT_MAX entries goes
+// through the network and back (keys to keys[], slots to the live list), then every entry takes its final row by RANK -- its
+// index within its own chunk plus, for each other chunk, the number of keys there below its own (a bisection; keys are
+// distinct, so the ranks are a permutation of [0, M)) -- and its slot goes to scratch[rank] (global: the free tail of the
+// dropped-slot list), which is then copied over the live list.  Afterwards the live list is in to_vec order like after any
+// other sort; the gather reads the rows from there (the hash from the table entry) and writes coalesced.
+// ~80 barriers per chunk, three chunks at most: ~0.1 ms for 12 288 rows, of a batch whose copy alone takes 2 ms.
+__device__ __forceinline__ void sort_wide_dev(u32 *live, u32 *scratch, u32 M, const SmallLds L) {
+    const u32 tid = threadIdx.x, nthr = blockDim.x; // (1024)
+    constexpr u32 CH = (u32)SMALL_SORT_MAX;
+    u64 *keys = L.keys;
+    const u32 nchunks = (M + CH - 1u) / CH;
+    for (u32 c = 0; c < nchunks; ++c) {
+        const u32 base = c * CH, n = M - base < CH ? M - base : CH;
+        u32 N = 1;
+        while (N < n) N <<= 1;
+        for (u32 i = tid; i < N; i += nthr) {
+            L.skeys[i] = i < n ? keys[base + i] : EMPTY64;
+            L.sslots[i] = i < n ? live[base + i] : 0xFFFFFFFFu;
+        }
+        __syncthreads();
+        bitonic_lds(L.skeys, L.sslots, N);
+        for (u32 i = tid; i < n; i += nthr) {
+            keys[base + i] = L.skeys[i];
+            live[base + i] = L.sslots[i];
+        }
+        __syncthreads();
+    }
+    for (u32 i = tid; i < M; i += nthr) {
+        const u64 key = keys[i];
+        const u32 own = i / CH;
+        u32 rank = i - own * CH;
+        for (u32 o = 0; o < nchunks; ++o) {
+            if (o == own) continue;
+            u32 lo = o * CH, hi = lo + CH < M ? lo + CH : M; // first index in [lo, hi] whose key is not below `key`
+            const u32 first = lo;
+            while (lo < hi) {
+                const u32 mid = (lo + hi) >> 1;
+                if (keys[mid] < key) lo = mid + 1u;
+                else hi = mid;
+            }
+            rank += lo - first;
+        }
+        scratch[rank] = live[i];
+    }
+    __syncthreads();
+    for (u32 i = tid; i < M; i += nthr) live[i] = scratch[i];
+    __syncthreads();
+}
+
 __device__ u32 prune_small_dev(Entry *table, u32 *live, u32 *dead, u32 dead_cap, Ctl *ctl, u32 M, u32 kind, u64 size, u64 max_hash,
-                               u32 sort_out, const SmallLds L) {
+                               u32 sort_out, const SmallLds L, const u32 keep_all = 0u) {
     const u32 tid = threadIdx.x, nthr = blockDim.x; // (1024)
     u64 *keys = L.keys;
     constexpr int PER = SMALL_MAX / 1024;
@@ -265,9 +342,21 @@ __device__ u32 prune_small_dev(Entry *table, u32 *live, u32 *dead, u32 dead_cap,
         }
         __syncthreads();
     }
-    if (sort_out && keep > (u32)SMALL_SORT_MAX) { // (never launched that way: the device-wide sort takes such sketches)
-        if (tid == 0) ctl->need_big = 1u;
-        return PRUNE_DECLINED;
+    if (sort_out && keep > (u32)SMALL_SORT_MAX) { // (an fh_sketcher never launches it that way: the device-wide sort takes such sketches)
+        // a Scaled file of a batch (EPI_KEEP_ALL): nothing is dropped, the chunk sort above needs M words of the dropped-slot list
+        const u32 nd_now = ctl->n_dead;
+        if (!keep_all || keep != M || nd_now > dead_cap || M > dead_cap - nd_now) {
+            if (tid == 0) ctl->need_big = 1u;
+            return PRUNE_DECLINED;
+        }
+        sort_wide_dev(live, dead + nd_now, M, L);
+        if (tid == 0) {
+            ctl->n_live = keep;
+            const u64 cur = ctl->tau;
+            ctl->tau = tau < cur ? tau : cur;
+            ctl->sorted = 1u;
+        }
+        return keep;
     }
     // partition: keys are distinct, so exactly `keep` of them are <= tau (or keep == M)
     const u32 nd0 = ctl->n_dead;
@@ -337,25 +426,7 @@ __device__ u32 prune_small_dev(Entry *table, u32 *live, u32 *dead, u32 dead_cap,
             L.sslots[i] = 0xFFFFFFFFu;
         }
         __syncthreads();
-        for (u32 kk = 2; kk <= N; kk <<= 1) {
-            for (u32 jj = kk >> 1; jj > 0; jj >>= 1) {
-                for (u32 i = tid; i < N; i += nthr) {
-                    const u32 ixj = i ^ jj;
-                    if (ixj > i) {
-                        const bool up = (i & kk) == 0;
-                        const u64 a = L.skeys[i], b = L.skeys[ixj];
-                        if ((a > b) == up) {
-                            L.skeys[i] = b;
-                            L.skeys[ixj] = a;
-                            const u32 sa = L.sslots[i];
-                            L.sslots[i] = L.sslots[ixj];
-                            L.sslots[ixj] = sa;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        bitonic_lds(L.skeys, L.sslots, N);
         for (u32 i = tid; i < keep; i += nthr) live[i] = L.sslots[i];
     }
     if (tid == 0) {
@@ -510,7 +581,7 @@ __device__ __forceinline__ u32 small_epilogue_body(const EpiArgs &a, unsigned ch
                 if (tid == 0) ctl->need_big = 1u;
             } else {
                 kept = prune_small_dev(a.table, a.live, a.dead, a.dead_cap, ctl, M, a.kind, a.size, a.max_hash, sort_out,
-                                       small_lds(smem, s_hist, s_wsum, s_bcast, s_cnt));
+                                       small_lds(smem, s_hist, s_wsum, s_bcast, s_cnt), a.flags & EPI_KEEP_ALL);
             }
         }
         __syncthreads();
@@ -530,10 +601,12 @@ __device__ __forceinline__ u32 small_epilogue_body(const EpiArgs &a, unsigned ch
             u64 *o_hash = a.out, *o_kmer = o_hash + st, *o_pos = o_kmer + st;
             u64 *o_kmer_hi = a.wide ? o_pos + st : nullptr;
             u32 *o_count = (u32 *)((a.wide ? o_kmer_hi : o_pos) + st), *o_extra = o_count + st;
+            // (more rows than the LDS network holds -- sort_wide_dev: the sorted slots are in the live list, the hash in the entry)
+            const bool from_live = kept > (u32)SMALL_SORT_MAX;
             for (u32 i = tid; i < kept; i += 1024u) {
-                const u32 sl = L.sslots[i];
+                const u32 sl = from_live ? a.live[i] : L.sslots[i];
                 const Entry e = a.table[sl];
-                o_hash[i] = L.skeys[i];
+                o_hash[i] = from_live ? e.hash : L.skeys[i];
                 const u64 occ = e.count + e.extra; // the table counts the two strands separately (fh_device.h)
                 o_count[i] = occ > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)occ;
                 o_extra[i] = e.extra > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)e.extra;
@@ -550,7 +623,10 @@ __device__ __forceinline__ u32 small_epilogue_body(const EpiArgs &a, unsigned ch
         __syncthreads();
         const bool spec_ok = !(a.flags & EPI_NEED_SPEC) || ctl->spec_ok != 0u;
         const bool dry = a.check_units == 0u || (ctl->next_unit >= a.check_units && ctl->n_left_out == 0u);
-        const bool ok = spec_ok && dry && !ctl->need_big && !ctl->overflow && ctl->sorted == 1u && (u64)ctl->n_live <= a.size;
+        // (EPI_KEEP_ALL: a Scaled file of a batch has as many rows as hashes at or below max_hash; whether those are the sketch --
+        // at least `size` of them -- is the host's question, fh_batch_wait)
+        const bool rows_ok = (a.flags & EPI_KEEP_ALL) ? true : (u64)ctl->n_live <= a.size;
+        const bool ok = spec_ok && dry && !ctl->need_big && !ctl->overflow && ctl->sorted == 1u && rows_ok;
         if (ok) fin = ((a.flags & EPI_RESET) && ctl->n_dead != 0xFFFFFFFFu) ? FIN_OK_RESET : FIN_OK;
         __syncthreads();
         if (fin && tid == 0) ctl->sorted = fin;
@@ -571,8 +647,9 @@ __device__ __forceinline__ u32 small_epilogue_body(const EpiArgs &a, unsigned ch
         const SmallLds L = small_lds(smem, s_hist, s_wsum, s_bcast, s_cnt);
         const u32 nl = ctl->n_live, nd = ctl->n_dead;
         u64 *khi = ctl->kmer_hi;
+        const bool from_live = nl > (u32)SMALL_SORT_MAX;
         for (u32 i = tid; i < nl; i += 1024u) {
-            const u32 sl = L.sslots[i];
+            const u32 sl = from_live ? a.live[i] : L.sslots[i];
             clear_entry(&a.table[sl]);
             if (khi) khi[sl] = EMPTY64;
         }
@@ -582,7 +659,7 @@ __device__ __forceinline__ u32 small_epilogue_body(const EpiArgs &a, unsigned ch
             if (khi) khi[sl] = EMPTY64;
         }
         __syncthreads(); // every thread has read the two counts
-        init_ctl_dev(ctl, a.tau0, 0u, a.size, 0ull, a.hist_on);
+        init_ctl_dev(ctl, a.tau0, 0u, a.size, (a.flags & EPI_KEEP_ALL) ? a.max_hash : 0ull, a.hist_on);
     }
     return fin;
 }
@@ -619,7 +696,7 @@ __global__ __launch_bounds__(1024) void k_batch_epilogue(const EpiArgs *args, u3
         for (u32 i = threadIdx.x; i < cap; i += 1024u) clear_entry(&a.table[i]);
         if (threadIdx.x < (u32)N_SHARDS) ctl->shard_cnt[threadIdx.x * SHARD_STRIDE] = 0;
         __syncthreads();
-        init_ctl_dev(ctl, a.tau0, 0u, a.size, 0ull, a.hist_on);
+        init_ctl_dev(ctl, a.tau0, 0u, a.size, (a.flags & EPI_KEEP_ALL) ? a.max_hash : 0ull, a.hist_on);
     }
     __syncthreads();
     if (threadIdx.x == 0) ctl->read_first = read_first; // (init_ctl_dev leaves it 0; the batch kernel has no queue reset that would set it)
@@ -632,7 +709,7 @@ hipError_t launch_batch_epilogue(const EpiArgs *args, uint32_t n_files, uint32_t
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(1024) void k_batch_init(const BatchPartition *parts, u64 size, u32 read_first) {
+__global__ __launch_bounds__(1024) void k_batch_init(const BatchPartition *parts, u64 size, u64 tau0, u64 tau_floor, u32 read_first) {
     const BatchPartition p = parts[blockIdx.x];
     for (u32 i = threadIdx.x; i < p.cap; i += 1024u) clear_entry(&p.table[i]);
     if (threadIdx.x < (u32)N_SHARDS) p.shard_cnt[threadIdx.x * SHARD_STRIDE] = 0;
@@ -652,14 +729,15 @@ __global__ __launch_bounds__(1024) void k_batch_init(const BatchPartition *parts
         ctl->text_bases = 0;
     }
     __syncthreads();
-    init_ctl_dev(p.ctl, EMPTY64, 0u, size, 0ull, 0u);
+    init_ctl_dev(p.ctl, tau0, 0u, size, tau_floor, 0u);
     __syncthreads();
     if (threadIdx.x == 0) p.ctl->read_first = read_first;
 }
 
-hipError_t launch_batch_init(const BatchPartition *parts, uint32_t n_files, uint64_t size, uint32_t read_first, hipStream_t st) {
+hipError_t launch_batch_init(const BatchPartition *parts, uint32_t n_files, uint64_t size, uint64_t tau0, uint64_t tau_floor,
+                             uint32_t read_first, hipStream_t st) {
     if (n_files == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_batch_init, dim3(n_files), dim3(1024), 0, st, parts, size, read_first);
+    hipLaunchKernelGGL(k_batch_init, dim3(n_files), dim3(1024), 0, st, parts, size, tau0, tau_floor, read_first);
     return hipGetLastError();
 }
 

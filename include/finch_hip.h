@@ -324,8 +324,15 @@ int fh_sketch_device_blocks(fh_sketcher *const *handles, const void *const *dev_
  * ~150 us of latency-bound device time for the ~6 us a 4 Mb genome takes to hash.  A batch handle sketches ALL the files its
  * caller has staged with one copy, one launch of the sketch kernel over the files' tiles (fh_k2b.hip), one launch of the
  * epilogue (a workgroup per file: select, sort, to_vec straight into pinned host memory, state left reset) and one
- * synchronisation.  Mash sketches of 1..3000 hashes, k = 1..32, any seed; everything else -- and every file the batch path
- * cannot vouch for -- goes through an fh_sketcher.
+ * synchronisation.  Mash sketches of 1..3000 hashes and Scaled sketches (size 0..FH_BATCH_SCALED_MAX, scale as fh_new takes
+ * it), k = 1..32, any seed; everything else (AllCounts: FH_ERR_UNSUPPORTED) -- and every file the batch path cannot vouch
+ * for -- goes through an fh_sketcher.
+ * A Scaled file is sketched at max_hash itself (scaled.rs:22-34) and is taken iff it holds at least `size` and at most
+ * FH_BATCH_SCALED_MAX distinct hashes at or below max_hash: then the reference's sketch is exactly those hashes, whatever
+ * the order of the input (scaled.rs:37-61: a hash <= max_hash is never evicted, one above it never survives a full heap).
+ * With fewer than `size` the reference also keeps hashes above max_hash, with order-dependent counts: not taken.  A
+ * Scaled handle's result columns are FH_BATCH_SCALED_MAX rows per file whatever `size` is (about 390 KiB of pinned memory
+ * per file and slot).
  *
  *   fh_batch_new(params, device, max_files, stage_bytes)   two slots, each a pinned staging buffer of stage_bytes
  *   fh_batch_stage(b, slot, &buf, &cap)                    where the caller writes the PACKED streams of its files (the
@@ -335,7 +342,8 @@ int fh_sketch_device_blocks(fh_sketcher *const *handles, const void *const *dev_
  *   fh_batch_wait(b, slot, status)                         status[i] = 0: sketch i is ready (fh_batch_result /
  *                                                          fh_batch_copy_out*); 1: NOT TAKEN -- the file holds fewer than
  *                                                          `size` distinct k-mers below the threshold it was sketched at
- *                                                          (low-complexity or tiny input), or two of its k-mers share a
+ *                                                          (low-complexity or tiny input; Scaled: or more than
+ *                                                          FH_BATCH_SCALED_MAX of them), or two of its k-mers share a
  *                                                          64-bit hash, or a capacity was exceeded: sketch it through an
  *                                                          fh_sketcher, which handles all of that.  Never an approximate
  *                                                          sketch: a taken file's hashes, counts and k-mer bytes are the
@@ -353,6 +361,7 @@ int fh_sketch_device_blocks(fh_sketcher *const *handles, const void *const *dev_
  *                                                          fh_batch_pack writes that form from a packed byte stream.
  * The two slots alternate: fill slot 1 while slot 0 is in flight.  A batch handle is single-threaded like an fh_sketcher;
  * different handles are independent (one per worker thread). */
+#define FH_BATCH_SCALED_MAX 12288u /* rows of a Scaled sketch the batch path serves (what its epilogue sorts in one workgroup's LDS) */
 typedef struct fh_batch fh_batch;
 fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes);
 void fh_batch_free(fh_batch *b);

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""finch_sketch_files with Scaled parameters over a directory of genomes, with and without the batch path; one JSON line.
+
+    python tools/batch_scaled_bench.py [--files 3000] [--distinct 500] [--reps 3] [--threads 0] [--dir DIR] [--only batch|one]
+
+Input: bench.py's configs[4] generator (synth_fasta_file: log-uniform 1-10 Mb genomes, 70-column lines); `--distinct` files
+are written to a temporary directory and the list of `--files` names cycles over them, so the page cache feeds every pass.
+Sketched with SketchParams.scaled(1000, 21, 0.001): a 1-10 Mb genome has 1000-10 000 rows, four in ten of them more than the
+4096 the epilogue's LDS network holds (those take its chunk sort).  Per mode -- option file_batch=0 (every file through a
+sketcher of its own: what the library did for Scaled parameters before the batch path served them) and the default -- one
+warm-up pass, then the best of `--reps` passes: files/s, files taken / not taken by the batch path, the sketch kernels'
+time (HIP events: fh_batch_kernel_time / fh_kernel_time, summed over the workers) and the launches behind it.  Both modes'
+sketches are compared row for row.
+
+The epilogue's time comes from a trace of its own (never in the timed passes):
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/batch_scaled_bench.py --files 256 --distinct 256 --reps 1 --only batch
+(profiles/batch_scaled_kernel_stats.txt is the kernel table of such a run)."""
+import argparse
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import finch_rs_amd as F  # noqa: E402
+from finch_rs_amd import host as H  # noqa: E402
+from finch_rs_amd import sketch_schemes as S  # noqa: E402
+
+SEED = 20250620
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=3000)
+    ap.add_argument("--distinct", type=int, default=500)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--threads", type=int, default=0, help="workers of finch_sketch_files (0: the library's choice)")
+    ap.add_argument("--dir", default=None, help="where the files are written (default: a temporary directory, removed afterwards)")
+    ap.add_argument("--only", choices=["batch", "one"], default=None)
+    a = ap.parse_args()
+    distinct = min(a.distinct, a.files)
+    d = a.dir or tempfile.mkdtemp(prefix="finch_batch_scaled_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    os.makedirs(d, exist_ok=True)
+    try:
+        names = []
+        for i in range(distinct):
+            p = os.path.join(d, "g%05d.fa" % i)
+            if not os.path.exists(p):
+                with open(p, "wb") as f:
+                    f.write(S.synth_fasta_file(i, SEED))
+            names.append(p)
+        paths = [names[i % distinct] for i in range(a.files)]
+        nbytes = sum(os.path.getsize(names[i % distinct]) for i in range(a.files))
+        params = S.SketchParams.scaled(1000, 21, 0.001)
+        out = {"files": a.files, "distinct": distinct, "text_gbytes": round(nbytes / 1e9, 3), "params": "scaled(1000, 21, 0.001)"}
+        sketches = {}
+        for mode in ("one", "batch"):
+            if a.only and a.only != mode:
+                continue
+            F.debug_set(file_batch="0" if mode == "one" else None)
+            H.sketch_files(names, params, H.FilterParams(None), n_threads=a.threads)  # warm-up: handles, page cache
+            best = None
+            for rep in range(a.reps):
+                t0, n0 = H.debug_file_batch()
+                H.debug_kernel_times(1)
+                w0 = time.perf_counter()
+                res = H.sketch_files(paths, params, H.FilterParams(None), n_threads=a.threads)
+                wall = time.perf_counter() - w0
+                ms, launches, positions = H.debug_kernel_times(0)
+                t1, n1 = H.debug_file_batch()
+                if best is None or wall < best[0]:
+                    best = (wall, ms, launches, positions, t1 - t0, n1 - n0)
+                out.setdefault(mode + "_walls_s", []).append(round(wall, 4))
+            wall, ms, launches, positions, taken, not_taken = best
+            rows = [len(res.sketch(i).arrays[0]) for i in range(distinct)]
+            out[mode] = {"files_per_s": round(a.files / wall, 1), "wall_s": round(wall, 4), "text_gbytes_per_s": round(nbytes / wall / 1e9, 2),
+                         "taken": taken, "not_taken": not_taken, "sketch_kernel_ms": round(ms, 2), "sketch_kernel_launches": launches,
+                         "sketch_kernel_ms_per_launch": round(ms / launches, 4) if launches else None,
+                         "rows_min_median_max": [min(rows), sorted(rows)[len(rows) // 2], max(rows)],
+                         "files_above_4096_rows": sum(1 for r in rows if r > 4096)}
+            sketches[mode] = [(res.sketch(i).arrays[0].tobytes(), res.sketch(i).arrays[1].tobytes()) for i in range(distinct)]
+        F.debug_set(file_batch=None)
+        if len(sketches) == 2:
+            out["sketches_equal"] = sketches["one"] == sketches["batch"]
+            out["speedup"] = round(out["batch"]["files_per_s"] / out["one"]["files_per_s"], 3)
+        print(json.dumps(out), flush=True)
+        if len(sketches) == 2 and not out["sketches_equal"]:
+            sys.exit(1)
+    finally:
+        if not a.dir:
+            shutil.rmtree(d, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
