@@ -23,6 +23,11 @@
 // those D hashes, ascending, with their exact counts -- a function of the multiset of k-mers -- and the file is taken iff
 // additionally D <= FH_BATCH_SCALED_MAX, nothing overflowed and no two k-mers shared a hash.  If D < size the reference's
 // sketch also holds hashes above max_hash whose counts depend on the order of the input: not taken.
+//
+// AllCounts (fh_batch_new_counts, k = 1..7): a handle of its own kind behind the same functions.  No partitions: a table of
+// 4^k u32 per file, counted by ONE launch of k_ac_batch_count and turned into to_vec's rows by ONE launch of
+// k_ac_batch_epilogue (fh_counts.hip, a workgroup per file), which leaves the tables zeroed.  A count is exact for any input:
+// every file is taken.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +38,7 @@
 
 #include "../../include/finch_hip.h"
 #include "fh_core.h"
+#include "fh_counts.h"
 #include "fh_device.h"
 #include "fh_internal.h"
 #include "fh_kernels.h"
@@ -62,6 +68,9 @@ static_assert(BATCH_SCALED_MAX == (uint64_t)SMALL_MAX && BATCH_SCALED_MAX <= PAR
               "a Scaled batch sketch fits the epilogue's LDS block and the partition");
 constexpr uint32_t BATCH_MAX_FILES = 4096;
 constexpr uint64_t BATCH_MAX_WAVES = 4096; // 16 per CU x 256 CUs
+// an AllCounts handle's staging buffer: below 2^21 tiles of the two-bit form, so that no file has 2^32 positions (the 4 KiB
+// rounding of stage_bytes stays below it too)
+constexpr uint64_t COUNTS_MAX_STAGE = (1ull << 21) * fh_pack2::TILE_BYTES - 4096;
 
 uint64_t expected_below(uint64_t n) { return n <= 2000 ? 4 * n : 3 * n; }
 
@@ -69,6 +78,7 @@ uint64_t expected_below(uint64_t n) { return n <= 2000 ? 4 * n : 3 * n; }
 
 struct fh_batch {
     fh_params p{};
+    bool counts = false;   // made by fh_batch_new_counts: p.kind == FH_KIND_ALL_COUNTS, p.k = 1..7, the rest of p unused
     uint64_t max_hash = 0; // FH_KIND_SCALED: the threshold of every file (EMPTY64 at scale 1: everything is admitted)
     int device = 0;
     hipStream_t stream = nullptr;
@@ -82,11 +92,13 @@ struct fh_batch {
     uint32_t *live = nullptr, *dead = nullptr, *shard_cnt = nullptr, *shard_buf = nullptr;
     CollRec *clog = nullptr;
     BatchPartition *d_parts = nullptr;
+    uint32_t *ac_tables = nullptr; // counts: max_files tables of 4^k forward counts, zero between batches
     struct Slot {
         uint8_t *h_stage = nullptr, *d_stage = nullptr;
         EpiArgs *d_epi = nullptr;
         Ctl *h_ctl = nullptr;
-        uint64_t *h_out = nullptr;
+        AcBatchResult *h_res = nullptr; // counts: rows and total_kmers per file, in place of h_ctl
+        uint64_t *h_out = nullptr;      // counts: three u32 columns per file (ix | count | extra_count)
         hipEvent_t done = nullptr, k0 = nullptr, k1 = nullptr;
         bool in_flight = false, waited = false;
         uint32_t n_files = 0;
@@ -111,6 +123,7 @@ void destroy(fh_batch *b) {
         if (s.d_stage) (void)hipFree(s.d_stage);
         if (s.d_epi) (void)hipFree(s.d_epi);
         if (s.h_ctl) (void)hipHostFree(s.h_ctl);
+        if (s.h_res) (void)hipHostFree(s.h_res);
         if (s.h_out) (void)hipHostFree(s.h_out);
         if (s.done) (void)hipEventDestroy(s.done);
         if (s.k0) (void)hipEventDestroy(s.k0);
@@ -124,6 +137,7 @@ void destroy(fh_batch *b) {
     if (b->shard_buf) (void)hipFree(b->shard_buf);
     if (b->clog) (void)hipFree(b->clog);
     if (b->d_parts) (void)hipFree(b->d_parts);
+    if (b->ac_tables) (void)hipFree(b->ac_tables);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -205,6 +219,32 @@ int build(fh_batch *b) {
     return FH_OK;
 }
 
+int build_counts(fh_batch *b) {
+    const uint32_t F = b->max_files;
+    const size_t bins = (size_t)ac_bins((int)b->p.k);
+    BHIP_TRY(hipSetDevice(b->device));
+    BHIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    BHIP_TRY(api_dev_malloc((void **)&b->ac_tables, (size_t)F * bins * sizeof(uint32_t)));
+    BHIP_TRY(hipMemsetAsync(b->ac_tables, 0, (size_t)F * bins * sizeof(uint32_t), b->stream));
+    // a file's columns hold the most rows to_vec can emit from 4^k bins: (4^k + palindromes) / 2
+    b->out_stride = (ac_max_rows((int)b->p.k) + 1u) & ~1u;
+    b->out_words = (size_t)b->out_stride * 3 / 2; // 3 x 4 bytes per entry
+    b->header_bytes = (((uint64_t)F * sizeof(BatchFile)) + 4095) & ~4095ull;
+    for (auto &s : b->slot) {
+        BHIP_TRY(api_host_malloc((void **)&s.h_stage, b->header_bytes + b->data_bytes + 64));
+        BHIP_TRY(api_dev_malloc((void **)&s.d_stage, b->header_bytes + b->data_bytes + 64));
+        BHIP_TRY(api_host_malloc((void **)&s.h_res, (size_t)F * sizeof(AcBatchResult)));
+        BHIP_TRY(api_host_malloc((void **)&s.h_out, (size_t)F * b->out_words * sizeof(uint64_t)));
+        BHIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+        BHIP_TRY(hipEventCreate(&s.k0));
+        BHIP_TRY(hipEventCreate(&s.k1));
+        s.len.resize(F);
+        s.status.resize(F);
+    }
+    BHIP_TRY(hipStreamSynchronize(b->stream));
+    return FH_OK;
+}
+
 std::mutex g_pool_mu;
 std::vector<fh_batch *> g_pool;
 constexpr size_t BATCH_POOL_MAX = 64;
@@ -221,6 +261,20 @@ void batch_release_cached() {
     for (fh_batch *b : v) destroy(b);
 }
 } // namespace fh
+
+static bool device_ok(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        (void)hipGetLastError();
+        api_fail(FH_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
+        return false;
+    }
+    if (device < 0 || device >= n_dev) {
+        api_fail(FH_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, n_dev);
+        return false;
+    }
+    return true;
+}
 
 extern "C" {
 
@@ -253,21 +307,12 @@ fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, 
         api_fail(FH_ERR_INVALID, "max_files 1..%u, stage_bytes 4 KiB..64 GiB", BATCH_MAX_FILES);
         return nullptr;
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        (void)hipGetLastError();
-        api_fail(FH_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
-        return nullptr;
-    }
-    if (device < 0 || device >= n_dev) {
-        api_fail(FH_ERR_NO_DEVICE, "device %d out of range (%d visible)", device, n_dev);
-        return nullptr;
-    }
+    if (!device_ok(device)) return nullptr;
     {
         std::lock_guard<std::mutex> g(g_pool_mu);
         for (size_t i = 0; i < g_pool.size(); ++i) {
             fh_batch *c = g_pool[i];
-            if (c->device == device && c->max_files == max_files && c->data_bytes == ((stage_bytes + 4095) & ~4095ull) &&
+            if (!c->counts && c->device == device && c->max_files == max_files && c->data_bytes == ((stage_bytes + 4095) & ~4095ull) &&
                 c->p.k == params->k && c->p.size == params->size && c->p.seed == params->seed && c->p.kind == params->kind &&
                 (!scaled || c->p.scale == params->scale)) {
                 g_pool.erase(g_pool.begin() + (long)i);
@@ -287,6 +332,58 @@ fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, 
     b->data_bytes = (stage_bytes + 4095) & ~4095ull;
     try {
         if (build(b) != FH_OK) {
+            destroy(b);
+            return nullptr;
+        }
+    } catch (...) {
+        destroy(b);
+        api_fail(FH_ERR_CAPACITY, "out of host memory");
+        return nullptr;
+    }
+    return b;
+}
+
+fh_batch *fh_batch_new_counts(uint32_t k, int device, uint32_t max_files, uint64_t stage_bytes) {
+    if (k < 1) {
+        api_fail(FH_ERR_INVALID, "kmer_length must be at least 1");
+        return nullptr;
+    }
+    if (k > (uint32_t)AC_LDS_MAX_K) {
+        api_fail(FH_ERR_UNSUPPORTED, "the AllCounts batch sketcher serves k = 1..%d (one file's 4^k counts in a workgroup's LDS): k = %u goes through an fh_sketcher",
+                 AC_LDS_MAX_K, k);
+        return nullptr;
+    }
+    // fewer than 2^32 positions per file, whichever form it is staged in: a slot of fewer than 2^21 tiles of the two-bit form
+    if (max_files < 1 || max_files > BATCH_MAX_FILES || stage_bytes < 4096 || stage_bytes > COUNTS_MAX_STAGE) {
+        api_fail(FH_ERR_INVALID, "max_files 1..%u, stage_bytes 4 KiB..%llu (an AllCounts file has fewer than 2^32 positions)", BATCH_MAX_FILES,
+                 (unsigned long long)COUNTS_MAX_STAGE);
+        return nullptr;
+    }
+    if (!device_ok(device)) return nullptr;
+    const uint64_t data_bytes = (stage_bytes + 4095) & ~4095ull;
+    {
+        std::lock_guard<std::mutex> g(g_pool_mu);
+        for (size_t i = 0; i < g_pool.size(); ++i) {
+            fh_batch *c = g_pool[i];
+            if (c->counts && c->p.k == k && c->device == device && c->max_files == max_files && c->data_bytes == data_bytes) {
+                g_pool.erase(g_pool.begin() + (long)i);
+                return c;
+            }
+        }
+    }
+    fh_batch *b = new (std::nothrow) fh_batch;
+    if (!b) {
+        api_fail(FH_ERR_CAPACITY, "out of host memory");
+        return nullptr;
+    }
+    b->counts = true;
+    b->p.kind = FH_KIND_ALL_COUNTS;
+    b->p.k = k;
+    b->device = device;
+    b->max_files = max_files;
+    b->data_bytes = data_bytes;
+    try {
+        if (build_counts(b) != FH_OK) {
             destroy(b);
             return nullptr;
         }
@@ -350,11 +447,13 @@ static int batch_submit(fh_batch *b, int slot, const uint64_t *offsets, const ui
         BatchFile &d = hd[f];
         d.seq = s.d_stage + b->header_bytes + offsets[f];
         d.len = lens[f];
-        d.ctl = b->ctls + f;
+        d.ctl = b->counts ? nullptr : b->ctls + f;
         // the threshold below which E of the file's positions' hashes are expected (every position a distinct k-mer, hashes uniform)
         const uint64_t E = expected_below(b->p.size);
         uint64_t tau = EMPTY64;
-        if (b->p.kind == FH_KIND_SCALED) {
+        if (b->counts) {
+            tau = 0; // (not looked at)
+        } else if (b->p.kind == FH_KIND_SCALED) {
             tau = b->max_hash; // (u64::MAX at scale 1 is EMPTY64: everything is admitted, and the one hash that cannot be a
                                // table key is counted in sp_count, which sends the file the long way)
         } else if (lens[f] > E) {
@@ -364,7 +463,7 @@ static int batch_submit(fh_batch *b, int slot, const uint64_t *offsets, const ui
         d.tau = tau;
         d.tile0 = (uint32_t)tiles;
         d.n_tiles = (uint32_t)n_tiles;
-        s.tau[f] = tau;
+        if (!b->counts) s.tau[f] = tau;
         s.len[f] = lens[f];
         tiles += n_tiles;
         positions += lens[f];
@@ -379,6 +478,23 @@ static int batch_submit(fh_batch *b, int slot, const uint64_t *offsets, const ui
         return FH_OK;
     }
     BHIP_TRY(hipMemcpyAsync(s.d_stage, s.h_stage, b->header_bytes + ((end + 15) & ~15ull), hipMemcpyHostToDevice, b->stream));
+    if (b->counts) {
+        if (tiles) {
+            AcBatchArgs a{};
+            a.files = reinterpret_cast<const BatchFile *>(s.d_stage);
+            a.n_files = n_files;
+            a.tiles_total = (uint32_t)tiles;
+            a.two_bit = two_bit ? 1u : 0u;
+            a.tables = b->ac_tables;
+            if (b->profiling) BHIP_TRY(hipEventRecord(s.k0, b->stream));
+            BHIP_TRY(launch_ac_batch_count((int)b->p.k, a, b->stream));
+            if (b->profiling) BHIP_TRY(hipEventRecord(s.k1, b->stream));
+        }
+        BHIP_TRY(launch_ac_batch_epilogue(b->ac_tables, (int)b->p.k, n_files, reinterpret_cast<uint32_t *>(s.h_out), b->out_stride, s.h_res, b->stream));
+        BHIP_TRY(hipEventRecord(s.done, b->stream));
+        s.in_flight = true;
+        return FH_OK;
+    }
     if (tiles) {
         BatchArgs a{};
         a.files = reinterpret_cast<const BatchFile *>(s.d_stage);
@@ -454,7 +570,11 @@ int fh_batch_wait(fh_batch *b, int slot, uint8_t *status) {
                 (void)hipGetLastError();
             }
         }
-        for (uint32_t f = 0; f < s.n_files; ++f) {
+        if (b->counts) { // the epilogue has run for every file: a count is exact whatever the input
+            std::fill(s.status.begin(), s.status.begin() + s.n_files, (uint8_t)0);
+            b->n_taken += s.n_files;
+        }
+        for (uint32_t f = 0; !b->counts && f < s.n_files; ++f) {
             const Ctl &c = s.h_ctl[f];
             // taken iff the epilogue finished the sketch and left the partition reset, the guess held (or admitted everything),
             // no two k-mers shared a hash and the one hash value that cannot be a table key did not occur
@@ -479,15 +599,36 @@ static int batch_file(fh_batch *b, int slot, uint32_t i, const Ctl **c, const ui
     if (s.in_flight || !s.waited) return api_fail(FH_ERR_STATE, "slot %d: fh_batch_wait first", slot);
     if (i >= s.n_files) return api_fail(FH_ERR_INVALID, "file %u of a batch of %u", i, s.n_files);
     if (s.status[i] != 0) return api_fail(FH_ERR_STATE, "file %u was not taken by the batch path", i);
-    *c = &s.h_ctl[i];
+    *c = b->counts ? nullptr : &s.h_ctl[i];
     *cols = s.h_out + (size_t)i * b->out_words;
     return FH_OK;
+}
+
+// a file of a counts handle: to_vec's rows as the epilogue left them (ix | count | extra_count).  hash = ix, the k-mer is the
+// text of ix, first_pos is 0 (as an AllCounts fh_sketcher gives them)
+static void counts_rows(const fh_batch *b, int slot, uint32_t i, const uint64_t *cols, uint64_t *hashes, uint32_t *counts, uint32_t *extra_counts,
+                        fh_kmer_count *records, uint8_t *kmers, uint64_t *first_pos) {
+    const size_t n = b->slot[slot].h_res[i].n_out, st = b->out_stride;
+    const uint32_t *ix = reinterpret_cast<const uint32_t *>(cols), *cc = ix + st, *ee = cc + st;
+    if (counts) memcpy(counts, cc, n * 4);
+    if (extra_counts) memcpy(extra_counts, ee, n * 4);
+    if (first_pos) memset(first_pos, 0, n * 8);
+    for (size_t j = 0; j < n; ++j) {
+        if (hashes) hashes[j] = ix[j];
+        if (records) records[j] = fh_kmer_count{ix[j], cc[j], ee[j]};
+        if (kmers) api_kmer_ascii(ix[j], 0, (int)b->p.k, kmers + j * b->p.k);
+    }
 }
 
 int fh_batch_result(fh_batch *b, int slot, uint32_t i, uint64_t *n_out, uint64_t *total_kmers) {
     const Ctl *c = nullptr;
     const uint64_t *cols = nullptr;
     if (int rc = batch_file(b, slot, i, &c, &cols)) return rc;
+    if (b->counts) {
+        if (n_out) *n_out = b->slot[slot].h_res[i].n_out;
+        if (total_kmers) *total_kmers = b->slot[slot].h_res[i].total_kmers;
+        return FH_OK;
+    }
     if (n_out) *n_out = c->n_live;
     if (total_kmers) {
         uint64_t t = 0;
@@ -502,6 +643,10 @@ int fh_batch_copy_out(fh_batch *b, int slot, uint32_t i, uint64_t *hashes, uint3
     const Ctl *c = nullptr;
     const uint64_t *cols = nullptr;
     if (int rc = batch_file(b, slot, i, &c, &cols)) return rc;
+    if (b->counts) {
+        counts_rows(b, slot, i, cols, hashes, counts, extra_counts, nullptr, kmers, first_pos);
+        return FH_OK;
+    }
     const size_t n = c->n_live, st = b->out_stride;
     const uint64_t *hh = cols, *kk = hh + st, *pp = kk + st;
     const uint32_t *cc = reinterpret_cast<const uint32_t *>(pp + st), *ee = cc + st;
@@ -518,6 +663,10 @@ int fh_batch_copy_out_records(fh_batch *b, int slot, uint32_t i, fh_kmer_count *
     const Ctl *c = nullptr;
     const uint64_t *cols = nullptr;
     if (int rc = batch_file(b, slot, i, &c, &cols)) return rc;
+    if (b->counts) {
+        counts_rows(b, slot, i, cols, nullptr, nullptr, nullptr, records, kmers, nullptr);
+        return FH_OK;
+    }
     const size_t n = c->n_live, st = b->out_stride;
     const uint64_t *hh = cols, *kk = hh + st, *pp = kk + st;
     const uint32_t *cc = reinterpret_cast<const uint32_t *>(pp + st), *ee = cc + st;

@@ -30,16 +30,13 @@ FH_HD u32 ac_revcomp(u32 ix, int k) { return pairrev32(~ix & ac_mask(k)) >> (32 
 // overflow checks); a palindrome (rc == ix, even k) gives 2c and c.
 FH_HD bool ac_emit(u32 ix, u32 rc, u32 c, u32 crc) { return c != 0 && (rc >= ix || crc == 0); }
 
-// Phase A of the counting kernel: 48 packed bytes (12 little-endian dwords, byte 0 = window start 0) -> f(j, ix) for every
-// window start j < min(32, limit) whose K bytes are all bases, ix = the window's m-form word.  Bytes at or behind the end of
-// the input must be passed as breakers (0).
+// The windows of a lane from its positions' classified form: codes[c] = the 2-bit codes of positions 16 c .. 16 c + 15 (c < 3),
+// bit b of g64 = position b is a base (b < 48) -> f(j, ix) for every window start j < min(32, limit) whose K positions are all
+// bases, ix = the window's m-form word.  The code of a position that is no base may be anything.
 template <int K, class F>
-FH_HDM void ac_lane_windows(const u32 *d, u32 limit, F &&f) {
+FH_HDM void ac_code_windows(const u32 *codes, u64 g64, u32 limit, F &&f) {
     static_assert(K >= 1 && K <= AC_MAX_K, "AllCounts k is 1..16");
-    u32 codes[3], good[3];
-    for (int c = 0; c < 3; ++c) classify_chunk(d[4 * c], d[4 * c + 1], d[4 * c + 2], d[4 * c + 3], codes[c], good[c]);
-    const u64 g64 = (u64)good[0] | ((u64)good[1] << 16) | ((u64)good[2] << 32);
-    u32 valid = (u32)window_valid_mask64<K>(g64); // bit j: bytes j .. j + K - 1 are all bases (j + K - 1 <= 46 < 48)
+    u32 valid = (u32)window_valid_mask64<K>(g64); // bit j: positions j .. j + K - 1 are all bases (j + K - 1 <= 46 < 48)
     if (limit < 32) valid &= (1u << limit) - 1u;
     const u32 mask = ac_mask(K);
     u32 m = 0;
@@ -52,5 +49,26 @@ FH_HDM void ac_lane_windows(const u32 *d, u32 limit, F &&f) {
         if (j >= 0 && ((valid >> j) & 1u)) f(j, m);
     }
 }
+
+// Phase A of the counting kernel: 48 packed bytes (12 little-endian dwords, byte 0 = window start 0) -> f(j, ix) for every
+// window start j < min(32, limit) whose K bytes are all bases, ix = the window's m-form word.  Bytes at or behind the end of
+// the input must be passed as breakers (0).
+template <int K, class F>
+FH_HDM void ac_lane_windows(const u32 *d, u32 limit, F &&f) {
+    u32 codes[3], good[3];
+    for (int c = 0; c < 3; ++c) classify_chunk(d[4 * c], d[4 * c + 1], d[4 * c + 2], d[4 * c + 3], codes[c], good[c]);
+    ac_code_windows<K>(codes, (u64)good[0] | ((u64)good[1] << 16) | ((u64)good[2] << 32), limit, f);
+}
+
+// The same for a lane of a file staged in the two-bit form (fh_pack2.h): `own` / g_own = the codes and base bits of the lane's
+// group of 32 positions, `next` / g_next = those of the group behind it (the halo: only its first K - 1 positions are looked at).
+template <int K, class F>
+FH_HDM void ac_group_windows(u64 own, u32 g_own, u64 next, u32 g_next, F &&f) {
+    const u32 codes[3] = {(u32)own, (u32)(own >> 32), (u32)next};
+    ac_code_windows<K>(codes, (u64)g_own | ((u64)(g_next & 0xFFFFu) << 32), 32u, f);
+}
+
+// rows to_vec emits at most from a table of 4^k bins: one per reverse-complement pair and one per palindrome (even k: 4^(k/2))
+FH_HD u32 ac_max_rows(int k) { return (u32)((ac_bins(k) + ((k & 1) ? 0ull : (1ull << k))) / 2); }
 
 } // namespace fh

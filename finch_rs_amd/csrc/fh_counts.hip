@@ -228,6 +228,148 @@ __global__ void k_ac_debug_add(u32 *table, uint64_t n, uint64_t add) {
     }
 }
 
+// ---- many files per launch (fh_batch_new_counts) ----
+// A workgroup takes a contiguous run of the batch's tile space (tiles of TILE_POS window starts, as k2_batch's), file by file:
+// its waves deal the file's tiles of the run among themselves, a lane takes the 32 window starts of its group -- in the byte
+// form exactly k_ac_count_lds's step, in the two-bit form one u64 of codes and one u32 of base bits plus the group behind
+// (the halo; the tile of zeroes behind a file's last tile is the halo of its last lane).  ONE file's histogram is in LDS at a
+// time, in k_ac_count_lds's layout; when the run leaves the file its nonzero bins go to the file's table, one atomic each, and
+// the LDS copies are cleared.  A window belongs to the lane that owns its start, so it is counted once whatever tile or
+// workgroup its last base lies in; bytes and positions at or behind a file's `len` are no bases, so no window spans two files
+// and the last K - 1 positions of a file start none.
+template <int K>
+__global__ __launch_bounds__(AC_LDS_THREADS) void k_ac_batch_count(AcBatchArgs a) {
+    constexpr u32 B = 1u << (2 * K);
+    constexpr int COPIES = ac_lds_copies(K);
+    constexpr u32 WAVES = AC_LDS_THREADS / 64;
+    __shared__ u32 hist[COPIES * B];
+    for (u32 i = threadIdx.x; i < COPIES * B; i += AC_LDS_THREADS) hist[i] = 0;
+    __syncthreads();
+    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    u32 *mine = hist + wave % COPIES * B;
+    const uint64_t t_first = (uint64_t)blockIdx.x * a.tiles_per_group;
+    if (t_first >= a.tiles_total) return;
+    u32 t = (u32)t_first;
+    const u32 t_stop = (u32)std::min<uint64_t>(t_first + a.tiles_per_group, a.tiles_total);
+    // the file tile t belongs to: the last one whose first tile is <= t (a file without tiles shares its successor's first tile
+    // and is never the last such)
+    u32 f = 0;
+    {
+        u32 lo = 0, hi = a.n_files;
+        while (hi - lo > 1u) {
+            const u32 mid = (lo + hi) >> 1;
+            if (a.files[mid].tile0 <= t) lo = mid;
+            else hi = mid;
+        }
+        f = lo;
+    }
+    while (t < t_stop) { // (t < tiles_total: some file from f on holds tile t, so f stays below n_files)
+        const BatchFile *const fd = a.files + f;
+        const u32 f_tile0 = fd->tile0, f_tiles = fd->n_tiles;
+        if (f_tiles == 0u || t >= f_tile0 + f_tiles) {
+            ++f;
+            continue;
+        }
+        const uint8_t *const seq = fd->seq;
+        const uint64_t len = fd->len;
+        const u32 run_end = std::min(t_stop, f_tile0 + f_tiles);
+        for (u32 tt = t - f_tile0 + wave; tt < run_end - f_tile0; tt += WAVES) {
+            const uint64_t p = (uint64_t)tt * TILE_POS + lane * AC_LANE_POS;
+            if (p >= len) continue;
+            const auto count = [&](int, u32 ix) { atomicAdd(mine + ix, 1u); };
+            if (a.two_bit) {
+                const uint64_t g = (uint64_t)tt * 64u + lane, g1 = g + 1; // (g1 may be group 0 of the next tile: it exists, fh_pack2.h)
+                const uint8_t *const t0 = seq + (g >> 6) * TWO_BIT_TILE_BYTES, *const t1 = seq + (g1 >> 6) * TWO_BIT_TILE_BYTES;
+                const uint64_t own = *reinterpret_cast<const uint64_t *>(t0 + 8u * (u32)(g & 63u));
+                const u32 g_own = *reinterpret_cast<const u32 *>(t0 + TWO_BIT_CODES_BYTES + 4u * (u32)(g & 63u));
+                const uint64_t next = *reinterpret_cast<const uint64_t *>(t1 + 8u * (u32)(g1 & 63u));
+                const u32 g_next = *reinterpret_cast<const u32 *>(t1 + TWO_BIT_CODES_BYTES + 4u * (u32)(g1 & 63u));
+                ac_group_windows<K>(own, g_own, next, g_next, count);
+            } else {
+                u32 d[12];
+                ac_load48(seq, len, p, true, d); // (a file's stream is 16-byte aligned; bytes behind len read as breakers)
+                ac_lane_windows<K>(d, 32u, count);
+            }
+        }
+        __syncthreads();
+        u32 *const table = a.tables + (size_t)f * B;
+        for (u32 i = threadIdx.x; i < B; i += AC_LDS_THREADS) {
+            u32 v = 0;
+            for (int c = 0; c < COPIES; ++c) {
+                v += hist[c * B + i];
+                hist[c * B + i] = 0;
+            }
+            if (v) atomicAdd(table + i, v); // (no wrap: a file has fewer than 2^32 positions, fh_batch_new_counts)
+        }
+        __syncthreads();
+        t = run_end;
+        ++f;
+    }
+}
+
+// to_vec of one file per workgroup.  The table (at most 16 384 bins) is read into LDS and zeroed behind; bins are looked at in
+// rounds of AC_FIN_THREADS consecutive ones (a lane a bin: ascending ix is round by round, wave by wave, lane by lane), so the
+// row offset of a bin is (rows of the (round, wave) cells in front of its own) + (emitting lanes below it in its wave).
+__global__ __launch_bounds__(AC_FIN_THREADS) void k_ac_batch_epilogue(u32 *tables, int k, u32 *out, u32 out_stride, AcBatchResult *res) {
+    constexpr u32 WAVES = AC_FIN_THREADS / 64;
+    __shared__ u32 c[1u << (2 * AC_LDS_MAX_K)];
+    __shared__ uint64_t ssum[AC_FIN_THREADS];
+    const u32 B = 1u << (2 * k), rounds = (B + AC_FIN_THREADS - 1) / AC_FIN_THREADS; // rounds * WAVES <= AC_FIN_THREADS cells
+    u32 *const table = tables + (size_t)blockIdx.x * B;
+    for (u32 i = threadIdx.x; i < B; i += AC_FIN_THREADS) {
+        c[i] = table[i];
+        table[i] = 0;
+    }
+    __syncthreads();
+    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const auto emits = [&](u32 ix, u32 &cnt, u32 &crc) {
+        if (ix >= B) return false;
+        cnt = c[ix];
+        const u32 rc = ac_revcomp(ix, k);
+        crc = c[rc];
+        return ac_emit(ix, rc, cnt, crc);
+    };
+    // pass 1: rows per cell (thread r * WAVES + w keeps cell (r, w)'s), and the sum of the forward counts
+    uint64_t s = 0;
+    u32 cell_rows = 0;
+    for (u32 r = 0; r < rounds; ++r) {
+        u32 cnt = 0, crc = 0;
+        const bool e = emits(r * AC_FIN_THREADS + threadIdx.x, cnt, crc);
+        s += cnt;
+        const u32 n = (u32)__popcll(__ballot(e));
+        if (lane == 0) ssum[r * WAVES + wave] = n; // (ssum doubles as the hand-over of the cells' rows)
+    }
+    __syncthreads();
+    if (threadIdx.x < rounds * WAVES) cell_rows = (u32)ssum[threadIdx.x];
+    __syncthreads();
+    u32 n_out = 0;
+    const u32 cell_off = ac_block_scan(cell_rows, &n_out);
+    ssum[threadIdx.x] = cell_off;
+    __syncthreads();
+    // pass 2: the rows
+    u32 *const o_ix = out + (size_t)blockIdx.x * 3u * out_stride, *const o_count = o_ix + out_stride, *const o_extra = o_count + out_stride;
+    for (u32 r = 0; r < rounds; ++r) {
+        u32 cnt = 0, crc = 0;
+        const u32 ix = r * AC_FIN_THREADS + threadIdx.x;
+        const bool e = emits(ix, cnt, crc);
+        const uint64_t m = __ballot(e);
+        if (e) {
+            const u32 o = (u32)ssum[r * WAVES + wave] + (u32)__popcll(m & ((1ull << lane) - 1ull));
+            o_ix[o] = ix;
+            o_count[o] = cnt + crc; // (cannot wrap: fh_batch_new_counts)
+            o_extra[o] = crc;
+        }
+    }
+    __syncthreads();
+    ssum[threadIdx.x] = s;
+    __syncthreads();
+    for (u32 off = AC_FIN_THREADS / 2; off; off >>= 1) {
+        if (threadIdx.x < off) ssum[threadIdx.x] += ssum[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) res[blockIdx.x] = AcBatchResult{ssum[0], n_out, 0u};
+}
+
 uint32_t grid_cap_of_device() {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
@@ -268,6 +410,30 @@ hipError_t launch_ac_count(int k, const AcCountArgs &a, hipStream_t st) {
 #undef FH_AC_CASE
     default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_ac_batch_count(int k, const AcBatchArgs &a0, hipStream_t st) {
+    if (a0.tiles_total == 0) return hipSuccess;
+    AcBatchArgs a = a0;
+    // every workgroup a run of at least one tile per wave; no more workgroups than the chip holds at once
+    a.tiles_per_group = std::max<uint32_t>(AC_LDS_THREADS / 64, (a.tiles_total + grid_cap_of_device() - 1) / grid_cap_of_device());
+    const dim3 grid((a.tiles_total + a.tiles_per_group - 1) / a.tiles_per_group), block(AC_LDS_THREADS);
+    switch (k) {
+#define FH_AC_CASE(K) \
+    case K: hipLaunchKernelGGL(k_ac_batch_count<K>, grid, block, 0, st, a); break;
+        FH_AC_CASE(1) FH_AC_CASE(2) FH_AC_CASE(3) FH_AC_CASE(4) FH_AC_CASE(5) FH_AC_CASE(6) FH_AC_CASE(7)
+#undef FH_AC_CASE
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_ac_batch_epilogue(uint32_t *tables, int k, uint32_t n_files, uint32_t *out, uint32_t out_stride, AcBatchResult *res,
+                                    hipStream_t st) {
+    if (k < 1 || k > AC_LDS_MAX_K) return hipErrorInvalidValue;
+    if (n_files == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ac_batch_epilogue, dim3(n_files), dim3(AC_FIN_THREADS), 0, st, tables, k, out, out_stride, res);
+    return hipGetLastError();
 }
 
 hipError_t launch_ac_mark(u32 *table, u32 *sat, int k, u32 *blk_cnt, uint64_t *blk_off, uint64_t *tot, hipStream_t st) {

@@ -4113,10 +4113,13 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     // Anything else, and every file the batch path reports as not taken, goes through sketch_stream as before.
     // Scaled sketches (kind 1) likewise: a file is sketched at max_hash and taken iff it holds between kmers_to_sketch and
     // FH_BATCH_SCALED_MAX distinct hashes at or below it (fh_batch.hip); process_post_filter leaves a Scaled sketch as it is.
+    // AllCounts (kind 2, k <= 7) through a handle of fh_batch_new_counts: every staged file is taken (a count is exact for any
+    // input), there is no strict error and no truncation (process_post_filter does nothing, mod.rs:115-128), seq_length is 0.
+    const bool group_counts = sp->kind == 2;
     const bool group_scaled = sp->kind == 1;
     const uint64_t group_n = group_scaled ? sp->kmers_to_sketch
                                           : ((sp->final_size >= 1 && sp->final_size < sp->kmers_to_sketch) ? sp->final_size : sp->kmers_to_sketch);
-    const bool group_ok = batch && (group_scaled ? (group_n <= FH_BATCH_SCALED_MAX && sp->scale > 0.0 && sp->scale <= 1.0) : (sp->kind == 0 && group_n >= 1 && group_n <= 3000)) &&
+    const bool group_ok = batch && (group_counts ? sp->kmer_length <= 7 : group_scaled ? (group_n <= FH_BATCH_SCALED_MAX && sp->scale > 0.0 && sp->scale <= 1.0) : (sp->kind == 0 && group_n >= 1 && group_n <= 3000)) &&
                           sp->kmer_length >= 1 && sp->kmer_length <= 32 && filters->filter_on <= 0 && file_batch_enabled();
     // A Scaled file whose size says it cannot fit is not staged at all (sending it would cost a wasted pass): if every byte began
     // a distinct k-mer, st_size x max_hash / 2^64 hashes would lie at or below max_hash.  Margin: staged up to 5/4 of the cap --
@@ -4193,7 +4196,7 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
                 }
                 uint64_t n = 0, tk = 0;
                 int r2 = fh_batch_result(bt, slot, (uint32_t)j, &n, &tk);
-                const size_t keep = group_scaled ? (size_t)n : (size_t)std::min<uint64_t>(n, sp->final_size); // process_post_filter (mod.rs:115-128)
+                const size_t keep = group_scaled || group_counts ? (size_t)n : (size_t)std::min<uint64_t>(n, sp->final_size); // process_post_filter (mod.rs:115-128)
                 const uint32_t k = sp->kmer_length;
                 std::unique_ptr<fh_kmer_count[]> recs(new fh_kmer_count[n + 1]);
                 std::unique_ptr<uint8_t[]> km(new uint8_t[n * (size_t)k + 1]);
@@ -4203,7 +4206,7 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
                     continue;
                 }
                 const std::string name = filenames[i];
-                if (!group_scaled && !sp->no_strict && keep < sp->final_size) {
+                if (!group_scaled && !group_counts && !sp->no_strict && keep < sp->final_size) {
                     char buf[512];
                     snprintf(buf, sizeof buf, "%s had too few kmers (%zu) to sketch", name.c_str(), keep);
                     record_error(i, FH_ERR_INVALID, buf);
@@ -4211,7 +4214,7 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
                 }
                 Sketch &out = res->v[i];
                 out.name = name;
-                out.seq_length = g.st[j].total_bases;
+                out.seq_length = group_counts ? 0 : g.st[j].total_bases; // (AllCountsSketcher never counts its bases: counts.rs:9, 36-37)
                 out.num_valid_kmers = tk;
                 out.comment = "";
                 out.hashes.resize(keep);
@@ -4264,7 +4267,8 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
             if (!bt) {
                 fh_params bp = to_fh(*sp, 0);
                 bp.size = group_n;
-                bt = fh_batch_new(&bp, handles.device, GROUP_FILES, GROUP_STAGE);
+                bt = group_counts ? fh_batch_new_counts(sp->kmer_length, handles.device, GROUP_FILES, GROUP_STAGE)
+                                  : fh_batch_new(&bp, handles.device, GROUP_FILES, GROUP_STAGE);
                 if (bt && (fh_batch_stage(bt, 0, &stage[0], &stage_cap) != FH_OK || fh_batch_stage(bt, 1, &stage[1], &stage_cap) != FH_OK)) {
                     fh_batch_free(bt);
                     bt = nullptr;

@@ -260,4 +260,24 @@ hipError_t launch_ac_compact(const uint32_t *table, int k, const uint64_t *blk_o
 hipError_t launch_ac_add(uint32_t *dst, const uint32_t *src, uint64_t n, hipStream_t st);  // saturating, element-wise
 hipError_t launch_ac_debug_add(uint32_t *table, uint64_t n, uint64_t add, hipStream_t st); // every nonzero bin, saturating
 
+// fh_counts.hip: AllCounts over MANY files per launch (fh_batch_new_counts, k = 1..AC_LDS_MAX_K).  tables: 4^k u32 forward
+// counts per file (file f's at tables + f * 4^k), zero before the count launch and left zero by the epilogue.
+struct AcBatchArgs {
+    const BatchFile *files; // the batch's descriptors (seq, len, tile0, n_tiles; ctl and tau are not looked at)
+    uint32_t n_files, tiles_total;
+    uint32_t tiles_per_group; // a workgroup takes the contiguous tiles [g q, (g + 1) q) of the batch's tile space
+    uint32_t two_bit;         // 1: the files are staged in the two-bit form (fh_pack2.h)
+    uint32_t *tables;
+};
+hipError_t launch_ac_batch_count(int k, const AcBatchArgs &a, hipStream_t st);
+// what the epilogue reports per file (pinned host memory)
+struct AcBatchResult {
+    uint64_t total_kmers; // the sum of the forward counts (num_valid_kmers)
+    uint32_t n_out, pad;  // to_vec's rows
+};
+// one workgroup per file: to_vec's rows in ascending ix as three u32 columns (ix | count | extra_count, out_stride entries
+// apart; file f's at out + 3 f out_stride), n_out and total_kmers to res[f], the file's table zeroed
+hipError_t launch_ac_batch_epilogue(uint32_t *tables, int k, uint32_t n_files, uint32_t *out, uint32_t out_stride, AcBatchResult *res,
+                                    hipStream_t st);
+
 } // namespace fh

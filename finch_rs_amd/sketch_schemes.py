@@ -268,6 +268,20 @@ class BatchSketcher:
         if not self._h:
             raise FinchHipError(-1, (self._L.fh_last_error() or b"").decode(errors="replace"))
 
+    @classmethod
+    def all_counts(cls, kmer_length: int, device: int = 0, max_files: int = 64, stage_bytes: int = 64 << 20):
+        """A batch sketcher of AllCounts files (fh_batch_new_counts, k = 1..7): the same stage / submit / wait / result /
+        sketch_many in both input forms; every block is taken, rows as an AllCounts HipSketcher delivers them."""
+        self = cls.__new__(cls)
+        self._L = _lib.load()
+        self.size, self.kmer_length, self.seed, self.device = 0, kmer_length, 0, device
+        self.max_files = max_files
+        self.kind, self.scale = KIND_ALL_COUNTS, 0.0
+        self._h = self._L.fh_batch_new_counts(kmer_length, device, max_files, stage_bytes)
+        if not self._h:
+            raise FinchHipError(-1, (self._L.fh_last_error() or b"").decode(errors="replace"))
+        return self
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.fh_batch_free(self._h)

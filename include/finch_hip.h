@@ -54,7 +54,8 @@ extern "C" {
  * count = c[ix] + c[rc(ix)] (a WRAPPING u32 add, as a release build of the reference computes it), extra_count = c[rc(ix)],
  * the k-mer = the text of ix; first_pos is undefined (0).  fh_merge adds the forward tables (saturating) and runs to_vec
  * again; fh_debug_add_counts adds add_count (saturating) to every nonzero forward count and takes add_extra = 0 only.
- * Refused with FH_ERR_UNSUPPORTED: fh_batch_new, fh_merge_partials, fh_merge_wire, fh_merge_arrays. */
+ * Refused with FH_ERR_UNSUPPORTED: fh_batch_new (batches of AllCounts files have a constructor of their own,
+ * fh_batch_new_counts), fh_merge_partials, fh_merge_wire, fh_merge_arrays. */
 #define FH_KIND_ALL_COUNTS 2
 
 /* POD mirror of the sketcher constructor arguments (mash.rs:21, scaled.rs:22). */
@@ -78,8 +79,8 @@ int fh_device_count(void);
 const char *fh_last_error(void);
 /* library/ABI version, bumped on any change of this header's functions (5: the batch sketcher with its two-bit input form, fh_set_option; the round-5
  * additions fh_set_record_stride, fh_debug_segments, fh_process_records_in, fh_debug_add_counts, fh_debug_gzip_feed_timeouts;
- * 6: FH_KIND_ALL_COUNTS, the AllCounts sketcher) */
-#define FH_ABI_VERSION 6
+ * 6: FH_KIND_ALL_COUNTS, the AllCounts sketcher; 7: fh_batch_new_counts) */
+#define FH_ABI_VERSION 7
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---
@@ -325,8 +326,8 @@ int fh_sketch_device_blocks(fh_sketcher *const *handles, const void *const *dev_
  * caller has staged with one copy, one launch of the sketch kernel over the files' tiles (fh_k2b.hip), one launch of the
  * epilogue (a workgroup per file: select, sort, to_vec straight into pinned host memory, state left reset) and one
  * synchronisation.  Mash sketches of 1..3000 hashes and Scaled sketches (size 0..FH_BATCH_SCALED_MAX, scale as fh_new takes
- * it), k = 1..32, any seed; everything else (AllCounts: FH_ERR_UNSUPPORTED) -- and every file the batch path cannot vouch
- * for -- goes through an fh_sketcher.
+ * it), k = 1..32, any seed; everything else (AllCounts: FH_ERR_UNSUPPORTED here, see fh_batch_new_counts below) -- and every
+ * file the batch path cannot vouch for -- goes through an fh_sketcher.
  * A Scaled file is sketched at max_hash itself (scaled.rs:22-34) and is taken iff it holds at least `size` and at most
  * FH_BATCH_SCALED_MAX distinct hashes at or below max_hash: then the reference's sketch is exactly those hashes, whatever
  * the order of the input (scaled.rs:37-61: a hash <= max_hash is never evicted, one above it never survives a full heap).
@@ -382,6 +383,26 @@ int fh_batch_copy_out_records(fh_batch *b, int slot, uint32_t i, fh_kmer_count *
 int fh_batch_set_profiling(fh_batch *b, int enable);
 int fh_batch_kernel_time(fh_batch *b, double *total_ms, uint64_t *launches, uint64_t *positions);
 int fh_batch_counters(fh_batch *b, uint64_t *taken, uint64_t *not_taken);
+/* Batches of AllCounts files (FH_KIND_ALL_COUNTS, `finch sketch -s none` over many genomes), k = 1..7: a handle of the same
+ * type, served by every fh_batch_* function above with the same staging rules and both input forms.  One launch counts the
+ * forward k-mers of all staged files (a workgroup keeps one file's 4^k histogram in LDS at a time), one launch runs to_vec
+ * per file (a workgroup each) and leaves the device tables zeroed for the next batch.
+ *   k = 0: FH_ERR_INVALID; k >= 8: FH_ERR_UNSUPPORTED (a 4^k table no longer fits a workgroup's LDS: such files go through
+ *   an fh_sketcher); max_files as fh_batch_new; stage_bytes 4 KiB .. 2^21 x 768 - 4096 (FH_ERR_INVALID beyond).  The
+ *   parameter checks come before the device check.
+ * The bound on stage_bytes keeps every file below 2^32 positions in either input form (a slot holds fewer than 2^21 tiles of
+ * the two-bit form).  So no forward count reaches u32::MAX, and count = c[ix] + c[rc] cannot wrap: the two bins count
+ * different windows of one file, and a k-mer that is its own reverse complement cannot start at two adjacent positions (only
+ * a run of one base repeats at distance 1), so 2 c[ix] <= positions as well.  The saturating add and the wrapping sum that an
+ * fh_sketcher carries a bitmap for (above, FH_KIND_ALL_COUNTS) are therefore unreachable here and have no code.
+ * Results per file, as an AllCounts fh_sketcher delivers them: rows ascending by ix, hash = ix, the k-mer bytes its text,
+ * extra_count = c[rc], count = c[ix] + c[rc], ix emitted iff c[ix] > 0 and (rc >= ix or c[rc] == 0); total_kmers = the sum
+ * of the forward counts; first_pos = 0.  Up to (4^k + P) / 2 rows per file, P = the 2^k palindromes of an even k (8192 rows at
+ * k = 7: 96 KiB of pinned result columns per file and slot).
+ * fh_batch_wait reports status 0 for EVERY file -- a count is exact for any input; an empty file or one shorter than k has 0
+ * rows -- and a failure of the batch as a whole by its return value.  A parked counts handle is handed out again by
+ * fh_batch_new_counts only, for the same k, device and sizes; fh_batch_new never sees it. */
+fh_batch *fh_batch_new_counts(uint32_t k, int device, uint32_t max_files, uint64_t stage_bytes);
 
 /* --- measurement support (bench.py) --- */
 /* when enabled, every sketch-kernel launch is bracketed by HIP events on the handle's stream */
