@@ -24,7 +24,9 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
+#include <system_error>
 #include <functional>
 #include <future>
 #include <thread>
@@ -39,6 +41,7 @@
 #include "fh_fqstrip.h"
 #include "fh_pack2.h"
 #include "fh_dist.h"
+#include "fh_slot_pipe.h"
 
 namespace fh {
 uint64_t api_scaled_max_hash(double scale); // fh_internal.h (which needs the HIP headers): a ScaledSketcher's max_hash, scaled.rs:23,31
@@ -74,6 +77,7 @@ public:
     bool run(unsigned n, J job, M mine) {
         if (n == 0 || n > MAX) return false;
         if (!busy_.try_lock()) return false;
+        std::lock_guard<std::mutex> in_use(busy_, std::adopt_lock); // (released on every way out, a throwing mine() included)
         std::function<void(unsigned)> fn = job;
         {
             std::unique_lock<std::mutex> lk(mu_);
@@ -83,7 +87,6 @@ public:
                     ++threads_;
                 }
             } catch (...) {
-                busy_.unlock();
                 return false;
             }
             job_ = &fn;
@@ -92,13 +95,15 @@ public:
             ++gen_;
         }
         cv_.notify_all();
+        struct WaitForTeam { // the helpers run `fn`, which lives in this frame: wait for them even if mine() throws
+            TeamPool &p;
+            ~WaitForTeam() {
+                std::unique_lock<std::mutex> lk(p.mu_);
+                p.cv_done_.wait(lk, [&] { return p.done_ == p.want_; });
+                p.job_ = nullptr;
+            }
+        } wait_for_team{*this};
         mine();
-        {
-            std::unique_lock<std::mutex> lk(mu_);
-            cv_done_.wait(lk, [&] { return done_ == want_; });
-            job_ = nullptr;
-        }
-        busy_.unlock();
         return true;
     }
 
@@ -134,6 +139,14 @@ namespace finch {
 using fh::cfg;
 using fh::cfg_on;
 using fh::cfg_u64;
+using fh::SlotPipe;
+
+// the option `trace`: per-phase timings on stderr (looked at once per process)
+static bool trace_on() {
+    static const bool on = cfg("trace") != nullptr;
+    return on;
+}
+static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 thread_local std::string g_host_err;
 
@@ -1044,13 +1057,12 @@ struct BgzfSource : ByteSource {
     struct Member { size_t in_off, in_len, out_off; uint32_t isize, crc; };
     // inflate the next batch of members into out[0, out_cap) (>= 64 KiB: room for any one member); false = end of
     // input or error; *produced may be 0 for a batch of empty members
-    // FH_TRACE: where a BGZF reader's time goes (compressed reads / member scan / parallel inflate), printed at the end
+    // the option `trace`: where a BGZF reader's time goes (compressed reads / member scan / parallel inflate), printed at the end
     double t_read = 0, t_scan = 0, t_inflate = 0;
     uint64_t n_batches = 0, n_members = 0;
-    static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
     ~BgzfSource() override {
         if (pending.valid()) pending.wait();
-        static const bool trace = cfg("trace") != nullptr;
+        const bool trace = trace_on();
         if (trace && n_batches)
             fprintf(stderr, "[finch] bgzf: %llu batches, %llu members, %u threads: read %.1f ms, scan %.1f ms, inflate %.1f ms\n",
                     (unsigned long long)n_batches, (unsigned long long)n_members, n_thr, t_read * 1e3, t_scan * 1e3, t_inflate * 1e3);
@@ -1376,8 +1388,7 @@ struct ParGzSource : ByteSource {
     std::unique_ptr<ByteSource> tail; // the sequential reader, once it has taken over
     uint64_t n_batches = 0, n_chunks = 0, n_false_starts = 0, sym_total = 0;
     static constexpr size_t CHUNKS_PER_THREAD = 2; // (chunks differ in how long they take: more than one per thread evens that out)
-    double t_fill = 0, t_find = 0, t_decode = 0, t_resolve = 0, t_deliver = 0; // FH_TRACE
-    static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    double t_fill = 0, t_find = 0, t_decode = 0, t_resolve = 0, t_deliver = 0; // (the option `trace`)
 
     ParGzSource(std::unique_ptr<ByteSource> in, unsigned threads) : inner(std::move(in)), n_thr(std::max(2u, threads)) {
         rewindable = inner && inner->can_rewind();
@@ -1387,7 +1398,7 @@ struct ParGzSource : ByteSource {
     ~ParGzSource() override {
         drop_prefetch();
         for (auto &c : ready) recycle(c);
-        static const bool trace = cfg("trace") != nullptr;
+        const bool trace = trace_on();
         if (trace && n_batches)
             fprintf(stderr, "[finch] parallel gzip: %llu batches, %llu chunks (%llu false starts), %.1f %% of the text decoded with markers, %u threads%s\n",
                     (unsigned long long)n_batches, (unsigned long long)n_chunks, (unsigned long long)n_false_starts,
@@ -2258,11 +2269,6 @@ static int fastq_host_strip_to_device(ByteSource &src, fh_sketcher *h, FastxStat
         int slot;
         uint64_t m;
     };
-    std::mutex mu;
-    std::condition_variable cv;
-    bool is_free[2] = {true, true}, producer_done = false;
-    std::vector<Job> ready;
-    std::atomic<bool> abort{false};
     int prc = FH_OK;
     std::string pmsg;
     uint64_t n_rec_total = 0, bases_total = 0;
@@ -2303,8 +2309,7 @@ static int fastq_host_strip_to_device(ByteSource &src, fh_sketcher *h, FastxStat
         }
         wcv.notify_all();
     };
-    static const bool trace = cfg("trace") != nullptr;
-    auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const bool trace = trace_on();
     const double t_begin = now_s();
     // (trace: how long the cgroup's CPU quota held this process's threads back meanwhile -- a team of as many threads as the
     // quota has CPUs, next to the pushing thread and the runtime's, is throttled as soon as anything else runs)
@@ -2324,20 +2329,12 @@ static int fastq_host_strip_to_device(ByteSource &src, fh_sketcher *h, FastxStat
     unsigned n_chunks = 0;
     int rc = FH_OK;
     std::string msg;
-    auto pipeline = [&] { // the reader (a thread of its own: member 0 of the team) and, on this thread, the pushes
-    std::thread producer([&] {
+    bool no_producer = false;
+    auto reader = [&](SlotPipe<Job> &pipe) { // member 0 of the team
         NearMemory::Seat seat(near_text);
         int slot = next;
         size_t off = 0;
-        while (off < n && !abort) {
-            {
-                const double w0 = trace ? now_s() : 0;
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return is_free[slot] || abort.load(); });
-                if (abort) break;
-                is_free[slot] = false;
-                if (trace) t_wait_slot += now_s() - w0;
-            }
+        while (off < n && pipe.acquire(slot)) {
             const double s0 = trace ? now_s() : 0;
             size_t len = std::min(CHUNK, n - off);
             if (off + len < n) { // cut behind the last whole record: the last header line whose line two below is a '+' line
@@ -2380,64 +2377,64 @@ static int fastq_host_strip_to_device(ByteSource &src, fh_sketcher *h, FastxStat
             bases_total += bases_out;
             if (trace) t_strip += now_s() - s0, n_chunks++;
             (void)fh_text_prefetch(h, slot, m_out); // the chunk's copy starts now, behind the previous chunk's
-            {
-                std::lock_guard<std::mutex> g(mu);
-                ready.push_back(Job{slot, m_out});
-            }
-            cv.notify_all();
+            pipe.publish(Job{slot, m_out});
             off += len;
             slot ^= 1;
         }
-        std::lock_guard<std::mutex> g(mu);
-        producer_done = true;
-        cv.notify_all();
-    });
-    int prev_slot = -1;
-    for (;;) {
-        Job job;
-        const double j0 = trace ? now_s() : 0;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return !ready.empty() || producer_done; });
-            if (ready.empty()) break;
-            job = ready.front();
-            ready.erase(ready.begin());
+    };
+    auto pipeline = [&] { // the reader (a thread of its own) and, on this thread, the pushes
+        struct StopHelpers { // on every way out, an exception included: the helpers are parked on state of this call's frame
+            decltype(stop_helpers) &stop;
+            ~StopHelpers() { stop(); }
+        } stop_on_exit{stop_helpers};
+        std::optional<SlotPipe<Job>> started;
+        try {
+            started.emplace(reader);
+        } catch (const std::system_error &) { // no thread to be had
+            no_producer = true;
+            return;
         }
-        const double j1 = trace ? now_s() : 0;
-        t_wait_job += j1 - j0;
-        if (rc == FH_OK) {
-            rc = fh_push_staged(h, job.m, 0u);
-            if (trace) t_push += now_s() - j1;
-            if (rc != FH_OK) {
-                msg = fh_last_error();
-                abort = true;
+        SlotPipe<Job> &pipe = *started;
+        int prev_slot = -1;
+        for (Job job; pipe.next(job);) {
+            if (rc == FH_OK) {
+                const double j1 = trace ? now_s() : 0;
+                rc = fh_push_staged(h, job.m, 0u);
+                if (trace) t_push += now_s() - j1;
+                if (rc != FH_OK) {
+                    msg = fh_last_error();
+                    pipe.abort();
+                }
             }
+            // the slot pushed BEFORE this one is free again: this push waited for its sketch launch (which had waited for its
+            // copy), while the copy out of this one's slot may still be running.  After a failed push: both.
+            if (prev_slot >= 0) pipe.release(prev_slot);
+            if (rc != FH_OK) pipe.release(job.slot);
+            prev_slot = job.slot;
         }
-        // the slot pushed BEFORE this one is free again: this push waited for its sketch launch (which had waited for its copy)
-        std::lock_guard<std::mutex> g(mu);
-        if (prev_slot >= 0) is_free[prev_slot] = true;
-        if (rc != FH_OK) is_free[0] = is_free[1] = true;
-        prev_slot = job.slot;
-        cv.notify_all();
-    }
-    producer.join();
-    stop_helpers();
+        if (pipe.producer_threw()) prc = FH_ERR_CAPACITY, pmsg = "out of host memory";
+        t_wait_slot = pipe.producer_waited();
+        t_wait_job = pipe.consumer_waited();
     };
     // the helpers are the process's parked team threads (TeamPool) where those are free -- starting fifteen threads per call is
     // a millisecond of a 15 ms call, and threads that have just been created run slower than threads that have run -- else
     // threads of this call's own
     if (!TeamPool::instance().run(T - 1, [&](unsigned i) { helper_main(i + 1); }, pipeline)) {
-        std::vector<std::thread> helpers;
+        struct Joined { // (pipeline() has told them to stop on every way out of it)
+            std::vector<std::thread> v;
+            ~Joined() {
+                for (auto &x : v) x.join();
+            }
+        } helpers;
         try {
-            for (unsigned t = 1; t < T; ++t) helpers.emplace_back(helper_main, t);
+            for (unsigned t = 1; t < T; ++t) helpers.v.emplace_back(helper_main, t);
         } catch (...) { // not enough threads: this path is not for now (the helpers that exist wait for a chunk that never comes)
             stop_helpers();
-            for (auto &x : helpers) x.join();
             return FH_ERR_STATE;
         }
         pipeline();
-        for (auto &x : helpers) x.join();
     }
+    if (no_producer) return FH_ERR_STATE; // (as above)
     if (trace)
         fprintf(stderr, "[finch] fastq host strip: %u chunks of <= %.0f MiB of text on %u threads in %.1f ms: strip %.1f ms, producer waited %.1f ms for a buffer, pushes took %.1f ms and waited %.1f ms for chunks; the cgroup throttled its threads for %.1f ms meanwhile\n",
                 n_chunks, CHUNK / 1048576.0, T, (now_s() - t_begin) * 1e3, t_strip * 1e3, t_wait_slot * 1e3, t_push * 1e3, t_wait_job * 1e3,
@@ -2561,9 +2558,8 @@ static int finish_mash_in_place(fh_sketcher *h, const std::string &name, const f
     uint64_t n_view = 0;
     if (fh_result_counts(h, &cnt, &ext, &n_view) != FH_OK || n_view != n) return FH_ERR_STATE;
     const bool filter_on = fp.filter_on == 1;
-    static const bool trace = cfg("trace") != nullptr;
-    auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double tt0 = trace ? now_ms() : 0;
+    const bool trace = trace_on();
+    const double tt0 = trace ? now_s() * 1e3 : 0;
     double tt1 = 0, tt2 = 0, tt3 = 0;
     // Three passes by ONE team of threads, each thread over its own stretch of the records:
     //   1. the strand filter (filtering.rs:413-432) and, for the error filter, the largest count among what it leaves;
@@ -2645,7 +2641,7 @@ static int finish_mash_in_place(fh_sketcher *h, const std::string &name, const f
             if (!(d && d[i]) && lo_t <= cnt[i] && cnt[i] <= hi_t) p.push_back((uint32_t)i);
     });
     if (!team_ok) return hfail(FH_ERR_CAPACITY, "out of host memory");
-    if (trace) tt1 = tt2 = now_ms();
+    if (trace) tt1 = tt2 = now_s() * 1e3;
     std::vector<uint32_t> rows;
     rows.reserve(want);
     for (const auto &p : rows_part) // (thread t took the t-th stretch: rows_part[0] is the lowest)
@@ -2653,7 +2649,7 @@ static int finish_mash_in_place(fh_sketcher *h, const std::string &name, const f
             if (rows.size() >= want) break;
             rows.push_back(r);
         }
-    if (trace) tt3 = now_ms();
+    if (trace) tt3 = now_s() * 1e3;
     if (!sp.no_strict && rows.size() < sp.final_size)
         return hfail(FH_ERR_INVALID, "%s had too few kmers (%zu) to sketch", name.c_str(), rows.size());
     const uint32_t k = sp.kmer_length;
@@ -2671,7 +2667,7 @@ static int finish_mash_in_place(fh_sketcher *h, const std::string &name, const f
     out.sketch_params = sp;
     if (trace)
         fprintf(stderr, "[finch] filters in place (n=%llu): three passes %.2f ms, joining the survivors %.2f ms, rows+records %.2f ms\n",
-                (unsigned long long)n, tt1 - tt0, tt3 - tt2, now_ms() - tt3);
+                (unsigned long long)n, tt1 - tt0, tt3 - tt2, now_s() * 1e3 - tt3);
     return FH_OK;
 }
 
@@ -2899,11 +2895,11 @@ static int sketch_stream(std::unique_ptr<ByteSource> raw, const std::string &nam
     if (int rc = open_source(std::move(raw), src, &is_gz, &first)) return rc;
     FastxStats st;
     const char *dp = cfg("device_parse");
-    // FINCH_DEVICE_PARSE: unset = plain FASTA and FASTQ text is split on the device (FASTQ with the host parser as the
+    // device_parse: unset = plain FASTA and FASTQ text is split on the device (FASTQ with the host parser as the
     // fallback, see below); 1 = on the device, no fallback; 0 = on the host.  Compressed input is inflated on the host
     // and its text treated the same way.
     const bool dp_on = dp && dp[0] == '1', dp_off = dp && dp[0] == '0';
-    // FINCH_DEVICE_INFLATE: unset / 1 = BGZF-compressed FASTQ is inflated on the device (with the host-side inflate as the
+    // device_inflate: unset / 1 = BGZF-compressed FASTQ is inflated on the device (with the host-side inflate as the
     // fallback whenever the device pass refuses the file); 0 = always on the host
     BgzfSource *bgzf_dev = nullptr;
     if (is_gz && !dp_off) {
@@ -2911,7 +2907,7 @@ static int sketch_stream(std::unique_ptr<ByteSource> raw, const std::string &nam
         BgzfSource *bz = dynamic_cast<BgzfSource *>(src.get());
         if (bz && !(di && di[0] == '0') && src->can_rewind() && bz->peek_first_text_byte() == '@') bgzf_dev = bz;
     }
-    // ... and so is plain gzip (FINCH_DEVICE_GZIP=0: on the host, by the call's read threads together, fh_pargz.h)
+    // ... and so is plain gzip (device_gzip=0: on the host, by the call's read threads together, fh_pargz.h)
     bool gzip_dev = false;
     size_t gzip_hdr = 0;
     if (is_gz && !dp_off && !bgzf_dev) {
@@ -2960,7 +2956,7 @@ static int sketch_stream(std::unique_ptr<ByteSource> raw, const std::string &nam
             if (int r2 = fh_text_bases(h, &st.total_bases)) return hfail(r2, "%s", fh_last_error());
             return finish_sketch(h, name, sp, filters, st, out);
         }
-        { // FINCH_DEVICE_GZIP=1: the device pass or nothing (its refusals stay loud)
+        { // device_gzip=1: the device pass or nothing (its refusals stay loud)
             const char *dg = cfg("device_gzip");
             if (dg && dg[0] == '1') return rc;
         }
@@ -2972,7 +2968,7 @@ static int sketch_stream(std::unique_ptr<ByteSource> raw, const std::string &nam
     bool fastq_host_counted = false; // the FASTQ text was stripped on the host (fastq_host_strip_to_device): st has the totals
     if (device_parse && first == '@' && !dp_on && !src->can_rewind()) device_parse = false; // no second chance: host parser
     if (device_parse && first == '@') {
-        // FASTQ on the device has to be strictly 4-line.  Unless the caller insists (FINCH_DEVICE_PARSE=1: errors stay
+        // FASTQ on the device has to be strictly 4-line.  Unless the caller insists (device_parse=1: errors stay
         // loud), a file the device pass rejects is read again through the host parser, which is the judge of what
         // needletail accepts (blank lines between records, ...); sources that cannot rewind start on the host.
         st.format = 2;
@@ -2988,7 +2984,7 @@ static int sketch_stream(std::unique_ptr<ByteSource> raw, const std::string &nam
     }
     if (device_parse && first == '>') {
         st.format = 1;
-        // FINCH_SMALL_FASTA_HOST: unset / 1 = a small plain file is packed while it is staged (fasta_small_on_host), 0 = never
+        // small_fasta_host: unset / 1 = a small plain file is packed while it is staged (fasta_small_on_host), 0 = never
         const char *sh_env = cfg("small_fasta_host");
         const bool small_host = !(sh_env && sh_env[0] == '0');
         int rc = (small_host && !dp_on && !is_gz) ? fasta_small_on_host(*src, h, st) : FH_ERR_STATE;
@@ -3097,6 +3093,7 @@ static int shard_reader(ByteSource &src_ref, bool fastq, uint32_t K, Take take_b
         uint32_t halo_len = 0;
         while ((!eof || !left.empty()) && !abort) {
             TextBuf *b = take_buf();
+            if (!b) break; // (the caller gave up while the reader waited for a buffer)
             uint8_t *buf = b->data();
             const size_t cap = b->size();
             if (left.size() >= cap && fastq) {
@@ -3202,26 +3199,21 @@ static int pump_text_to_device(ByteSource &src, fh_sketcher *h, bool fastq, uint
     if (int rc = fh_text_buffers(h, raw, &cap, &next)) return hfail(rc, "%s", fh_last_error());
     if (!fastq) cap = std::min<uint64_t>(cap, (1ull << 30) - 1);
     TextBuf tb[2] = {TextBuf{raw[0], (size_t)cap, 0}, TextBuf{raw[1], (size_t)cap, 1}};
-    std::mutex mu;
-    std::condition_variable cv;
-    bool is_free[2] = {true, true}, producer_done = false;
     int fill = next; // the slot the next chunk goes to: pushes consume the slots alternately, starting with `next`
-    std::vector<ShardWork> ready;
-    std::atomic<bool> abort{false};
     int prc = FH_OK;
     std::string pmsg;
     FastxStats pst;
-    // FH_TRACE: how long each side waited for the other, and what the pushes took
-    static const bool trace = cfg("trace") != nullptr;
-    auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    // the option `trace`: how long each side waited for the other, and what the pushes took
+    const bool trace = trace_on();
     const double t_begin = now_s();
-    double t_reader_waits = 0, t_pusher_waits = 0, t_push = 0;
+    double t_push = 0;
     unsigned n_chunks = 0;
     if (src.remaining_hint() < cap) {
         // The whole input fits one staging buffer (a genome of a batch: configs[4]): read it and push it right here -- no reader
         // thread to start, hand over to and join per file.
         int rc = FH_OK;
         std::string msg;
+        std::atomic<bool> abort{false};
         const int prc1 = shard_reader(
             src, fastq, k, [&] { return &tb[fill]; }, [&](TextBuf *) {},
             [&](const ShardWork &job) {
@@ -3246,71 +3238,42 @@ static int pump_text_to_device(ByteSource &src, fh_sketcher *h, bool fastq, uint
         st.n_records = pst.n_records;
         return FH_OK;
     }
-    std::thread producer([&] {
-        const int rc = shard_reader(
-            src, fastq, k,
-            [&] {
-                const double t0 = trace ? now_s() : 0;
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return is_free[fill] || abort.load(); });
-                is_free[fill] = false;
-                if (trace) t_reader_waits += now_s() - t0;
-                return &tb[fill];
-            },
-            [&](TextBuf *b) { // taken but not used
-                std::lock_guard<std::mutex> g(mu);
-                is_free[b->id] = true;
-            },
+    int rc = FH_OK;
+    std::string msg;
+    SlotPipe<ShardWork> pipe([&](SlotPipe<ShardWork> &p) {
+        prc = shard_reader(
+            src, fastq, k, [&]() -> TextBuf * { return p.acquire(fill) ? &tb[fill] : nullptr; },
+            [&](TextBuf *b) { p.release(b->id); }, // taken but not used
             [&](const ShardWork &job) {
                 // the chunk's copy to the device starts now, behind the previous chunk's, while that one's push is still busy
                 // with its record-splitting kernel -- the link never idles between pushes
                 (void)fh_text_prefetch(h, job.buf->id, job.len);
-                std::lock_guard<std::mutex> g(mu);
-                ready.push_back(job);
+                p.publish(job);
                 fill ^= 1;
-                cv.notify_all();
             },
-            abort, pst);
-        std::lock_guard<std::mutex> g(mu);
-        prc = rc;
-        if (rc != FH_OK) pmsg = g_host_err; // (thread-local: carried over to the caller's thread below)
-        producer_done = true;
-        cv.notify_all();
+            p.aborted(), pst);
+        if (prc != FH_OK) pmsg = g_host_err; // (thread-local: carried over to the caller's thread below)
     });
-    int rc = FH_OK;
-    std::string msg;
     bool first = true;
-    for (;;) {
-        ShardWork job;
-        const double tw0 = trace ? now_s() : 0;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return !ready.empty() || producer_done; });
-            if (ready.empty()) break;
-            job = ready.front();
-            ready.erase(ready.begin());
-        }
-        const double tw1 = trace ? now_s() : 0;
-        t_pusher_waits += tw1 - tw0;
+    for (ShardWork job; pipe.next(job);) {
         n_chunks++;
         if (rc == FH_OK) {
+            const double tw1 = trace ? now_s() : 0;
             rc = fastq ? fh_push_fastq_text(h, job.len) : fh_push_fasta_text(h, job.len, job.start_state, first ? 0u : FH_PUSH_CONTINUE);
             if (trace) t_push += now_s() - tw1;
             if (rc != FH_OK) {
                 msg = fh_last_error();
-                abort = true;
+                pipe.abort();
             }
             first = false;
         }
-        std::lock_guard<std::mutex> g(mu);
-        is_free[job.buf->id] = true;
-        cv.notify_all();
+        pipe.release(job.buf->id); // the job's own slot (these pushes synchronise with the device once per chunk)
     }
-    producer.join();
     if (trace)
         fprintf(stderr, "[finch] text pump: %u chunks of <= %.0f MiB in %.1f ms: reader waited %.1f ms for a buffer, pushes took %.1f ms and waited %.1f ms for text\n",
-                n_chunks, cap / 1048576.0, (now_s() - t_begin) * 1e3, t_reader_waits * 1e3, t_push * 1e3, t_pusher_waits * 1e3);
+                n_chunks, cap / 1048576.0, (now_s() - t_begin) * 1e3, pipe.producer_waited() * 1e3, t_push * 1e3, pipe.consumer_waited() * 1e3);
     if (rc != FH_OK) return hfail(rc, "%s", msg.c_str());
+    if (pipe.producer_threw()) return hfail(FH_ERR_CAPACITY, "out of host memory");
     if (prc != FH_OK) return hfail(prc, "%s", pmsg.c_str());
     st.total_bases = pst.total_bases;
     st.n_records = pst.n_records;
@@ -3339,34 +3302,23 @@ static int bgzf_fastq_to_device(BgzfSource &bz, fh_sketcher *h) {
         uint32_t n;
         bool last, more; // more: only copied over; inflated together with the jobs that follow (FH_BGZF_MORE)
     };
-    std::mutex mu;
-    std::condition_variable cv;
-    bool is_free[2] = {true, true}, producer_done = false, producer_ok = true;
+    bool producer_ok = true;
     constexpr uint32_t MAX_LAUNCH_MEMBERS = 1u << 16; // (fh_push_bgzf_fastq's limit)
     // members are handed over ~1500 at a time (96 MiB of text): each push starts inflating at once, on one of four side
     // streams, while the next ones are still being read, so the device fills up as the file comes in
     constexpr uint64_t PUSH_TEXT = (uint64_t)96 << 20;
-    std::vector<Job> ready;
-    std::atomic<bool> abort{false};
-    static const bool trace = cfg("trace") != nullptr;
-    auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const bool trace = trace_on();
     const double t_begin = now_s();
-    double t_reader_waits = 0, t_pusher_waits = 0, t_push = 0, t_read = 0;
+    double t_push = 0, t_read = 0;
     uint64_t n_members = 0, n_bytes = 0;
     unsigned n_batches = 0;
-    std::thread producer([&] {
+    int rc = FH_OK;
+    std::string msg;
+    SlotPipe<Job> pipe([&](SlotPipe<Job> &p) {
         int slot = next;
         uint64_t acc_text = 0; // text of the members handed over since the last launch
         uint32_t acc_n = 0;
-        for (;;) {
-            {
-                const double t0 = trace ? now_s() : 0;
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return is_free[slot] || abort.load(); });
-                if (trace) t_reader_waits += now_s() - t0;
-                if (abort) break;
-                is_free[slot] = false;
-            }
+        while (p.acquire(slot)) {
             Job job{slot, 0, 0, false, false};
             uint64_t text = 0;
             bool budget_hit = false;
@@ -3381,7 +3333,6 @@ static int bgzf_fastq_to_device(BgzfSource &bz, fh_sketcher *h) {
             if (budget_hit && acc_text + 65536 <= text_budget) budget_hit = false; // (only this push's share was used up)
             job.more = ok && !job.last && !budget_hit && job.n > 0 && acc_n < MAX_LAUNCH_MEMBERS;
             if (!job.more) acc_text = acc_n = 0;
-            std::lock_guard<std::mutex> g(mu);
             if (!ok) {
                 producer_ok = false;
                 break;
@@ -3389,48 +3340,30 @@ static int bgzf_fastq_to_device(BgzfSource &bz, fh_sketcher *h) {
             if (job.n == 0) job.bytes = 0;
             n_members += job.n;
             n_bytes += job.bytes;
-            ready.push_back(job);
-            cv.notify_all();
+            p.publish(job);
             if (job.last) break;
             slot ^= 1;
         }
-        std::lock_guard<std::mutex> g(mu);
-        producer_done = true;
-        cv.notify_all();
     });
-    int rc = FH_OK;
-    std::string msg;
-    for (;;) {
-        Job job;
-        const double tw0 = trace ? now_s() : 0;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return !ready.empty() || producer_done; });
-            if (ready.empty()) break;
-            job = ready.front();
-            ready.erase(ready.begin());
-        }
-        const double tw1 = trace ? now_s() : 0;
-        t_pusher_waits += tw1 - tw0;
+    for (Job job; pipe.next(job);) {
         n_batches++;
         if (rc == FH_OK) {
+            const double tw1 = trace ? now_s() : 0;
             rc = fh_push_bgzf_fastq(h, job.bytes, job.n, job.last ? FH_BGZF_LAST : job.more ? FH_BGZF_MORE : 0u);
             if (trace) t_push += now_s() - tw1;
             if (rc != FH_OK) {
                 msg = fh_last_error();
-                abort = true;
+                pipe.abort();
             }
         }
-        std::lock_guard<std::mutex> g(mu);
-        is_free[job.slot] = true;
-        cv.notify_all();
+        pipe.release(job.slot); // the job's own slot, after its push
     }
-    producer.join();
     if (trace)
         fprintf(stderr, "[finch] bgzf on the device: %u batches, %llu members, %.1f MB in %.1f ms: reads %.1f ms, reader waited %.1f ms for a buffer, pushes took %.1f ms and waited %.1f ms for members\n",
-                n_batches, (unsigned long long)n_members, n_bytes / 1e6, (now_s() - t_begin) * 1e3, t_read * 1e3, t_reader_waits * 1e3,
-                t_push * 1e3, t_pusher_waits * 1e3);
+                n_batches, (unsigned long long)n_members, n_bytes / 1e6, (now_s() - t_begin) * 1e3, t_read * 1e3, pipe.producer_waited() * 1e3,
+                t_push * 1e3, pipe.consumer_waited() * 1e3);
     if (rc != FH_OK) return hfail(rc == FH_ERR_INVALID ? FH_ERR_INVALID : rc, "%s", msg.c_str());
+    if (pipe.producer_threw()) return hfail(FH_ERR_CAPACITY, "out of host memory");
     if (!producer_ok) return hfail(FH_ERR_INVALID, "not a plain chain of BGZF members");
     return FH_OK;
 }
@@ -3465,29 +3398,18 @@ static int gzip_fastq_to_device(BgzfSource &bz, size_t hdr_len, fh_sketcher *h) 
         uint64_t bytes;
         bool more, last;
     };
-    std::mutex mu;
-    std::condition_variable cv;
-    bool is_free[2] = {true, true}, producer_done = false;
-    std::vector<Job> ready;
-    std::atomic<bool> abort{false};
-    static const bool trace = cfg("trace") != nullptr;
-    auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const bool trace = trace_on();
     const double t_begin = now_s();
-    double t_read = 0, t_push = 0, t_wait = 0;
+    double t_read = 0, t_push = 0;
     uint64_t n_bytes = 0;
     unsigned n_pushes = 0, n_batches = 0;
-    std::thread producer([&] {
+    int rc = FH_OK;
+    std::string msg;
+    SlotPipe<Job> pipe([&](SlotPipe<Job> &p) {
         int slot = next;
         uint64_t acc = 0;
-        for (;;) {
-            if (acc == 0) {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return is_free[slot] || abort.load(); });
-                if (abort) break;
-                is_free[slot] = false;
-            } else if (abort) {
-                break;
-            }
+        // a buffer is taken once per batch and handed over piece by piece
+        while (acc == 0 ? p.acquire(slot) : !p.aborted()) {
             const double t0 = trace ? now_s() : 0;
             const uint64_t want = std::min<uint64_t>(PIECE, cap - acc);
             const size_t got = bz.raw_read(raw[slot] + acc, (size_t)want);
@@ -3495,37 +3417,18 @@ static int gzip_fastq_to_device(BgzfSource &bz, size_t hdr_len, fh_sketcher *h) 
             acc += got;
             const bool eof = got < want;
             Job job{slot, got, !eof && cap - acc >= ((uint64_t)1 << 16), eof};
-            {
-                std::lock_guard<std::mutex> g(mu);
-                n_bytes += got;
-                ready.push_back(job);
-                cv.notify_all();
-            }
+            n_bytes += got;
+            p.publish(job);
             if (eof) break;
             if (!job.more) {
                 slot ^= 1;
                 acc = 0;
             }
         }
-        std::lock_guard<std::mutex> g(mu);
-        producer_done = true;
-        cv.notify_all();
     });
-    int rc = FH_OK;
-    std::string msg;
     bool first = true, done = false;
-    for (;;) {
-        Job job;
-        const double tw0 = trace ? now_s() : 0;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return !ready.empty() || producer_done; });
-            if (ready.empty()) break;
-            job = ready.front();
-            ready.erase(ready.begin());
-        }
+    for (Job job; pipe.next(job);) {
         const double tw1 = trace ? now_s() : 0;
-        t_wait += tw1 - tw0;
         if (rc == FH_OK) {
             if (done) { // bytes behind the member's end
                 if (job.bytes) rc = FH_ERR_INVALID, msg = "more than one gzip member";
@@ -3544,22 +3447,15 @@ static int gzip_fastq_to_device(BgzfSource &bz, size_t hdr_len, fh_sketcher *h) 
                 }
             }
             if (trace) t_push += now_s() - tw1;
-            if (rc != FH_OK) abort = true;
+            if (rc != FH_OK) pipe.abort();
         }
-        if (!job.more) {
-            std::lock_guard<std::mutex> g(mu);
-            is_free[job.slot] = true;
-            cv.notify_all();
-        } else if (rc != FH_OK) {
-            std::lock_guard<std::mutex> g(mu);
-            cv.notify_all();
-        }
+        if (!job.more) pipe.release(job.slot); // the slot goes back after the last piece of its batch
     }
-    producer.join();
     if (trace)
         fprintf(stderr, "[finch] gzip on the device: %u batches in %u pushes, %.1f MB in %.1f ms: reads %.1f ms, pushes took %.1f ms and waited %.1f ms for bytes\n",
-                n_batches, n_pushes, n_bytes / 1e6, (now_s() - t_begin) * 1e3, t_read * 1e3, t_push * 1e3, t_wait * 1e3);
+                n_batches, n_pushes, n_bytes / 1e6, (now_s() - t_begin) * 1e3, t_read * 1e3, t_push * 1e3, pipe.consumer_waited() * 1e3);
     if (rc != FH_OK) return hfail(rc, "%s", msg.c_str());
+    if (pipe.producer_threw()) return hfail(FH_ERR_CAPACITY, "out of host memory");
     if (!done) return hfail(FH_ERR_INVALID, "gzip: the stream ends before its final block");
     return FH_OK;
 }
@@ -3631,7 +3527,7 @@ static int sketch_stream_sharded(std::unique_ptr<ByteSource> raw, const std::str
         W[d]->h = fh_new(&fp, devs[d]);
         if (!W[d]->h) return hfail(FH_ERR_NO_DEVICE, "%s", fh_last_error());
         if (int rc = fh_reset(W[d]->h)) return hfail(rc, "%s", fh_last_error());
-        // (the handles' staging buffers may be smaller than asked for -- the FH_STAGE_BYTES test knob: cut chunks that fit)
+        // (the handles' staging buffers may be smaller than asked for -- the stage_bytes test knob: cut chunks that fit)
         uint8_t *raw2[2] = {nullptr, nullptr};
         uint64_t cap = 0;
         int next = 0;
@@ -4077,7 +3973,7 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
         const uint64_t table = (4ull << (2 * sp->kmer_length)), per_dev = std::max<uint64_t>(1, (32ull << 30) / table);
         n_threads = (uint32_t)std::min<uint64_t>(n_threads, per_dev * devs.size());
     }
-    static const bool trace_call = cfg("trace") != nullptr;
+    const bool trace_call = trace_on();
     const auto call_t0 = std::chrono::steady_clock::now();
     auto res = std::make_unique<finch_sketches>();
     res->v.resize(n_files);
@@ -4175,8 +4071,7 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
         const bool two_bit = !(cfg("batch_two_bit") && cfg("batch_two_bit")[0] == '0'); // how a group's files cross the link
         std::unique_ptr<fh_pack2::Packer> packer;
         std::vector<uint8_t> status;
-        static const bool trace = cfg("trace") != nullptr;
-        auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        const bool trace = trace_on();
         double t_read = 0, t_pack = 0, t_submit = 0, t_wait = 0, t_collect = 0;
         const double t_worker0 = now_s();
         auto collect = [&](int slot) { // wait for the group in `slot`, turn its results into Sketches
