@@ -158,7 +158,7 @@ struct fh_sketcher {
         uint32_t unit_tiles = UNIT_TILES; // queue granularity of this range (1 for inputs that would not fill the chip with 2)
         uint32_t first_units = 0, grid_waves = 0; // the range's first launch: units every wave starts on unasked, and its waves
         uint32_t seg = 0; // != 0: the range runs through the segment kernel with this stride (tiles of 64 / seg_sub x seg positions)
-        uint32_t seg_sub = 1; // lanes per record there (fh_device.h, seg_sub_for)
+        uint32_t seg_sub = 1; // lanes per record there (fh_core.h, seg_sub_for)
         uint32_t max_units = MAX_UNITS; // units a pull takes at most
         int left_cur = 0;
         double admit_at_start = 1.0; // admit rate the range started with (for the novelty estimate)
@@ -1094,11 +1094,11 @@ int sketch_device_range(fh_sketcher *s, const uint8_t *d_seq, uint64_t len, uint
                 probe_behind = true;
             }
             // (records of up to SEG_MAX_RECORD - 1 bases, two or four lanes to a record beyond SEG_MAX_STRIDE; the two-word kernels
-            // take a lane per record only)
-            const uint32_t s_max = s->p.k > 32 ? SEG_MAX_STRIDE : SEG_MAX_RECORD;
-            if (S >= SEG_MIN_STRIDE && S <= s_max && S > s->p.k && n_pos >= 64ull * S) {
+            // take a lane per record only, k < 3 two lanes at most: fh_core.h seg_sub_for, which launch_k2 goes by as well)
+            const uint32_t sub_S = seg_sub_for(s->p.k, S);
+            if (sub_S && n_pos >= 64ull * S) {
                 s->blk_seg = S;
-                s->blk_sub = seg_sub_for(S);
+                s->blk_sub = sub_S;
                 s->gran = seg_tile_pos(S, s->blk_sub);
             } else if (seg_ragged_k((int)s->p.k) && n_pos >= 64ull * SEG_RAGGED_STRIDE) {
                 // no one stride, but records of a few hundred bases at most (a breaker in every 256 bytes the probe looked at, or

@@ -457,6 +457,108 @@ FH_HD u32 window_valid_mask(u64 g64) { return (u32)window_valid_mask64<K>(g64); 
 constexpr bool seg_long(int K) { return FH_SEG_LONG && (K <= FH_SEG_LONG_MAXK || (K == 26 && FH_SEG_LONG_MAXK == 24)); }
 constexpr int seg_round(int K) { return seg_long(K) ? (65 - K < 48 ? 65 - K : 48) : (K >= 23 ? 16 : 32); }
 constexpr int seg_doff(int K) { return seg_long(K) ? pre_shift(K) / 2 : 0; }
+// Rounds of 16 unrolled positions (the K whose registers allow no more) come in PAIRS (fh_k2s.hip): seg_ro = a round's positions
+// as the tile's bookkeeping counts them.  FH_SEG_HALVES=0: single rounds of 16.
+#ifndef FH_SEG_HALVES
+#define FH_SEG_HALVES 1
+#endif
+constexpr int seg_halves(int K) { return (FH_SEG_HALVES && !seg_long(K) && seg_round(K) == 16) ? 2 : 1; }
+constexpr int seg_ro(int K) { return seg_round(K) * seg_halves(K); }
+
+// ---- the segment kernels' geometry (fh_k2s.hip K = 1..32, fh_k2ws.hip K = 33..64) ----
+// Stated ONCE, for the kernels, for the host code that picks a kernel (fh_api.hip sketch_device_range, fh_kernels.hip launch_k2)
+// and for the host sweep over every (k, stride) (tests/hostcore/fhcore_host.cpp, tests/test_seg_geometry_host.py).
+//
+// A lane owns one SEGMENT of `stride` consecutive k-mer start positions instead of 32, a tile is 64 segments.  With the stride
+// of fixed-length records (read length + 1) the windows that cross a record's breaker sit at the end of every lane's segment and
+// are skipped for the whole wave -- 21 of 151 positions at k = 21, 31 at k = 31; the result does not depend on the stride (a
+// round of positions is skipped only when no lane has a valid window in it).
+constexpr u32 SEG_MIN_STRIDE = 40, SEG_MAX_STRIDE = 168; // (what a wave's share of the 160 KB of LDS holds two strings of)
+// Records longer than a lane's segment may be (2 x 250 / 2 x 300 reads: strides 251, 301) are shared by TWO or FOUR lanes
+// (SketchArgs::seg_sub): a tile is then 32 or 16 records, its strings the same 10.7 KB at most, and the record's valid windows
+// are dealt out evenly -- the first lanes take H = ceil((stride - K) / sub) start positions each, the last lane the rest, LAST,
+// with the K positions behind the last window -- so that every lane of the wave runs out of valid windows in the same round.
+constexpr u32 SEG_MAX_RECORD = 4 * SEG_MAX_STRIDE;
+// LAST - H = K - pad with pad = sub H - (stride - K) in 0..sub-1: the rounds and a round's length go by LAST, so the front lanes
+// lose their offsets [LAST, H) where pad > K -- four lanes at K = 1 (half of the strides) and K = 2 (a quarter).  Those K do not
+// get the four-lane form: their blocks of such strides take the tile kernel.
+#ifndef FH_SEG_SUB4_MIN_K
+#define FH_SEG_SUB4_MIN_K 3 // (1: the form as it was up to the geometry sweep, which fails with it)
+#endif
+// lanes per record for k-mers of k bases in records of `stride` start positions; 0: no segment kernel takes the pair
+constexpr u32 seg_sub_for(u32 k, u32 stride) {
+    if (k < 1u || k > 64u || stride < SEG_MIN_STRIDE || stride <= k) return 0u;
+    if (k > 32u) return stride <= SEG_MAX_STRIDE ? 1u : 0u; // (the two-word kernels take a lane per record only)
+    if (stride <= SEG_MAX_STRIDE) return 1u;
+    if (stride <= 2u * SEG_MAX_STRIDE) return 2u;
+    return stride <= SEG_MAX_RECORD && k >= (u32)FH_SEG_SUB4_MIN_K ? 4u : 0u;
+}
+// what launch_k2 accepts as SketchArgs::seg_stride / seg_sub of a fixed-stride launch (seg_sub 0 reads as 1)
+constexpr bool seg_launch_ok(u32 k, u32 stride, u32 sub) { return seg_sub_for(k, stride) != 0u && (sub ? sub : 1u) == seg_sub_for(k, stride); }
+// RAGGED records (trimmed reads: no stride fits): SketchArgs::seg_sub == SEG_RAGGED with seg_stride == SEG_RAGGED_STRIDE.  A lane
+// looks at SEG_RAGGED_STRIDE positions of the tile in cells of 32; a cell that holds valid windows becomes a WORK ITEM (from its
+// first to its last valid window), the items are ordered by size class in the wave's LDS and dealt out 64 a round -- a round
+// ends behind the longest of its items, and cells without a window cost nothing (fh_k2s.hip).  K = 25, 27..32 only (rounds of 32
+// positions; the K that live off the LDS pipe, where every window not hashed is lookups saved: docs/MEASUREMENTS_r06.md 4).
+constexpr u32 SEG_RAGGED = 0x100u, SEG_RAGGED_STRIDE = 128u;
+constexpr bool seg_ragged_k(int k) { return k == 25 || (k >= 27 && k <= 32); }
+constexpr u32 seg_tile_pos(u32 stride, u32 sub) { return sub == SEG_RAGGED ? 64u * stride : (64u / sub) * stride; } // start positions of a tile (a multiple of 16)
+// (the segment kernels' leftover lists hold TRIPLES (t0, t1, c0): tiles [t0, t1), t0 from round c0 on -- a wave may stop inside a tile)
+
+// LDS words of a wave's strings (K <= 32: Fc, Rv, Gd; K > 32: one code string and the good bits)
+constexpr u32 K2S_NCH_MAX = 4 * SEG_MAX_STRIDE + 6; // 16-byte chunks of a tile with its 96-byte halo
+constexpr u32 K2S_FC_DW = K2S_NCH_MAX + 3, K2S_RV_DW = K2S_NCH_MAX + 2, K2S_G_DW = K2S_NCH_MAX / 2 + 3;
+constexpr u32 K2WS_NCH_MAX = 4 * SEG_MAX_STRIDE + 8;                           // 16-byte chunks of a tile with its 128-byte halo
+constexpr u32 K2WS_C_DW = K2WS_NCH_MAX + 2, K2WS_G_DW = K2WS_NCH_MAX / 2 + 4; // codes: chunk i at word i; good bits: at half-word i
+
+FH_HD u32 seg_sub_sat(u32 a, u32 b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_elementwise_sub_sat(a, b);
+#else
+    return a > b ? a - b : 0u;
+#endif
+}
+// A record of S start positions belongs to 1 << SH lanes: the first ones take H positions each, the last one the rest (LAST).
+// SH = 0: a lane per record, H = LAST = S.  Everything here is wave-uniform.
+struct SegGeom {
+    u32 SH, SUBM;  // lanes per record = 1 << SH = SUBM + 1
+    u32 H, LAST;   // start positions of a record's front lanes / of its last lane
+    u32 tile_pos;  // start positions of a tile (64 >> SH records)
+    u32 NCH;       // 16-byte chunks of the tile's strings (with the 96-byte halo)
+    u32 NR;        // rounds per tile
+};
+FH_HD u32 seg_shift(u32 sub) { return sub >= 4u ? 2u : sub >= 2u ? 1u : 0u; }
+FH_HD SegGeom seg_geom(u32 K, u32 RO, u32 S, u32 SH) {
+    SegGeom g;
+    g.SH = SH;
+    g.SUBM = (1u << SH) - 1u;
+    g.H = SH ? (S - K + g.SUBM) >> SH : S;
+    g.LAST = S - g.SUBM * g.H;
+    g.tile_pos = (64u >> SH) * S;
+    g.NCH = (g.tile_pos >> 4) + 6u;
+    g.NR = (g.LAST + RO - 1u) / RO;
+    return g;
+}
+// where lane l's segment begins in the tile
+FH_HD u32 seg_start(const SegGeom &g, u32 S, u32 l) { return S * (l >> g.SH) + (l & g.SUBM) * g.H; }
+// round c's first segment offset (wave-uniform); the lane's view of the round begins at tile position seg_start + seg_round_off
+FH_HD u32 seg_round_off(u32 RO, u32 c) { return RO * c; }
+// positions of the (longest) segment the round at offset rc0 covers (wave-uniform, <= RO)
+FH_HD u32 seg_round_nmax(const SegGeom &g, u32 RO, u32 rc0) { return g.LAST - rc0 < RO ? g.LAST - rc0 : RO; }
+// what is left of the lane's own share at offset rc0 (the lanes in front of a record's last one own H positions, not LAST)
+FH_HD u32 seg_lane_own(const SegGeom &g, u32 lane, u32 rc0) { return seg_sub_sat((lane & g.SUBM) == g.SUBM ? g.LAST : g.H, rc0); }
+// positions lane `lane` may take in the round at offset rc0, before the launch's range (tile_room) and validity cut them down
+FH_HD u32 seg_lane_take(const SegGeom &g, u32 RO, u32 lane, u32 rc0) {
+    const u32 nmax = seg_round_nmax(g, RO, rc0), own = seg_lane_own(g, lane, rc0);
+    return g.SH ? (nmax < own ? nmax : own) : nmax;
+}
+// The two-word kernel: a lane per record, rounds of 32 positions, a 96-base view (128-byte halo)
+struct SegGeomW {
+    u32 tile_pos, NCH, NR;
+};
+FH_HD SegGeomW segw_geom(u32 S) { return SegGeomW{64u * S, 4u * S + 8u, (S + 31u) / 32u}; }
+FH_HD u32 segw_start(u32 S, u32 l) { return S * l; }
+FH_HD u32 segw_round_nmax(u32 S, u32 rc0) { return S - rc0 < 32u ? S - rc0 : 32u; }
 
 template <int K>
 FH_HD void seg_cut_views(const u32 *Fc, const u32 *Rv, u32 NCH, u32 p0, u32 *nc, u32 *d) {

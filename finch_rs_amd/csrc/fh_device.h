@@ -13,6 +13,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "fh_core.h"
+
 namespace fh {
 
 struct Entry {          // 40 B
@@ -116,26 +118,9 @@ constexpr int MAX_UNITS = FH_MAX_UNITS;   // (guided self-scheduling: big pulls 
 constexpr int WAVE_OVERSHOOT = 3072 + 64;
 constexpr int WAVE_BUDGET = 2048; // + at most TILE_POS-1 overshoot inside the tile that crosses it   // tiles a wave pulls from the queue at a time (contiguous: halo reuse)
 
-// The segment kernel (fh_k2s.hip): a lane owns one SEGMENT of seg_stride consecutive k-mer start positions instead of 32, a
-// tile is 64 segments.  With the stride of fixed-length records (read length + 1) the windows that cross a record's breaker
-// sit at the end of every lane's segment and are skipped for the whole wave -- 21 of 151 positions at k = 21, 31 at k = 31;
-// the result does not depend on the stride (a round of positions is skipped only when no lane has a valid window in it).
-constexpr uint32_t SEG_MIN_STRIDE = 40, SEG_MAX_STRIDE = 168; // (what a wave's share of the 160 KB of LDS holds two strings of)
-// Records longer than a lane's segment may be (2 x 250 / 2 x 300 reads: strides 251, 301) are shared by TWO or FOUR lanes
-// (SketchArgs::seg_sub): a tile is then 32 or 16 records, its strings the same 10.7 KB at most, and the record's valid windows
-// are dealt out evenly -- the first lanes take ceil((stride - K) / sub) start positions each, the last lane the rest with the K
-// positions behind the last window -- so that every lane of the wave runs out of valid windows in the same round.
-constexpr uint32_t SEG_MAX_RECORD = 4 * SEG_MAX_STRIDE;
-constexpr uint32_t seg_sub_for(uint32_t stride) { return stride <= SEG_MAX_STRIDE ? 1u : stride <= 2 * SEG_MAX_STRIDE ? 2u : stride <= SEG_MAX_RECORD ? 4u : 0u; }
-// RAGGED records (trimmed reads: no stride fits): SketchArgs::seg_sub == SEG_RAGGED with seg_stride == SEG_RAGGED_STRIDE.  A lane
-// looks at SEG_RAGGED_STRIDE positions of the tile in cells of 32; a cell that holds valid windows becomes a WORK ITEM (from its
-// first to its last valid window), the items are ordered by size class in the wave's LDS and dealt out 64 a round -- a round
-// ends behind the longest of its items, and cells without a window cost nothing (fh_k2s.hip).  K = 25, 27..32 only (rounds of 32
-// positions; the K that live off the LDS pipe, where every window not hashed is lookups saved: docs/MEASUREMENTS_r06.md 4).
-constexpr uint32_t SEG_RAGGED = 0x100u, SEG_RAGGED_STRIDE = 128u;
-constexpr bool seg_ragged_k(int k) { return k == 25 || (k >= 27 && k <= 32); }
-constexpr uint32_t seg_tile_pos(uint32_t stride, uint32_t sub) { return sub == SEG_RAGGED ? 64u * stride : (64u / sub) * stride; } // start positions of a tile (a multiple of 16)
-// (the segment kernels' leftover lists hold TRIPLES (t0, t1, c0): tiles [t0, t1), t0 from round c0 on -- a wave may stop inside a tile)
+// The segment kernels' geometry -- SEG_MIN_STRIDE, SEG_MAX_STRIDE, SEG_MAX_RECORD, seg_sub_for(k, stride), SEG_RAGGED, seg_tile_pos,
+// the split of a record over lanes and of a segment over rounds -- is stated once in fh_core.h ("the segment kernels' geometry"),
+// where the host sweep over every (k, stride) compiles it too.
 
 struct SketchArgs {
     const uint8_t *seq;   // packed stream (device), 16-byte aligned

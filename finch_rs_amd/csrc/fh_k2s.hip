@@ -56,8 +56,7 @@ static_assert(64 * 48 + QCAP <= WAVE_OVERSHOOT, "a round's positions are what a 
 // LDS of the workgroup: lookup tables, admit queues, then a block per wave
 constexpr u32 K2S_A1 = 0, K2S_A2 = 4096, K2S_B1 = 8192, K2S_B2 = 10240, K2S_P = 12288, K2S_Q = 20480;
 constexpr u32 K2S_TILE = K2S_Q + K2S_WPB * (u32)sizeof(AdmitQueueT<false>);
-constexpr u32 K2S_NCH_MAX = 4 * SEG_MAX_STRIDE + 6; // 16-byte chunks of a tile with its 96-byte halo
-constexpr u32 K2S_FC_DW = K2S_NCH_MAX + 3, K2S_RV_DW = K2S_NCH_MAX + 2, K2S_G_DW = K2S_NCH_MAX / 2 + 3;
+// (K2S_NCH_MAX, K2S_FC_DW, K2S_RV_DW, K2S_G_DW: the strings' words, fh_core.h)
 constexpr u32 K2S_WAVE_DW = (K2S_FC_DW + K2S_RV_DW + K2S_G_DW + 3) / 4 * 4;
 constexpr u32 K2S_BYTES = K2S_TILE + K2S_WPB * 4 * K2S_WAVE_DW;
 static_assert(K2S_BYTES <= 160 * 1024, "one workgroup's LDS");
@@ -101,11 +100,8 @@ __global__ __launch_bounds__(64 * K2S_WPB, 4) void k2_sketch_seg(const SketchArg
     using Mask = std::conditional_t<LONG, u64, u32>; // a round's valid windows
     // Rounds of 16 unrolled positions (the K whose registers allow no more: fh_core.h, seg_long) come in PAIRS: one set-up -- the
     // validity mask, the wave's question, the two views -- serves 32 positions, the strings are moved on 32 bits in between as
-    // in k2_sketch (Windows::advance<16>).  RO = a round's positions as the tile's bookkeeping counts them.
-#ifndef FH_SEG_HALVES
-#define FH_SEG_HALVES 1
-#endif
-    constexpr int HALVES = (FH_SEG_HALVES && !LONG && R == 16) ? 2 : 1, RO = R * HALVES;
+    // in k2_sketch (Windows::advance<16>).  RO = a round's positions as the tile's bookkeeping counts them (fh_core.h, seg_ro).
+    constexpr int HALVES = seg_halves(K), RO = seg_ro(K);
     static_assert(RO + K - 1 <= 64, "a round's windows lie inside the lane's 64-base view");
     __shared__ __attribute__((aligned(16))) unsigned char blob[K2S_BYTES];
     Rec4 *const sA1 = (Rec4 *)(blob + K2S_A1), *const sA2 = (Rec4 *)(blob + K2S_A2);
@@ -147,18 +143,16 @@ __global__ __launch_bounds__(64 * K2S_WPB, 4) void k2_sketch_seg(const SketchArg
     u32 *const Rv = Fc + K2S_FC_DW;                                      // digit-reversed codes: chunk i at word NCH - 1 - i
     u32 *const Gd = Rv + K2S_RV_DW;                                      // good bits: chunk i at half-word i
     // A record of S start positions belongs to 1 << SH lanes: the first ones take H positions each, the last one the rest
-    // (LAST >= H: it holds the K positions behind the record's last window).  SH = 0: a lane per record, H = LAST = S.
+    // (LAST >= H: it holds the K positions behind the record's last window -- for every (K, S, lanes) launch_k2 lets through).
+    // SH = 0: a lane per record, H = LAST = S.  The split and the rounds' bookkeeping are fh_core.h's (seg_geom and what follows
+    // it), which the host sweep walks for every k and stride (tests/test_seg_geometry_host.py).
     const u32 S = (u32)__builtin_amdgcn_readfirstlane((int)a.seg_stride);
-    // RAG: records of many lengths -- the lanes' cells become work items, 64 a round (fh_device.h, SEG_RAGGED); not for the K whose
+    // RAG: records of many lengths -- the lanes' cells become work items, 64 a round (fh_core.h, SEG_RAGGED); not for the K whose
     // rounds are longer than 32 positions
     const bool RAG = !LONG && RO == 32 && (u32)__builtin_amdgcn_readfirstlane((int)a.seg_sub) == SEG_RAGGED;
-    const u32 SH = RAG ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)(a.seg_sub >= 4u ? 2u : a.seg_sub >= 2u ? 1u : 0u));
-    const u32 SUBM = (1u << SH) - 1u;
-    const u32 H = SH ? (S - (u32)K + SUBM) >> SH : S, LAST = S - SUBM * H;
-    const u32 tile_pos = (64u >> SH) * S;
-    const u32 NCH = (tile_pos >> 4) + 6u, NR = (LAST + (u32)RO - 1u) / (u32)RO;
-    // where lane l's segment begins in the tile, and how long it is
-    auto seg_start = [&](u32 l) -> u32 { return S * (l >> SH) + (l & SUBM) * H; };
+    const u32 SH = RAG ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)seg_shift(a.seg_sub));
+    const SegGeom G = seg_geom((u32)K, (u32)RO, S, SH);
+    const u32 tile_pos = G.tile_pos, NCH = G.NCH, NR = G.NR;
     // RAG: the tile's work items (start position | windows << 16), at most 256, in the room the strings of a 128-position stride
     // leave behind them (two halves: behind the complemented codes and behind the reversed ones; 8 words of zeroes stay between)
     u32 *const ItA = Fc + (NCH + 8u), *const ItB = Rv + (NCH + 8u);
@@ -308,13 +302,13 @@ __global__ __launch_bounds__(64 * K2S_WPB, 4) void k2_sketch_seg(const SketchArg
             }
 #pragma unroll 1
             for (u32 c = c_first; c < NRt; ++c) {
-                const u32 rc0 = RAG ? 0u : (u32)RO * c; // the round's first segment offset (wave-uniform)
+                const u32 rc0 = RAG ? 0u : seg_round_off((u32)RO, c); // the round's first segment offset (wave-uniform)
                 Win win;
                 Mask Wc;
-                u32 nmax = RAG ? (u32)RO : (LAST - rc0 < (u32)RO ? LAST - rc0 : (u32)RO); // positions of the (longest) segment this round covers
+                u32 nmax = RAG ? (u32)RO : seg_round_nmax(G, (u32)RO, rc0); // positions of the (longest) segment this round covers
                 {
                     const u32 lane = lane_now();
-                    u32 p0 = seg_start(lane) + rc0; // the lane's view begins at this tile position
+                    u32 p0 = seg_start(G, S, lane) + rc0; // the lane's view begins at this tile position
                     u32 item_n = 0;
                     if (RAG) { // the lane's work item of this round (none: no windows)
                         const u32 ii = 64u * c + lane;
@@ -327,7 +321,7 @@ __global__ __launch_bounds__(64 * K2S_WPB, 4) void k2_sketch_seg(const SketchArg
                     u32 limit = __builtin_elementwise_sub_sat(tile_room, p0);
                     limit = limit < nmax ? limit : nmax; // <= RO
                     if (SH) { // (wave-uniform: the lanes in front of a record's last one own H positions, not LAST)
-                        const u32 own = __builtin_elementwise_sub_sat((lane & SUBM) == SUBM ? LAST : H, rc0);
+                        const u32 own = seg_lane_own(G, lane, rc0);
                         limit = limit < own ? limit : own;
                     }
                     if (RAG) limit = limit < item_n ? limit : item_n;
@@ -402,7 +396,7 @@ __global__ __launch_bounds__(64 * K2S_WPB, 4) void k2_sketch_seg(const SketchArg
                                 queue->ka[my] = hp.ka;
                                 queue->kb[my] = hp.kb;
                                 queue->k[my] = cm;
-                                u32 p_here = seg_start(lane_now()) + rc0;
+                                u32 p_here = seg_start(G, S, lane_now()) + rc0;
                                 if (RAG) p_here = *item_ptr(64u * c + lane_now()) & 0xFFFFu; // (a candidate's lane has an item)
                                 const u64 pos = tile_stream_pos + (u64)(p_here + (u32)(h * R + j));
                                 bool is_rc = rc_loop;

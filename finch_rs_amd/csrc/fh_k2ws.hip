@@ -23,8 +23,7 @@
 
 namespace fh {
 
-constexpr u32 K2WS_NCH_MAX = 4 * SEG_MAX_STRIDE + 8;                  // 16-byte chunks of a tile with its 128-byte halo
-constexpr u32 K2WS_C_DW = K2WS_NCH_MAX + 2, K2WS_G_DW = K2WS_NCH_MAX / 2 + 4; // codes: chunk i at word i; good bits: at half-word i
+// (K2WS_NCH_MAX, K2WS_C_DW, K2WS_G_DW: the strings' words, fh_core.h -- codes: chunk i at word i; good bits: at half-word i)
 constexpr int K2WS_MAX_LOADS = (K2WS_NCH_MAX + 63) / 64;
 
 __device__ __forceinline__ u32 wave_or_w(u32 x) { // (fh_k2s.hip, wave_or)
@@ -76,8 +75,8 @@ __global__ __launch_bounds__(256, 2) void k2_sketch_ws(const SketchArgs a) {
     u32 *const Cd = sC[wave];
     u32 *const Gd = sG[wave];
     const u32 S = (u32)__builtin_amdgcn_readfirstlane((int)a.seg_stride);
-    const u32 NCH = 4u * S + 8u, NR = (S + 31u) / 32u;
-    const u32 tile_pos = 64u * S;
+    const SegGeomW G = segw_geom(S); // (fh_core.h: the host sweep walks the same rounds)
+    const u32 NCH = G.NCH, NR = G.NR, tile_pos = G.tile_pos;
     u32 nvalid = 0;
 #define FLUSHWS(ctl_, q_, qn_, shard_) ([&] { const u32 r_ = (u32)__builtin_amdgcn_readfirstlane((int)flush_queue<true>(ctl_, q_, qn_, shard_)); want_refresh |= r_ >> 31; return r_ & 0x7FFFFFFFu; }())
     u32 wave_inserts = 0, qn = 0, want_refresh = 0;
@@ -154,8 +153,8 @@ __global__ __launch_bounds__(256, 2) void k2_sketch_ws(const SketchArgs a) {
 #pragma unroll 1
             for (u32 c = c_first; c < NR; ++c) {
                 const u32 rc0 = 32u * c;
-                const u32 p0 = S * (u32)lane + rc0; // the lane's 96-base view begins at this tile position
-                u32 nmax = S - rc0 < 32u ? S - rc0 : 32u;
+                const u32 p0 = segw_start(S, (u32)lane) + rc0; // the lane's 96-base view begins at this tile position
+                u32 nmax = segw_round_nmax(S, rc0);
                 const u32 wi = p0 >> 4, ws = (2u * p0) & 31u; // codes: 16 bases a word
                 const u32 gi = p0 >> 5, gs = p0 & 31u;
                 u32 cw[7], gw4[4];

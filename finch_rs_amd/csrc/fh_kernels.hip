@@ -21,7 +21,7 @@ hipError_t launch_k2(int k, const SketchArgs &a, int blocks, hipStream_t st) {
     static_assert(FH_NPARTS == 4, "dispatcher below is written for 4 parts");
     if (k < 1 || k > FH_MAX_K) return hipErrorInvalidValue;
     if (k > 32 && a.seg_stride) { // two-word k-mers, segment form (fh_k2ws.hip)
-        if (a.seg_stride < SEG_MIN_STRIDE || a.seg_stride > SEG_MAX_STRIDE || a.seg_sub > 1u) return hipErrorInvalidValue;
+        if (!seg_launch_ok((uint32_t)k, a.seg_stride, a.seg_sub)) return hipErrorInvalidValue; // (fh_core.h: a lane per record, strides up to SEG_MAX_STRIDE)
         switch ((k - 33) / (32 / FH_NPARTS)) {
         case 0: return launch_k2ws_part0(k, a, st);
         case 1: return launch_k2ws_part1(k, a, st);
@@ -41,8 +41,8 @@ hipError_t launch_k2(int k, const SketchArgs &a, int blocks, hipStream_t st) {
         const uint32_t sub = a.seg_sub ? a.seg_sub : 1u;
         if (sub == SEG_RAGGED) {
             if (a.seg_stride != SEG_RAGGED_STRIDE || !seg_ragged_k(k) || a.tau_lo || a.hash_mask != ~0ull) return hipErrorInvalidValue;
-        } else if (a.seg_stride < SEG_MIN_STRIDE || (sub != 1u && sub != 2u && sub != 4u) || (a.seg_stride + sub - 1u) / sub > SEG_MAX_STRIDE ||
-                   a.seg_stride <= (uint32_t)k || a.tau_lo || a.hash_mask != ~0ull) {
+        } else if (!seg_launch_ok((uint32_t)k, a.seg_stride, sub) || a.tau_lo || a.hash_mask != ~0ull) {
+            // (the lanes per record are what seg_sub_for(k, stride) says, fh_core.h: the one split the geometry sweep has walked)
             return hipErrorInvalidValue;
         }
         switch ((k - 1) / (32 / FH_NPARTS)) {

@@ -238,7 +238,7 @@ int fh_push_device(fh_sketcher *s, const void *dev_bytes, uint64_t len);
  * once) -- so a handle's first block below 256 MiB runs the tile kernel.  With a stride the block is sketched by a kernel that
  * does not hash the k positions of every record whose window crosses its breaker (fh_k2s.hip; the reference's canonical_kmers
  * yields len - k + 1 windows per record, mash.rs:76): strides 40..168 one lane per record, 169..336 two, 337..672 four
- * (k > 32: 40..168 only); any seed.  A TUNING hint: the sketch is the same bit for bit whatever is said here, also when it is
+ * (k > 32: 40..168 only; k < 3: 40..336 only -- every other block runs the tile kernel); any seed.  A TUNING hint: the sketch is the same bit for bit whatever is said here, also when it is
  * wrong or stale (tests/test_gpu_segments.py).  Strides outside those ranges are taken as 1. */
 int fh_set_record_stride(fh_sketcher *s, uint32_t stride);
 /* debug / tests: launches of the segment kernel, blocks probed for a stride, the stride of the last block (0: none) */

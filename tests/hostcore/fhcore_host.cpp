@@ -223,3 +223,100 @@ extern "C" void fhcore_classify(const uint8_t *bytes, uint64_t n_chunks, uint32_
         classify_chunk(d[0], d[1], d[2], d[3], codes[c], good[c]);
     }
 }
+
+// ---- the segment kernels' geometry (fh_core.h: seg_sub_for, seg_geom, seg_lane_take, segw_geom ...) ----
+// One tile walked the way k2_sketch_seg<k> / k2_sketch_ws<k> walk it, with the helpers the kernels compile: every lane, every
+// round, every position a lane may take before the launch's range and validity cut it down.  0 = all is well; otherwise which
+// property fails (tests/test_seg_geometry_host.py names them):
+//   1 a tile offset nobody takes      2 a tile offset taken twice (a doubled count)      3 a lane takes more than a round holds
+//   4 a position outside the tile     5 a view that leaves the tile's strings            6 LDS words outside K2S_*_DW / K2WS_*_DW
+//   7 rounds >= c0 and rounds < c0 do not make up the tile for some resume round c0      8 no such kernel form
+// `lost`, if given, receives the number of tile offsets nobody takes.
+extern "C" int fhcore_seg_check(uint32_t k, uint32_t S, uint32_t sub, uint32_t *lost) {
+    if (lost) *lost = 0;
+    if (k < 1 || k > 64 || S <= k || (sub != 1 && sub != 2 && sub != 4) || (k > 32 && sub != 1)) return 8;
+    std::vector<uint8_t> taken;
+    std::vector<u32> per_round;
+    u32 tile_pos, NR;
+    int rc = 0;
+    auto fail = [&](int code) { if (!rc) rc = code; };
+    if (k <= 32) {
+        const u32 RO = (u32)seg_ro((int)k), DOFF = (u32)seg_doff((int)k), ND = DOFF ? 5u : 4u;
+        const int PRE = pre_shift((int)k);
+        const SegGeom g = seg_geom(k, RO, S, seg_shift(sub));
+        tile_pos = g.tile_pos, NR = g.NR;
+        if (tile_pos != seg_tile_pos(S, sub) || (tile_pos & 15u)) fail(4);
+        taken.assign(tile_pos, 0);
+        per_round.assign(NR, 0);
+        // phase A: chunk i < NCH goes to Fc[1 + i], Rv[NCH - 1 - i], half-word i of Gd
+        if (g.NCH > K2S_NCH_MAX || g.NCH + 1u > K2S_FC_DW || g.NCH > K2S_RV_DW || (g.NCH + 1u) / 2u > K2S_G_DW) fail(6);
+        for (u32 c = 0; c < NR; ++c) {
+            const u32 rc0 = seg_round_off(RO, c);
+            for (u32 lane = 0; lane < 64; ++lane) {
+                const u32 p0 = seg_start(g, S, lane) + rc0;
+                // the views are cut for every lane of a running round, whatever it takes (seg_cut_views, seg_good_bits)
+                if (!(p0 + 63u + DOFF < 16u * g.NCH)) fail(5);
+                const int gc = (int)(2u * p0) - PRE;
+                const u32 ic = (u32)((gc >> 5) + 1);
+                const u32 gd = 2u * (16u * g.NCH - 64u - DOFF - p0), id = gd >> 5;
+                if (gc < -32 || ic + 5u >= K2S_FC_DW || id + ND >= K2S_RV_DW || (p0 >> 5) + 2u >= K2S_G_DW) fail(6);
+                const u32 n = seg_lane_take(g, RO, lane, rc0);
+                if (n > RO) fail(3);
+                for (u32 j = 0; j < n && j < RO; ++j) {
+                    if (p0 + j >= tile_pos) { fail(4); continue; }
+                    if (taken[p0 + j] < 255) taken[p0 + j]++;
+                    per_round[c]++;
+                }
+            }
+        }
+    } else {
+        const SegGeomW g = segw_geom(S);
+        tile_pos = g.tile_pos, NR = g.NR;
+        taken.assign(tile_pos, 0);
+        per_round.assign(NR, 0);
+        if (g.NCH > K2WS_NCH_MAX || g.NCH > K2WS_C_DW || (g.NCH + 1u) / 2u > K2WS_G_DW) fail(6);
+        for (u32 c = 0; c < NR; ++c) {
+            const u32 rc0 = 32u * c;
+            for (u32 lane = 0; lane < 64; ++lane) {
+                const u32 p0 = segw_start(S, lane) + rc0;
+                if (!(p0 + 95u < 16u * g.NCH)) fail(5); // a 96-base view
+                if ((p0 >> 4) + 6u >= K2WS_C_DW || (p0 >> 5) + 3u >= K2WS_G_DW) fail(6);
+                const u32 n = segw_round_nmax(S, rc0);
+                if (n > 32u) fail(3);
+                for (u32 j = 0; j < n && j < 32u; ++j) {
+                    if (p0 + j >= tile_pos) { fail(4); continue; }
+                    if (taken[p0 + j] < 255) taken[p0 + j]++;
+                    per_round[c]++;
+                }
+            }
+        }
+    }
+    u32 n_lost = 0, n_twice = 0;
+    for (u32 p = 0; p < tile_pos; ++p) n_lost += taken[p] == 0, n_twice += taken[p] > 1;
+    if (lost) *lost = n_lost;
+    if (n_twice) fail(2);
+    if (n_lost) fail(1);
+    // a wave that stopped behind round c0 - 1 hands (tile, c0) back; whoever resumes walks rounds c0 .. NR - 1 with the same helpers
+    // (they take the round's number and nothing of the wave's past): the two parts must make up the tile, each offset once
+    for (u32 c0 = 0; c0 <= NR; ++c0) {
+        u64 before = 0, after = 0;
+        for (u32 c = 0; c < NR; ++c) (c < c0 ? before : after) += per_round[c];
+        if (before + after != tile_pos || n_twice || n_lost) fail(7);
+    }
+    return rc;
+}
+
+extern "C" uint32_t fhcore_seg_sub_for(uint32_t k, uint32_t S) { return seg_sub_for(k, S); }
+extern "C" int fhcore_seg_launch_ok(uint32_t k, uint32_t S, uint32_t sub) { return seg_launch_ok(k, S, sub) ? 1 : 0; }
+// out: RO, H, LAST, NR, tile_pos, min stride, max stride of one lane, max record stride (K > 32: rounds of 32, a lane per record)
+extern "C" void fhcore_seg_geom(uint32_t k, uint32_t S, uint32_t sub, uint32_t *out) {
+    if (k <= 32) {
+        const u32 RO = (u32)seg_ro((int)k);
+        const SegGeom g = seg_geom(k, RO, S, seg_shift(sub));
+        out[0] = RO, out[1] = g.H, out[2] = g.LAST, out[3] = g.NR, out[4] = g.tile_pos;
+    } else {
+        const SegGeomW g = segw_geom(S);
+        out[0] = 32u, out[1] = S, out[2] = S, out[3] = g.NR, out[4] = g.tile_pos;
+    }
+    out[5] = SEG_MIN_STRIDE, out[6] = SEG_MAX_STRIDE, out[7] = SEG_MAX_RECORD;
+}

@@ -330,3 +330,164 @@ print("child ok", n_rag)
     r = subprocess.run([sys.executable, "-c", code], env=F.debug_env(seg_ragged="1"), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                        text=True, timeout=900)
     assert r.returncode == 0 and "child ok" in r.stdout, r.stdout[-3000:]
+
+
+# --- the lane splits and rounds of every k, at strides chosen by the host model of the geometry (tests/seg_model.py: the helpers
+# of fh_core.h that the kernels compile; tests/test_seg_geometry_host.py walks all of them without a GPU) ---
+# Inputs are small: a block reaches the segment path from 64 strides' worth of positions on, so four lanes get 8 whole tiles of
+# 16 records and a partial one, two lanes 8 of 32, one lane 4 of 64.
+N_RECORDS = {4: 16 * 8 + 5, 2: 32 * 8 + 5, 1: 64 * 4 + 5}
+
+
+@pytest.fixture(scope="module")
+def model():
+    from seg_model import SegModel
+    return SegModel()
+
+
+@pytest.fixture(scope="module")
+def small_genome():
+    return S.synth_genome_host(3000, 81)
+
+
+def lanes_of(model, stride):
+    """lanes per record of the stride's form (whether or not the k at hand gets that form)"""
+    return 1 if stride <= model.max_stride else 2 if stride <= 2 * model.max_stride else 4
+
+
+def both_kinds(rng, n, L, small_genome, genome):
+    """(a) clean reads of a 3 000-base genome: few distinct k-mers, every count of the sketch large -- one lost or doubled window
+    changes a count; (b) the usual noisy reads of the 300 kb genome"""
+    return (("clean", packed(fixed_reads(rng, n, L, small_genome, p_n=0.0))), ("noisy", packed(fixed_reads(rng, n, L, genome))))
+
+
+def check_right_stride(model, small_genome, genome, k, stride, seed):
+    """reads of stride - 1 bases sketched with that stride, both kinds of stream: the oracle's sketch, and for the clean reads
+    records x (L - k + 1) k-mers in all"""
+    L, n = stride - 1, N_RECORDS[lanes_of(model, stride)]
+    rng = np.random.default_rng(seed)
+    for kind, stream in both_kinds(rng, n, L, small_genome, genome):
+        sk, _ = sketch_on_device(F.SketchParams.mash(1000, 1000, True, k, 0), stream, stride)
+        ctx = "%s k=%d stride=%d" % (kind, k, stride)
+        if model.sub_for(k, stride):
+            assert sk.debug_segments()[0] > 0 and sk.debug_segments()[2] == stride, ctx
+        assert_same(sk, oracle_of(O.MASH, 1000, k, stream), ctx)
+        if kind == "clean":
+            assert sk.finish()[1] == n * (L - k + 1), ctx
+
+
+def strides_for(model, k):
+    """at most 12 strides of the two- and four-lane forms for this k: the forms' ends, strides whose front lanes need a round the
+    last lane does not and the other way round (where there are any), and for every remainder (stride - k) mod lanes a stride
+    that leaves it -- one in the middle of the form's range rather than at its ends as long as twelve allow"""
+    rng = np.random.default_rng(40 + k)
+    forms = ((2, model.max_stride + 1, 2 * model.max_stride), (4, 2 * model.max_stride + 1, model.max_record))
+    out = [model.max_stride + 1, 2 * model.max_stride, 2 * model.max_stride + 1, model.max_record]  # 169, 336, 337, 672
+    cand = {sub: [int(s) for s in rng.permutation(np.arange(lo, hi + 1))] for sub, lo, hi in forms}
+    for sub, lo, hi in forms:
+        rounds = lambda s: [-(-x // model.geom(k, s, sub)[0]) for x in model.geom(k, s, sub)[1:3]]  # ceil(H / RO), ceil(LAST / RO)
+        for want in ((lambda h, l: h > l), (lambda h, l: h < l)):
+            out += [s for s in cand[sub] if want(*rounds(s))][:1]
+    for ends_count in (True, False):
+        for sub, lo, hi in forms:
+            for pad in range(sub):
+                have = [s for s in out if lo <= s <= hi and (s - k) % sub == pad and (ends_count or s not in (lo, hi))]
+                if not have and len(set(out)) < 12:
+                    out.append(next(s for s in cand[sub] if (s - k) % sub == pad and s not in (lo, hi)))
+    out = list(dict.fromkeys(out))
+    assert len(out) <= 12 and all({(s - k) % sub for s in out if lo <= s <= hi} == set(range(sub)) for sub, lo, hi in forms), out
+    return out
+
+
+@pytest.mark.parametrize("k", list(range(1, 33)))
+def test_every_k_on_two_and_four_lanes(model, small_genome, genome, k):
+    for stride in strides_for(model, k):
+        check_right_stride(model, small_genome, genome, k, stride, 9000 + 1000 * k + stride)
+
+
+@pytest.mark.parametrize("L,k", [(401, 1), (337, 1), (338, 2)])
+def test_four_lane_strides_of_k_1_and_2(model, small_genome, genome, L, k):
+    """H = ceil((S - k) / 4) start positions for each of a record's front lanes, LAST = S - 3 H for the last one: S = 402 at k = 1
+    gives 101 and 99, S = 338 at k = 1 85 and 83, S = 339 at k = 2 85 and 84 -- rounds that go by LAST never reach the front
+    lanes' last offsets (tests/test_seg_geometry_host.py), so these k keep to the tile kernel at such strides"""
+    check_right_stride(model, small_genome, genome, k, L + 1, 9500 + L + k)
+
+
+@pytest.mark.parametrize("stride", [337, 338, 339, 402, 671, 672])
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_long_strides_that_are_wrong_change_nothing_at_small_k(model, small_genome, k, stride):
+    """test_long_strides_that_are_wrong_change_nothing, small, at the k where a front lane's share may be longer than the last's"""
+    genome = S.synth_genome_host(60_000, 79)
+    rng = np.random.default_rng(7100 + 10 * stride + k)
+    streams = {
+        "150s clean": packed(fixed_reads(rng, 600, 150, small_genome, p_n=0.0)),
+        "150s": packed(fixed_reads(rng, 600, 150, genome)),
+        "ragged": packed(random_reads(rng, 400, 0, 420, p_n=0.01, genome=genome)),
+        "one": np.concatenate([genome[:50_000], np.zeros(1, np.uint8)]),
+    }
+    for name, stream in streams.items():
+        sk, _ = sketch_on_device(F.SketchParams.mash(1000, 1000, True, k, 0), stream, stride)
+        ctx = "%s k=%d stride=%d" % (name, k, stride)
+        if model.sub_for(k, stride):
+            assert sk.debug_segments()[0] > 0 and sk.debug_segments()[2] == stride, ctx
+        assert_same(sk, oracle_of(O.MASH, 1000, k, stream), ctx)
+        if name == "150s clean":
+            assert sk.finish()[1] == 600 * (150 - k + 1), ctx
+
+
+@pytest.mark.parametrize("stride", [401, 672])
+@pytest.mark.parametrize("k", [2, 21, 31])
+def test_four_lanes_with_stops_inside_a_tile(model, small_genome, genome, k, stride):
+    """a scaled sketch that keeps half of all k-mers on four waves: they run into their insert budget, stop at the end of a round
+    of a four-lane tile and hand (tile, round) back"""
+    L, n = stride - 1, 16 * 24 + 5
+    rng = np.random.default_rng(9700 + stride + k)
+    for kind, stream in both_kinds(rng, n, L, small_genome, genome):
+        sk, _ = sketch_on_device(F.SketchParams.scaled(1000, k, 0.5, 0), stream, stride, max_launch=4096)
+        ctx = "%s scaled 0.5 k=%d stride=%d" % (kind, k, stride)
+        if model.sub_for(k, stride):
+            assert sk.debug_segments()[0] > 0 and sk.debug_segments()[2] == stride, ctx
+        # a wave stops when it has inserted its budget of NEW hashes: the noisy reads of the 300 kb genome hold enough distinct
+        # k-mers for that at k = 21 and 31; the ten canonical 2-mers, and the clean reads' 3 000-base genome, never use a budget
+        # up however many records there are (k = 2 also keeps to the tile kernel at these strides: seg_sub_for)
+        if kind == "noisy" and k >= 21:
+            assert sk.debug_counters()["relaunches"] > 0, ctx
+        assert_same(sk, oracle_of(O.SCALED, 1000, k, stream, 0.5), ctx)
+        if kind == "clean":
+            assert sk.finish()[1] == n * (L - k + 1), ctx
+
+
+@pytest.mark.parametrize("stride", [301, 501])
+@pytest.mark.parametrize("k", [21, 31])
+def test_two_and_four_lanes_over_several_pushes(model, small_genome, genome, k, stride):
+    L, n = stride - 1, 3 * N_RECORDS[lanes_of(model, stride)]
+    rng = np.random.default_rng(9800 + stride + k)
+    for kind, stream in both_kinds(rng, n, L, small_genome, genome):
+        sk, _ = sketch_on_device(F.SketchParams.mash(1000, 1000, True, k, 0), stream, stride, pushes=3)
+        ctx = "%s three pushes k=%d stride=%d" % (kind, k, stride)
+        assert sk.debug_segments()[0] > 0 and sk.debug_segments()[2] == stride, ctx
+        assert_same(sk, oracle_of(O.MASH, 1000, k, stream), ctx)
+        if kind == "clean":
+            assert sk.finish()[1] == n * (L - k + 1), ctx
+
+
+@pytest.mark.parametrize("k", [33, 40, 64])
+def test_two_word_kernel_strides(model, small_genome, genome, k):
+    """fh_k2ws.hip at the strides where its rounds of 32 end (64, 65, 96, 97, 128, 129), its longest (167, 168) and k + 1, which
+    leaves one window per record; Mash, and a scaled sketch on four waves that stop inside tiles"""
+    for stride in sorted({k + 1, 64, 65, 96, 97, 128, 129, 167, 168}):
+        if stride <= k or stride < 40:
+            continue
+        assert model.sub_for(k, stride) == 1
+        L, n = stride - 1, N_RECORDS[1]
+        rng = np.random.default_rng(9900 + 100 * k + stride)
+        for kind, stream in both_kinds(rng, n, L, small_genome, genome):
+            ctx = "%s k=%d stride=%d" % (kind, k, stride)
+            sk, _ = sketch_on_device(F.SketchParams.mash(1000, 1000, True, k, 0), stream, stride)
+            assert sk.debug_segments()[0] > 0 and sk.debug_segments()[2] == stride, ctx
+            assert_same(sk, oracle_of(O.MASH, 1000, k, stream), ctx)
+            if kind == "clean":
+                assert sk.finish()[1] == n * (L - k + 1), ctx
+            sk, _ = sketch_on_device(F.SketchParams.scaled(100, k, 0.5, 0), stream, stride, max_launch=4096)
+            assert sk.debug_segments()[0] > 0 and sk.debug_segments()[2] == stride, "scaled " + ctx
+            assert_same(sk, oracle_of(O.SCALED, 100, k, stream, 0.5), "scaled " + ctx)
