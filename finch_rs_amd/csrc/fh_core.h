@@ -600,13 +600,20 @@ FH_HD u64 seg_good_bits(const u32 *Gd, u32 p0) {
 // are folded into the tables as far as linearity reaches; w = hi(u) + v (mod 2^32) is the only non-linear coupling:
 //   R = 33:  rotl(x,33) = (u << 33) + 2w + (lo(u) >> 31)            =>  kx = U2[A] + w * (2C)
 //            U2[A] = ((u << 33) + (lo(u) >> 31)) * C
+//            With M = 2C:  w * M = w * lo(M) + ((w * hi(M)) << 32)  (mod 2^64), and the cross term is linear mod 2^32:
+//            w * hi(M) = hi(u) * hi(M) + v * hi(M).  Each addend depends on one group, so both come from the tables: the
+//            first is added into the high word of the A record's U2' = U2 + ((hi(u) * hi(M)) << 32), the second is the
+//            B record's second dword X = v * hi(M):
+//                                                                     =>  kx = U2'[A] + w * lo(M) + (X[B] << 32)
+//            one 32 x 32 + 64 multiply-add and one 32-bit add, no second multiply.
 //   R = 31:  rotl(x,31) = (u << 31) + (v << 63) + (w >> 1)          =>  kx = U1[A] + ((v << 31) << 32) + (w >> 1) * C
 //            U1[A] = (u << 31) * C          (C odd: (v << 63) * C = v << 63)
 //   no B  :  kx = F[A] straight from the table (A up to five bases: a lone trailing base is merged into A).
-// That is one 32x32->64 multiply-add, one mul_lo and a few adds per two-group word instead of a rotate (2 alignbit)
-// and a full 64-bit multiply (4 multiplier ops), and nothing at all for the single-group tail word.
+// That is one 32x32->64 multiply-add and two adds per two-group k2 word, two multiply-adds and a few adds per k1 word, instead
+// of a rotate (2 alignbit) and a full 64-bit multiply (4 multiplier ops), and nothing at all for the single-group tail word.
 // Records are laid out for one LDS access per group: A records 16 B {lo(U), hi(U), hi(u), -}, B records 8 B
-// {v, v << 31}, single-group records 8 B {lo(kx), hi(kx)} (an 8-byte LDS read costs what a 4-byte one does).
+// {v << 31, v} (k1) or {v, v * hi(M)} (k2), single-group records 8 B {lo(kx), hi(kx)} (an 8-byte LDS read costs what a
+// 4-byte one does).
 struct alignas(16) Rec4 {
     u32 x, y, z, w;
 };
@@ -721,16 +728,20 @@ FH_HD u64 ascii_group_n(u32 q, int nb) {
 FH_HD u64 rotl64c(u64 x, int r) { return (x << r) | (x >> (64 - r)); }
 
 // table builders (once per workgroup into LDS; on the host for the logic tests)
+// high word of a k2 word's second-stage multiplier M = 2 c1: what the cross term w * hi(M) of w * M is made of
+constexpr u32 K2_MH = (u32)((MURMUR_C1 << 1) >> 32);
 FH_HD Rec4 lut_rec_A(u32 q, bool k2) {
     const u64 u = ascii_group_n(q, 4) * (k2 ? MURMUR_C2 : MURMUR_C1);
-    const u64 U = k2 ? ((u << 33) + (u64)((u32)u >> 31)) * MURMUR_C1 : (u << 31) * MURMUR_C2;
+    // k2: the A group's share hi(u) * hi(M) of the cross term rides in the high word of U
+    const u64 U = k2 ? ((u << 33) + (u64)((u32)u >> 31)) * MURMUR_C1 + ((u64)((u32)(u >> 32) * K2_MH) << 32) : (u << 31) * MURMUR_C2;
     return Rec4{(u32)U, (u32)(U >> 32), (u32)(u >> 32), 0u};
 }
 FH_HD Rec2 lut_rec_B(u32 q, int nb, bool k2) {
     const u32 v = (u32)(ascii_group_n(q, nb) * (k2 ? MURMUR_C2 : MURMUR_C1));
     // k1 words need v << 31 as the addend of a multiply-add (key_word_mix): it comes first, so that the register pair the
-    // record is loaded into is that instruction's accumulator as it stands; k2 words only ever read v
-    return k2 ? Rec2{v, v << 31} : Rec2{v << 31, v};
+    // record is loaded into is that instruction's accumulator as it stands; k2 words read v and the B group's share
+    // v * hi(M) of the cross term
+    return k2 ? Rec2{v, v * K2_MH} : Rec2{v << 31, v};
 }
 // xr: a constant folded in by xor (the key length, which murmur3 xors into h1 / h2 right after the tail words)
 FH_HD Rec2 lut_rec_S(u32 q, int nb, bool k2, u64 xr) {
@@ -866,11 +877,8 @@ FH_HD void murmur_lookup(u64 cm, const LutTables &T, KeyWords<K> &w) { // cm = c
 #endif
             const Rec2 *TB = g.partial ? T.P : (g.is_k2 ? T.B2 : T.B1);
             const Rec2 rb = *(const Rec2 *)((const char *)TB + field_off(cml, cmh, g.shiftB + PRE, g.nbB, 3));
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(FH_NO_B64_KEEP)
-            // likewise an 8-byte read (6.5 cycles per wave under random-index bank conflicts) beats the 4-byte one (9) the
-            // compiler narrows a k2 word's B record to -- only its first dword is used there (tools/ubench_lds.hip)
-            if (g.is_k2) asm volatile("" ::"v"(rb.y));
-#endif
+            // (both dwords of a B record are used by either word kind: the 8-byte read -- 6.5 cycles per wave under random-index
+            // bank conflicts where a 4-byte one costs 9, tools/ubench_lds.hip -- stays one read)
             w.a0[i] = ra.x;
             w.a1[i] = ra.y;
             w.a2[i] = ra.z;
@@ -900,9 +908,9 @@ FH_HD u64 key_word_mix(const KeyWords<K> &w, int i) {
     if (g.kind == 1) return acc;
     const u32 ww = w.a2[i] + w.b0[i];
     if (g.is_k2) {
-        constexpr u64 M = MURMUR_C1 << 1;
-        const u64 t = mad64(ww, (u32)M, acc);
-        return ((u64)((u32)(t >> 32) + ww * (u32)(M >> 32)) << 32) | (u32)t; // only the high word takes the cross term
+        // the cross term ww * hi(M) comes from the tables: the A group's share sits in acc's high word, the B group's is b1
+        const u64 t = mad64(ww, (u32)(MURMUR_C1 << 1), acc);
+        return ((u64)((u32)(t >> 32) + w.b1[i]) << 32) | (u32)t;
     }
     const u32 y = ww >> 1;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1181,11 +1189,10 @@ FH_HD void murmur_lookup_w(const u32 *cm, const LutTables &T, KeyWords<K> &w) { 
             const Rec2 *TB = g.partial ? T.P : (g.is_k2 ? T.B2 : T.B1);
             const Rec2 rb = *(const Rec2 *)((const char *)TB + field_off_w(cm, g.shiftB + PRE, g.nbB, 3));
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(FH_NO_B64_KEEP)
-            // one 16-byte and one 8-byte LDS read per word, as in murmur_lookup: left alone the compiler splits the A record
-            // into an 8- and a 4-byte read (its fourth dword is unused) and narrows a k2 word's B record to 4 bytes -- 13 LDS
-            // instructions per position at K = 33 on a kernel that lives off the LDS pipe (profiles/r03_k33_*)
+            // one 16-byte LDS read per A record, as in murmur_lookup: left alone the compiler splits it into an 8- and a 4-byte
+            // read (its fourth dword is unused) -- 13 LDS instructions per position at K = 33 on a kernel that lives off the
+            // LDS pipe (profiles/r03_k33_*).  (The B record's two dwords are both used.)
             asm volatile("" ::"v"(ra.w));
-            if (g.is_k2) asm volatile("" ::"v"(rb.y));
 #endif
             w.a0[i] = ra.x;
             w.a1[i] = ra.y;
