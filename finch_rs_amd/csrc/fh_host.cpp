@@ -41,6 +41,7 @@
 #include "fh_fqstrip.h"
 #include "fh_pack2.h"
 #include "fh_dist.h"
+#include "fh_matrix.h"
 #include "fh_slot_pipe.h"
 
 namespace fh {
@@ -4962,6 +4963,150 @@ int finch_sketches_select(const finch_sketches *s, const uint32_t *idx, uint32_t
         res->v.push_back(s->v[idx[i]]);
     }
     *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// minmer_matrix (lib/src/distance.rs:345-364): the counts many sketches hold for the hashes of one reference sketch, an
+// S x R matrix of i32.  The device fills whole rows (fh_matrix.hip); this side checks, deals rows and copies.  DESIGN.md §3.9.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint64_t MATRIX_CHUNK_BYTES = 64ull << 20; // cells per result buffer (device and pinned), in bytes
+
+int matrix_check(const Sketch &s, const char *what, size_t idx) {
+    const std::vector<KmerCount> &h = s.hashes;
+    if (h.size() >= UINT32_MAX)
+        return hfail(FH_ERR_INVALID, "%s %zu (%s) has %zu hashes (at most 2^32 - 2)", what, idx, s.name.c_str(), h.size());
+    for (size_t j = 1; j < h.size(); ++j)
+        if (!(h[j - 1].hash < h[j].hash))
+            return hfail(FH_ERR_INVALID, "%s %zu (%s): hashes not strictly ascending at %zu", what, idx, s.name.c_str(), j);
+    return FH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int finch_minmer_matrix(const finch_sketches *refs, uint32_t ir, const finch_sketches *sketches, const int *devices,
+                        uint32_t n_devices, int32_t *out, uint64_t out_len, double *kernel_ms, uint64_t *launches) try {
+    if (kernel_ms) *kernel_ms = 0.;
+    if (launches) *launches = 0;
+    if (!refs || !sketches || (n_devices && !devices) || (out_len && !out)) return hfail(FH_ERR_INVALID, "null argument");
+    if (n_devices > DIST_MAX_ENTRIES) return hfail(FH_ERR_INVALID, "at most %u device entries (got %u)", DIST_MAX_ENTRIES, n_devices);
+    if (ir >= refs->v.size()) return hfail(FH_ERR_INVALID, "reference sketch %u of %zu sketches", ir, refs->v.size());
+    const Sketch &ref = refs->v[ir];
+    const std::vector<Sketch> &Ss = sketches->v;
+    if (int rc = matrix_check(ref, "reference sketch", ir)) return rc;
+    uint64_t longest = 0;
+    for (size_t i = 0; i < Ss.size(); ++i) {
+        if (int rc = matrix_check(Ss[i], "sketch", i)) return rc;
+        longest = std::max<uint64_t>(longest, Ss[i].hashes.size());
+    }
+    const uint64_t S = Ss.size(), R = ref.hashes.size();
+    if (R == 0 && longest) // the reference reads ref_sketch[0] for the first hash of any sketch: a panic
+        return hfail(FH_ERR_INVALID, "reference sketch %u (%s) is empty", ir, ref.name.c_str());
+    if (out_len != S * R) // (S < 2^32 and R < 2^32 - 1: no overflow)
+        return hfail(FH_ERR_INVALID, "out_len %llu, the matrix has %llu x %llu cells", (unsigned long long)out_len,
+                     (unsigned long long)S, (unsigned long long)R);
+    if (S * R == 0) return FH_OK;
+
+    const int ndev = fh_device_count();
+    if (ndev <= 0) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
+    std::vector<int> devs = n_devices ? std::vector<int>(devices, devices + n_devices) : std::vector<int>{0};
+    for (int d : devs)
+        if (d < 0 || d >= ndev) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device: device %d requested, %d visible", d, ndev);
+    struct RestoreDevice { // (this thread runs the first device entry)
+        int prev = fh::matrix_current_device();
+        ~RestoreDevice() { fh::matrix_restore_device(prev); }
+    } restore_device;
+
+    std::vector<uint64_t> ref_hashes(R);
+    for (uint64_t p = 0; p < R; ++p) ref_hashes[p] = ref.hashes[p].hash;
+    const uint64_t budget_rows = std::max<uint64_t>(1, MATRIX_CHUNK_BYTES / (R * sizeof(int32_t)));
+    const uint32_t per_chunk = (uint32_t)std::min<uint64_t>(
+        {std::max<uint64_t>(1, cfg_u64("matrix_chunk_rows", budget_rows)), S, fh::MATRIX_MAX_ROWS});
+    const uint32_t n_chunks = (uint32_t)((S + per_chunk - 1) / per_chunk);
+    uint64_t max_entries = 0;
+    for (uint32_t k = 0; k < n_chunks; ++k) {
+        uint64_t e = 0;
+        for (uint64_t i = (uint64_t)k * per_chunk; i < std::min<uint64_t>(S, (uint64_t)(k + 1) * per_chunk); ++i) e += Ss[i].hashes.size();
+        max_entries = std::max(max_entries, e);
+    }
+    const uint32_t n_entries = (uint32_t)std::min<uint64_t>(devs.size(), n_chunks); // (an entry without a chunk opens nothing)
+    const unsigned T = std::max(1u, DIST_MAX_ENTRIES / n_entries);
+    const uint32_t slice = (uint32_t)std::min<uint64_t>(cfg_u64("matrix_slice", fh::MATRIX_MAX_SLICE), fh::MATRIX_MAX_SLICE);
+
+    std::mutex err_mu;
+    int err_rc = FH_OK;
+    std::string err_msg;
+    std::atomic<bool> failed{false};
+    auto fail_with = [&](int rc, const std::string &msg) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (err_rc == FH_OK) err_rc = rc, err_msg = msg;
+        failed = true;
+    };
+    std::mutex stat_mu;
+    double ms_total = 0.;
+    uint64_t launches_total = 0;
+
+    // one thread per device entry: chunks e, e + n_entries, ...; chunk m + 1's upload and kernel run while chunk m's rows
+    // cross the link and are copied out of the pinned buffer (by T threads where the chunk is large)
+    fork_join(n_entries, [&](unsigned e) {
+        fh::MatrixDevice *md = nullptr;
+        try {
+            if (int rc = fh::matrix_open(devs[e], ref_hashes.data(), (uint32_t)R, per_chunk, max_entries, (uint32_t)longest, slice, &md)) {
+                fail_with(rc, fh_last_error());
+                return;
+            }
+            std::vector<uint32_t> mine;
+            for (uint32_t k = e; k < n_chunks; k += n_entries) mine.push_back(k);
+            auto launch = [&](size_t m) {
+                const uint64_t r0 = (uint64_t)mine[m] * per_chunk, r1 = std::min<uint64_t>(S, r0 + per_chunk);
+                uint64_t entries = 0;
+                for (uint64_t i = r0; i < r1; ++i) entries += Ss[i].hashes.size();
+                uint64_t *off, *hs;
+                uint32_t *cs;
+                if (int rc = fh::matrix_stage(md, (int)(m & 1), (uint32_t)(r1 - r0), entries, &off, &hs, &cs)) return rc;
+                uint64_t at = 0;
+                for (uint64_t i = r0; i < r1; ++i) {
+                    off[i - r0] = at;
+                    for (const KmerCount &h : Ss[i].hashes) hs[at] = h.hash, cs[at] = h.count, ++at;
+                }
+                off[r1 - r0] = at;
+                return fh::matrix_launch(md, (int)(m & 1));
+            };
+            double ms_sum = 0.;
+            int rc = launch(0);
+            for (size_t m = 0; rc == FH_OK && m < mine.size() && !failed; ++m) {
+                if (m + 1 < mine.size() && (rc = launch(m + 1)) != FH_OK) break;
+                const int32_t *cells = nullptr;
+                double ms = 0.;
+                if ((rc = fh::matrix_wait(md, (int)(m & 1), &cells, &ms)) != FH_OK) break;
+                ms_sum += ms;
+                const uint64_t r0 = (uint64_t)mine[m] * per_chunk, r1 = std::min<uint64_t>(S, r0 + per_chunk);
+                const uint64_t n_cells = (r1 - r0) * R;
+                const unsigned t_copy = (unsigned)std::min<uint64_t>(T, std::max<uint64_t>(1, n_cells >> 20)); // a thread per 4 MiB
+                const uint64_t per = (n_cells + t_copy - 1) / t_copy;
+                fork_join(t_copy, [&](unsigned t) {
+                    const uint64_t lo = std::min<uint64_t>(n_cells, t * per), hi = std::min<uint64_t>(n_cells, lo + per);
+                    memcpy(out + r0 * R + lo, cells + lo, (hi - lo) * sizeof(int32_t));
+                });
+            }
+            if (rc != FH_OK) fail_with(rc, fh_last_error());
+            std::lock_guard<std::mutex> g(stat_mu);
+            ms_total += ms_sum;
+            launches_total += mine.size();
+        } catch (const std::bad_alloc &) {
+            fail_with(FH_ERR_CAPACITY, "out of host memory");
+        }
+        fh::matrix_close(md);
+    });
+    if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
+    if (kernel_ms) *kernel_ms = ms_total;
+    if (launches) *launches = launches_total;
     return FH_OK;
 } FINCH_CATCH
 

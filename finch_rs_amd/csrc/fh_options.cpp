@@ -84,6 +84,9 @@ const OptDef DEFS[] = {
     // --- finch_dist ---
     {"dist_slice", "query hashes per LDS slice of the distance kernel, 1..8192 (default 4096; tests: many slices per query)"},
     {"dist_chunk_pairs", "pairs per distance launch (default 4 M; tests: many reference chunks)"},
+    // --- finch_minmer_matrix ---
+    {"matrix_slice", "sketch entries per LDS slice of the count-matrix kernel, 1..4096 (default 4096; tests: many slices per sketch)"},
+    {"matrix_chunk_rows", "rows (sketches) per count-matrix launch, at most 65535 (default: 64 MiB of cells per result buffer; tests: many chunks)"},
 };
 constexpr int N_OPTS = (int)(sizeof(DEFS) / sizeof(DEFS[0]));
 

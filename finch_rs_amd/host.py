@@ -134,6 +134,8 @@ _SYMS["finch_dist_to_json"] = (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64
 _SYMS["finch_dist_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)])
 _SYMS["finch_dist_free"] = (None, [_P])
 _SYMS["finch_sketches_select"] = (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)])
+_SYMS["finch_minmer_matrix"] = (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_int), C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_double),
+                                          C.POINTER(C.c_uint64)])
 _bound = None
 
 
@@ -578,6 +580,32 @@ def select(sketches: Sketches, idx: Sequence[int]) -> Sketches:
     out = _P()
     _check(lib().finch_sketches_select(sketches._p, a.ctypes.data if len(a) else None, len(a), C.byref(out)))
     return Sketches(out, sketches.params)
+
+
+def minmer_matrix(refs: Sketches, ir: int, sketches: Sketches, devices: Sequence[int] = (0,), stats: Optional[dict] = None) -> np.ndarray:
+    """minmer_matrix (distance.rs:345-364) on the GPU: the (len(sketches), hashes of refs[ir]) int32 matrix whose cell (i, p) is
+    the count sketches[i] holds for the reference's p-th hash (a count >= 2^31 wraps negative, as `as i32` does), 0 where it
+    does not have that hash; `stats`, if given, receives the kernels' time and launches"""
+    L = lib()
+    devs = list(devices) if devices else [0]
+    darr = (C.c_int * len(devs))(*devs)
+    out = np.empty((len(sketches), L.finch_sketch_n_hashes(refs._p, ir)), np.int32)
+    ms, nl = C.c_double(), C.c_uint64()
+    _check(L.finch_minmer_matrix(refs._p, ir, sketches._p, darr, len(devs), out.ctypes.data if out.size else None, out.size,
+                                 C.byref(ms), C.byref(nl)))
+    if stats is not None:
+        stats.update(kernel_ms=ms.value, launches=nl.value)
+    return out
+
+
+def counts(sk: Sketches, i: int) -> np.ndarray:
+    """Sketch.counts (python.rs:579-583): the counts of sketch i, each u32 as i32"""
+    L = lib()
+    if not 0 <= i < len(sk):
+        raise FinchError("sketch %d of %d" % (i, len(sk)))
+    cs = np.zeros(L.finch_sketch_n_hashes(sk._p, i), np.uint32)
+    _check(L.finch_sketch_copy(sk._p, i, None, cs.ctypes.data, None, None))
+    return cs.view(np.int32)
 
 
 def dist_queries(names: Sequence[str], pairwise: bool = False, queries=None) -> Optional[List[int]]:

@@ -165,6 +165,20 @@ void finch_dist_free(finch_dist_result *r);
 /* the sketches idx[0..n) of s, in that order (the `--queries` selection of main.rs:97-108) */
 int finch_sketches_select(const finch_sketches *s, const uint32_t *idx, uint32_t n, finch_sketches **out);
 
+/* minmer_matrix (lib/src/distance.rs:345-364; behind Sketch.compare_matrix and Sketch.counts, python.rs:561-583): sketch ir
+ * of `refs` (R hashes) against the S sketches of `sketches`.  out is the row-major S x R matrix: out[i * R + p] = the count
+ * sketch i holds for the reference's p-th hash (the u32's bits as i32: a count >= 2^31 comes out negative), 0 where sketch
+ * i does not have that hash.  Every cell is written.  `refs` and `sketches` may be the same handle.  The lookups run on the
+ * devices: rows dealt in chunks round-robin over `devices` (as finch_dist: NULL/0 = device 0, an entry may repeat, at most
+ * 16 entries); kernel_ms / launches (either may be NULL) receive the kernels' time (HIP events, summed) and the launch
+ * count.  Decided before any device is touched: FH_ERR_INVALID for a null argument (out may be NULL only with out_len 0),
+ * ir out of range, the reference sketch or any sketch of `sketches` not strictly ascending or of 2^32 hashes or more (named
+ * in finch_last_error), an empty reference sketch next to a non-empty sketch (the reference indexes ref[0] and panics),
+ * out_len != S * R; FH_OK without a device for a matrix of zero cells.  Otherwise FH_ERR_NO_DEVICE without a usable device.
+ * The caller's current device is the same after the call. */
+int finch_minmer_matrix(const finch_sketches *refs, uint32_t ir, const finch_sketches *sketches, const int *devices,
+                        uint32_t n_devices, int32_t *out, uint64_t out_len, double *kernel_ms, uint64_t *launches);
+
 /* ---- pieces that need no GPU (unit-testable on the host) ---- */
 /* Build a one-sketch result from arrays (to exercise filtering / serialisation without a device).  FH_ERR_INVALID for
  * records no sketcher can emit: count == 0 or extra_count > count (mash.rs:45-56). */
