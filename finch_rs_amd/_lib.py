@@ -77,6 +77,7 @@ SYMBOLS = {
     "fh_sketch_device_blocks": (C.c_int, [_P, _P, _U64P, _U64P, C.c_uint32]),
     "fh_batch_new": (_P, [C.POINTER(FhParams), C.c_int, C.c_uint32, C.c_uint64]),
     "fh_batch_new_counts": (_P, [C.c_uint32, C.c_int, C.c_uint32, C.c_uint64]),
+    "fh_batch_new_wide": (_P, [C.POINTER(FhParams), C.c_int, C.c_uint32, C.c_uint64]),
     "fh_batch_free": (None, [_P]),
     "fh_batch_stage": (C.c_int, [_P, C.c_int, C.POINTER(_P), _U64P]),
     "fh_batch_submit": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint32]),

@@ -28,6 +28,13 @@
 // 4^k u32 per file, counted by ONE launch of k_ac_batch_count and turned into to_vec's rows by ONE launch of
 // k_ac_batch_epilogue (fh_counts.hip, a workgroup per file), which leaves the tables zeroed.  A count is exact for any input:
 // every file is taken.
+//
+// k = 33..64 (fh_batch_new_wide): the same handle with the two-word sketch kernel (k2_batch_w, fh_k2bw.hip) in k2_batch's
+// place.  Every partition owns the high k-mer words of its table (PART_CAP u64, Ctl::kmer_hi), the epilogue writes them as a
+// column of their own (EpiArgs::wide: 40 bytes per row) and the copy-outs decode a row's k bases from both words.  The rule
+// for "taken" is unchanged; what is new is that the collision log also receives occurrences that are no collision
+// (wide_kmer_update, fh_k2_common.h: one that raced the claimer's high word, and the 64-mers whose low word is all ones), and
+// any record sends the file the long way, where fh_finish resolves it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -91,6 +98,7 @@ struct fh_batch {
     Entry *tables = nullptr;
     uint32_t *live = nullptr, *dead = nullptr, *shard_cnt = nullptr, *shard_buf = nullptr;
     CollRec *clog = nullptr;
+    uint64_t *kmer_hi = nullptr; // k > 32: max_files x PART_CAP high k-mer words (EMPTY64 = not written)
     BatchPartition *d_parts = nullptr;
     uint32_t *ac_tables = nullptr; // counts: max_files tables of 4^k forward counts, zero between batches
     struct Slot {
@@ -136,6 +144,7 @@ void destroy(fh_batch *b) {
     if (b->shard_cnt) (void)hipFree(b->shard_cnt);
     if (b->shard_buf) (void)hipFree(b->shard_buf);
     if (b->clog) (void)hipFree(b->clog);
+    if (b->kmer_hi) (void)hipFree(b->kmer_hi);
     if (b->d_parts) (void)hipFree(b->d_parts);
     if (b->ac_tables) (void)hipFree(b->ac_tables);
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -144,8 +153,10 @@ void destroy(fh_batch *b) {
 
 int build(fh_batch *b) {
     const uint32_t F = b->max_files;
+    const bool wide = b->p.k > 32;
     BHIP_TRY(hipSetDevice(b->device));
     BHIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    if (wide) BHIP_TRY(api_dev_malloc((void **)&b->kmer_hi, (size_t)F * PART_CAP * sizeof(uint64_t)));
     BHIP_TRY(api_dev_malloc((void **)&b->ctls, (size_t)F * sizeof(Ctl)));
     BHIP_TRY(api_dev_malloc((void **)&b->tables, (size_t)F * PART_CAP * sizeof(Entry)));
     BHIP_TRY(api_dev_malloc((void **)&b->live, (size_t)F * PART_LIVE * sizeof(uint32_t)));
@@ -167,15 +178,17 @@ int build(fh_batch *b) {
         q.live_cap = PART_LIVE;
         q.clog_cap = PART_CLOG;
         q.shard_cap = PART_SHARD_CAP;
+        q.kmer_hi = wide ? b->kmer_hi + (size_t)f * PART_CAP : nullptr;
     }
     BHIP_TRY(hipMemcpyAsync(b->d_parts, parts.data(), (size_t)F * sizeof(BatchPartition), hipMemcpyHostToDevice, b->stream));
     const bool scaled = b->p.kind == FH_KIND_SCALED;
     BHIP_TRY(launch_batch_init(b->d_parts, F, b->p.size, scaled ? b->max_hash : EMPTY64, scaled ? b->max_hash : 0ull, 1u, b->stream));
-    // a sketch's columns as fh_finish lays them out: hash | k-mer | first position | count | extra, out_stride entries apart
+    // a sketch's columns as fh_finish lays them out: hash | k-mer | first position | [k > 32: high k-mer word] | count | extra,
+    // out_stride entries apart
     // (a Scaled sketch has up to BATCH_SCALED_MAX rows whatever its size)
     const uint64_t rows = scaled ? BATCH_SCALED_MAX : std::min<uint64_t>(b->p.size + 1, (uint64_t)SMALL_MAX);
     b->out_stride = (uint32_t)(((size_t)rows + 2) & ~(size_t)1);
-    b->out_words = (size_t)b->out_stride * 4; // 3 x 8 + 2 x 4 bytes per entry
+    b->out_words = (size_t)b->out_stride * (wide ? 5 : 4); // (3 or 4) x 8 + 2 x 4 bytes per entry
     b->header_bytes = (((uint64_t)F * sizeof(BatchFile)) + 4095) & ~4095ull;
     for (auto &s : b->slot) {
         BHIP_TRY(api_host_malloc((void **)&s.h_stage, b->header_bytes + b->data_bytes + 64));
@@ -206,7 +219,7 @@ int build(fh_batch *b) {
             e.hist_on = 0;
             e.out = s.h_out + (size_t)f * b->out_words;
             e.out_stride = b->out_stride;
-            e.wide = 0;
+            e.wide = wide ? 1u : 0u;
             e.h_ctl = s.h_ctl + f;
         }
         BHIP_TRY(hipMemcpyAsync(s.d_epi, epi.data(), (size_t)F * sizeof(EpiArgs), hipMemcpyHostToDevice, b->stream));
@@ -276,33 +289,10 @@ static bool device_ok(int device) {
     return true;
 }
 
-extern "C" {
-
-fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
-    if (!params) {
-        api_fail(FH_ERR_INVALID, "null params");
-        return nullptr;
-    }
-    if (params->kind == FH_KIND_ALL_COUNTS) {
-        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher serves Mash sketches only: AllCounts sketches go through an fh_sketcher");
-        return nullptr;
-    }
-    if (params->kind != FH_KIND_MASH && params->kind != FH_KIND_SCALED) {
-        api_fail(FH_ERR_INVALID, "unknown sketch kind %u", params->kind);
-        return nullptr;
-    }
+// what fh_batch_new and fh_batch_new_wide share behind their parameter checks: the sizes, the device, a parked handle of the
+// same parameters (k among them, so neither constructor is handed the other's) or a new one
+static fh_batch *batch_new_checked(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
     const bool scaled = params->kind == FH_KIND_SCALED;
-    if (params->k < 1 || params->k > 32 || params->hash_mask != 0 ||
-        (scaled ? params->size > BATCH_SCALED_MAX : (params->size < 1 || params->size > BATCH_MAX_N))) {
-        api_fail(FH_ERR_UNSUPPORTED,
-                 "the batch sketcher serves Mash sketches of 1..%llu hashes and Scaled sketches of size 0..%llu, k = 1..32, no test mask",
-                 (unsigned long long)BATCH_MAX_N, (unsigned long long)BATCH_SCALED_MAX);
-        return nullptr;
-    }
-    if (scaled && !(params->scale > 0.0 && params->scale <= 1.0)) { // (as fh_new)
-        api_fail(FH_ERR_INVALID, "scale must be in (0, 1]");
-        return nullptr;
-    }
     if (max_files < 1 || max_files > BATCH_MAX_FILES || stage_bytes < 4096 || stage_bytes > (1ull << 36)) {
         api_fail(FH_ERR_INVALID, "max_files 1..%u, stage_bytes 4 KiB..64 GiB", BATCH_MAX_FILES);
         return nullptr;
@@ -341,6 +331,75 @@ fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, 
         return nullptr;
     }
     return b;
+}
+
+extern "C" {
+
+fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
+    if (!params) {
+        api_fail(FH_ERR_INVALID, "null params");
+        return nullptr;
+    }
+    if (params->kind == FH_KIND_ALL_COUNTS) {
+        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher serves Mash sketches only: AllCounts sketches go through an fh_sketcher");
+        return nullptr;
+    }
+    if (params->kind != FH_KIND_MASH && params->kind != FH_KIND_SCALED) {
+        api_fail(FH_ERR_INVALID, "unknown sketch kind %u", params->kind);
+        return nullptr;
+    }
+    const bool scaled = params->kind == FH_KIND_SCALED;
+    if (params->k < 1 || params->k > 32 || params->hash_mask != 0 ||
+        (scaled ? params->size > BATCH_SCALED_MAX : (params->size < 1 || params->size > BATCH_MAX_N))) {
+        api_fail(FH_ERR_UNSUPPORTED,
+                 "the batch sketcher serves Mash sketches of 1..%llu hashes and Scaled sketches of size 0..%llu, k = 1..32, no test mask (k = 33..64: fh_batch_new_wide)",
+                 (unsigned long long)BATCH_MAX_N, (unsigned long long)BATCH_SCALED_MAX);
+        return nullptr;
+    }
+    if (scaled && !(params->scale > 0.0 && params->scale <= 1.0)) { // (as fh_new)
+        api_fail(FH_ERR_INVALID, "scale must be in (0, 1]");
+        return nullptr;
+    }
+    return batch_new_checked(params, device, max_files, stage_bytes);
+}
+
+fh_batch *fh_batch_new_wide(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
+    if (!params) {
+        api_fail(FH_ERR_INVALID, "null params");
+        return nullptr;
+    }
+    if (params->kind == FH_KIND_ALL_COUNTS) {
+        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher for k = 33..64 serves Mash and Scaled sketches: AllCounts (kind 2) batches are fh_batch_new_counts, k = 1..%d",
+                 AC_LDS_MAX_K);
+        return nullptr;
+    }
+    if (params->kind != FH_KIND_MASH && params->kind != FH_KIND_SCALED) {
+        api_fail(FH_ERR_INVALID, "unknown sketch kind %u (0 Mash, 1 Scaled)", params->kind);
+        return nullptr;
+    }
+    if (params->k <= 32) {
+        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_wide serves k = 33..64: k = %u is fh_batch_new's (k = 1..32)", params->k);
+        return nullptr;
+    }
+    if (params->k > (uint32_t)FH_MAX_K) {
+        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_wide serves k = 33..64: k = %u is beyond what the device hashes", params->k);
+        return nullptr;
+    }
+    if (params->hash_mask != 0) {
+        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher takes no test mask (hash_mask must be 0)");
+        return nullptr;
+    }
+    const bool scaled = params->kind == FH_KIND_SCALED;
+    if (scaled ? params->size > BATCH_SCALED_MAX : (params->size < 1 || params->size > BATCH_MAX_N)) {
+        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher serves Mash sketches of 1..%llu hashes and Scaled sketches of size 0..%llu: size %llu",
+                 (unsigned long long)BATCH_MAX_N, (unsigned long long)BATCH_SCALED_MAX, (unsigned long long)params->size);
+        return nullptr;
+    }
+    if (scaled && !(params->scale > 0.0 && params->scale <= 1.0)) { // (as fh_new)
+        api_fail(FH_ERR_INVALID, "scale must be in (0, 1]");
+        return nullptr;
+    }
+    return batch_new_checked(params, device, max_files, stage_bytes);
 }
 
 fh_batch *fh_batch_new_counts(uint32_t k, int device, uint32_t max_files, uint64_t stage_bytes) {
@@ -500,13 +559,14 @@ static int batch_submit(fh_batch *b, int slot, const uint64_t *offsets, const ui
         a.files = reinterpret_cast<const BatchFile *>(s.d_stage);
         a.n_files = n_files;
         a.tiles_total = (uint32_t)tiles;
-        const uint64_t wpb = (uint64_t)k2_waves_per_block((int)b->p.k);
+        const bool wide = b->p.k > 32;
+        const uint64_t wpb = (uint64_t)k2_waves_per_block((int)b->p.k); // (WAVES_PER_BLOCK for k > 32)
         a.tiles_per_wave = (uint32_t)std::max<uint64_t>(1, (tiles + BATCH_MAX_WAVES - 1) / BATCH_MAX_WAVES);
         const uint64_t waves = ((tiles + a.tiles_per_wave - 1) / a.tiles_per_wave + wpb - 1) / wpb * wpb;
         a.seed = b->p.seed;
         a.two_bit = two_bit ? 1u : 0u;
         if (b->profiling) BHIP_TRY(hipEventRecord(s.k0, b->stream));
-        BHIP_TRY(launch_k2b((int)b->p.k, a, (uint32_t)waves, b->stream));
+        BHIP_TRY(wide ? launch_k2bw((int)b->p.k, a, (uint32_t)waves, b->stream) : launch_k2b((int)b->p.k, a, (uint32_t)waves, b->stream));
         if (b->profiling) BHIP_TRY(hipEventRecord(s.k1, b->stream));
     }
     BHIP_TRY(launch_batch_epilogue(s.d_epi, n_files, 1u, b->stream));
@@ -620,6 +680,24 @@ static void counts_rows(const fh_batch *b, int slot, uint32_t i, const uint64_t 
     }
 }
 
+// the columns of one file's rows as the epilogue laid them out (small_epilogue_body, fh_kernels.hip): the high k-mer words sit
+// between the first positions and the counts when k > 32
+struct BatchCols {
+    const uint64_t *hash, *kmer, *pos, *kmer_hi;
+    const uint32_t *count, *extra;
+};
+static BatchCols batch_cols(const fh_batch *b, const uint64_t *cols) {
+    const size_t st = b->out_stride;
+    BatchCols v;
+    v.hash = cols;
+    v.kmer = v.hash + st;
+    v.pos = v.kmer + st;
+    v.kmer_hi = b->p.k > 32 ? v.pos + st : nullptr;
+    v.count = reinterpret_cast<const uint32_t *>((v.kmer_hi ? v.kmer_hi : v.pos) + st);
+    v.extra = v.count + st;
+    return v;
+}
+
 int fh_batch_result(fh_batch *b, int slot, uint32_t i, uint64_t *n_out, uint64_t *total_kmers) {
     const Ctl *c = nullptr;
     const uint64_t *cols = nullptr;
@@ -647,15 +725,14 @@ int fh_batch_copy_out(fh_batch *b, int slot, uint32_t i, uint64_t *hashes, uint3
         counts_rows(b, slot, i, cols, hashes, counts, extra_counts, nullptr, kmers, first_pos);
         return FH_OK;
     }
-    const size_t n = c->n_live, st = b->out_stride;
-    const uint64_t *hh = cols, *kk = hh + st, *pp = kk + st;
-    const uint32_t *cc = reinterpret_cast<const uint32_t *>(pp + st), *ee = cc + st;
-    if (hashes) memcpy(hashes, hh, n * 8);
-    if (counts) memcpy(counts, cc, n * 4);
-    if (extra_counts) memcpy(extra_counts, ee, n * 4);
-    if (first_pos) memcpy(first_pos, pp, n * 8);
+    const size_t n = c->n_live;
+    const BatchCols v = batch_cols(b, cols);
+    if (hashes) memcpy(hashes, v.hash, n * 8);
+    if (counts) memcpy(counts, v.count, n * 4);
+    if (extra_counts) memcpy(extra_counts, v.extra, n * 4);
+    if (first_pos) memcpy(first_pos, v.pos, n * 8);
     if (kmers)
-        for (size_t j = 0; j < n; ++j) api_kmer_ascii(kk[j], 0, (int)b->p.k, kmers + j * b->p.k);
+        for (size_t j = 0; j < n; ++j) api_kmer_ascii(v.kmer[j], v.kmer_hi ? v.kmer_hi[j] : 0, (int)b->p.k, kmers + j * b->p.k);
     return FH_OK;
 }
 
@@ -667,13 +744,12 @@ int fh_batch_copy_out_records(fh_batch *b, int slot, uint32_t i, fh_kmer_count *
         counts_rows(b, slot, i, cols, nullptr, nullptr, nullptr, records, kmers, nullptr);
         return FH_OK;
     }
-    const size_t n = c->n_live, st = b->out_stride;
-    const uint64_t *hh = cols, *kk = hh + st, *pp = kk + st;
-    const uint32_t *cc = reinterpret_cast<const uint32_t *>(pp + st), *ee = cc + st;
+    const size_t n = c->n_live;
+    const BatchCols v = batch_cols(b, cols);
     if (records)
-        for (size_t j = 0; j < n; ++j) records[j] = fh_kmer_count{hh[j], cc[j], ee[j]};
+        for (size_t j = 0; j < n; ++j) records[j] = fh_kmer_count{v.hash[j], v.count[j], v.extra[j]};
     if (kmers)
-        for (size_t j = 0; j < n; ++j) api_kmer_ascii(kk[j], 0, (int)b->p.k, kmers + j * b->p.k);
+        for (size_t j = 0; j < n; ++j) api_kmer_ascii(v.kmer[j], v.kmer_hi ? v.kmer_hi[j] : 0, (int)b->p.k, kmers + j * b->p.k);
     return FH_OK;
 }
 

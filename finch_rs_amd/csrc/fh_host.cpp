@@ -4006,7 +4006,8 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     // a slot of its batch handle and has them sketched by ONE launch, finished by ONE epilogue launch (a workgroup per file),
     // behind one copy and in front of one synchronisation -- while it stages the next group in the other slot.  Applies to
     // what a batch of genomes is: Mash sketches of <= 3000 hashes (after the cut to final_size the small sketcher makes),
-    // k <= 32, no filtering (the default for FASTA, lib.rs:70-76), regular uncompressed files that begin with '>'.
+    // k <= 64 (above 32 through a handle of fh_batch_new_wide), no filtering (the default for FASTA, lib.rs:70-76), regular
+    // uncompressed files that begin with '>'.
     // Anything else, and every file the batch path reports as not taken, goes through sketch_stream as before.
     // Scaled sketches (kind 1) likewise: a file is sketched at max_hash and taken iff it holds between kmers_to_sketch and
     // FH_BATCH_SCALED_MAX distinct hashes at or below it (fh_batch.hip); process_post_filter leaves a Scaled sketch as it is.
@@ -4017,7 +4018,7 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     const uint64_t group_n = group_scaled ? sp->kmers_to_sketch
                                           : ((sp->final_size >= 1 && sp->final_size < sp->kmers_to_sketch) ? sp->final_size : sp->kmers_to_sketch);
     const bool group_ok = batch && (group_counts ? sp->kmer_length <= 7 : group_scaled ? (group_n <= FH_BATCH_SCALED_MAX && sp->scale > 0.0 && sp->scale <= 1.0) : (sp->kind == 0 && group_n >= 1 && group_n <= 3000)) &&
-                          sp->kmer_length >= 1 && sp->kmer_length <= 32 && filters->filter_on <= 0 && file_batch_enabled();
+                          sp->kmer_length >= 1 && sp->kmer_length <= 64 && filters->filter_on <= 0 && file_batch_enabled();
     // A Scaled file whose size says it cannot fit is not staged at all (sending it would cost a wasted pass): if every byte began
     // a distinct k-mer, st_size x max_hash / 2^64 hashes would lie at or below max_hash.  Margin: staged up to 5/4 of the cap --
     // headers, line ends, N and repeated k-mers make the true number smaller than that estimate, never larger, so a file up to a
@@ -4164,7 +4165,8 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
                 fh_params bp = to_fh(*sp, 0);
                 bp.size = group_n;
                 bt = group_counts ? fh_batch_new_counts(sp->kmer_length, handles.device, GROUP_FILES, GROUP_STAGE)
-                                  : fh_batch_new(&bp, handles.device, GROUP_FILES, GROUP_STAGE);
+                                  : sp->kmer_length > 32 ? fh_batch_new_wide(&bp, handles.device, GROUP_FILES, GROUP_STAGE) // (two-word k-mers: fh_k2bw.hip)
+                                                         : fh_batch_new(&bp, handles.device, GROUP_FILES, GROUP_STAGE);
                 if (bt && (fh_batch_stage(bt, 0, &stage[0], &stage_cap) != FH_OK || fh_batch_stage(bt, 1, &stage[1], &stage_cap) != FH_OK)) {
                     fh_batch_free(bt);
                     bt = nullptr;

@@ -49,6 +49,13 @@ hipError_t launch_k2b_part1(int k, const BatchArgs &a, uint32_t n_waves, hipStre
 hipError_t launch_k2b_part2(int k, const BatchArgs &a, uint32_t n_waves, hipStream_t st);
 hipError_t launch_k2b_part3(int k, const BatchArgs &a, uint32_t n_waves, hipStream_t st);
 hipError_t launch_k2b(int k, const BatchArgs &a, uint32_t n_waves, hipStream_t st);
+// fh_k2bw.hip: the batch form for K = 33..64 (any seed), WAVES_PER_BLOCK waves per workgroup; every file's control block points
+// at a kmer_hi array (BatchPartition)
+hipError_t launch_k2bw_part0(int k, const BatchArgs &a, uint32_t n_waves, hipStream_t st);
+hipError_t launch_k2bw_part1(int k, const BatchArgs &a, uint32_t n_waves, hipStream_t st);
+hipError_t launch_k2bw_part2(int k, const BatchArgs &a, uint32_t n_waves, hipStream_t st);
+hipError_t launch_k2bw_part3(int k, const BatchArgs &a, uint32_t n_waves, hipStream_t st);
+hipError_t launch_k2bw(int k, const BatchArgs &a, uint32_t n_waves, hipStream_t st);
 constexpr int FH_MAX_K = 64;
 hipError_t launch_prune_small(Entry *table, uint32_t *live, uint32_t *dead, uint32_t dead_cap, Ctl *ctl, uint32_t kind,
                               uint64_t size, uint64_t max_hash, uint32_t trigger, uint32_t force, uint32_t sort_out,
@@ -98,6 +105,7 @@ struct BatchPartition {
     uint32_t *live, *shard_cnt, *shard_buf;
     CollRec *clog;
     uint32_t cap, live_cap, clog_cap, shard_cap;
+    uint64_t *kmer_hi; // K > 32: `cap` high k-mer words, filled with EMPTY64 by the init (null otherwise)
 };
 // (tau0 / tau_floor: the control block's threshold and its floor -- EMPTY64 / 0 for Mash, max_hash twice for Scaled)
 hipError_t launch_batch_init(const BatchPartition *parts, uint32_t n_files, uint64_t size, uint64_t tau0, uint64_t tau_floor,

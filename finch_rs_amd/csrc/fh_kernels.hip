@@ -70,6 +70,16 @@ hipError_t launch_k2b(int k, const BatchArgs &a, uint32_t n_waves, hipStream_t s
     }
 }
 
+hipError_t launch_k2bw(int k, const BatchArgs &a, uint32_t n_waves, hipStream_t st) {
+    if (k < 33 || k > FH_MAX_K) return hipErrorInvalidValue;
+    switch ((k - 33) / (32 / FH_NPARTS)) {
+    case 0: return launch_k2bw_part0(k, a, n_waves, st);
+    case 1: return launch_k2bw_part1(k, a, n_waves, st);
+    case 2: return launch_k2bw_part2(k, a, n_waves, st);
+    default: return launch_k2bw_part3(k, a, n_waves, st);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K3 (small): single workgroup, bitonic sort of the live hashes in LDS
 // ------------------------------------------------------------------------------------------------
@@ -693,7 +703,11 @@ __global__ __launch_bounds__(1024) void k_batch_epilogue(const EpiArgs *args, u3
     if (fin != FIN_OK_RESET) {
         __syncthreads();
         const u32 cap = ctl->cap;
-        for (u32 i = threadIdx.x; i < cap; i += 1024u) clear_entry(&a.table[i]);
+        u64 *const khi = ctl->kmer_hi; // K > 32: the partition's high k-mer words go back to "not written" with it
+        for (u32 i = threadIdx.x; i < cap; i += 1024u) {
+            clear_entry(&a.table[i]);
+            if (khi) khi[i] = EMPTY64;
+        }
         if (threadIdx.x < (u32)N_SHARDS) ctl->shard_cnt[threadIdx.x * SHARD_STRIDE] = 0;
         __syncthreads();
         init_ctl_dev(ctl, a.tau0, 0u, a.size, (a.flags & EPI_KEEP_ALL) ? a.max_hash : 0ull, a.hist_on);
@@ -711,11 +725,14 @@ hipError_t launch_batch_epilogue(const EpiArgs *args, uint32_t n_files, uint32_t
 
 __global__ __launch_bounds__(1024) void k_batch_init(const BatchPartition *parts, u64 size, u64 tau0, u64 tau_floor, u32 read_first) {
     const BatchPartition p = parts[blockIdx.x];
-    for (u32 i = threadIdx.x; i < p.cap; i += 1024u) clear_entry(&p.table[i]);
+    for (u32 i = threadIdx.x; i < p.cap; i += 1024u) {
+        clear_entry(&p.table[i]);
+        if (p.kmer_hi) p.kmer_hi[i] = EMPTY64;
+    }
     if (threadIdx.x < (u32)N_SHARDS) p.shard_cnt[threadIdx.x * SHARD_STRIDE] = 0;
     if (threadIdx.x == 0) {
         Ctl *ctl = p.ctl;
-        ctl->kmer_hi = nullptr;
+        ctl->kmer_hi = p.kmer_hi; // (init_ctl_dev leaves it alone: every re-initialisation of the epilogue keeps it)
         ctl->table = p.table;
         ctl->live = p.live;
         ctl->clog = p.clog;

@@ -251,7 +251,8 @@ class BatchSketcher:
     """Many sketches per launch (include/finch_hip.h, fh_batch_*): the packed streams of a batch of files sketched by one
     launch, finished by one epilogue launch, one synchronisation -- what a worker of sketch_files (lib.rs:29-49) does with
     the files it has staged.  Mash (1..3000 hashes) or Scaled (kind=KIND_SCALED, size 0..SCALED_MAX_ROWS, scale in (0, 1]: a
-    file is taken iff it holds between `size` and SCALED_MAX_ROWS distinct hashes at or below max_hash), k <= 32.
+    file is taken iff it holds between `size` and SCALED_MAX_ROWS distinct hashes at or below max_hash), k <= 32;
+    `BatchSketcher.wide(...)` makes one for k = 33..64.
     `sketch_many(blocks)` -> per block either (records, kmers, first_pos, total_kmers) or None ("not taken": sketch that
     block through a HipSketcher)."""
 
@@ -278,6 +279,23 @@ class BatchSketcher:
         self.max_files = max_files
         self.kind, self.scale = KIND_ALL_COUNTS, 0.0
         self._h = self._L.fh_batch_new_counts(kmer_length, device, max_files, stage_bytes)
+        if not self._h:
+            raise FinchHipError(-1, (self._L.fh_last_error() or b"").decode(errors="replace"))
+        return self
+
+    @classmethod
+    def wide(cls, size: int, kmer_length: int, seed: int = 0, device: int = 0, max_files: int = 64,
+             stage_bytes: int = 64 << 20, kind: int = KIND_MASH, scale: float = 0.0):
+        """A batch sketcher for two-word k-mers (fh_batch_new_wide, k = 33..64), Mash or Scaled as the constructor takes them:
+        the same stage / submit / pack / wait / result / sketch_many / counters in both input forms.  A block whose k-mers left
+        a record in the collision log (a true collision or not: include/finch_hip.h) is not taken, like any other."""
+        self = cls.__new__(cls)
+        self._L = _lib.load()
+        self.size, self.kmer_length, self.seed, self.device = size, kmer_length, seed, device
+        self.max_files = max_files
+        self.kind, self.scale = kind, scale
+        p = FhParams(kind, kmer_length, size, seed, scale, 0, 0, 0)
+        self._h = self._L.fh_batch_new_wide(C.byref(p), device, max_files, stage_bytes)
         if not self._h:
             raise FinchHipError(-1, (self._L.fh_last_error() or b"").decode(errors="replace"))
         return self

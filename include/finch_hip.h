@@ -80,8 +80,8 @@ const char *fh_last_error(void);
 /* library/ABI version, bumped on any change of this header's functions (5: the batch sketcher with its two-bit input form, fh_set_option; the round-5
  * additions fh_set_record_stride, fh_debug_segments, fh_process_records_in, fh_debug_add_counts, fh_debug_gzip_feed_timeouts;
  * 6: FH_KIND_ALL_COUNTS, the AllCounts sketcher; 7: fh_batch_new_counts; 8: finch_minmer_matrix in finch_host.h and the
- * options matrix_slice, matrix_chunk_rows) */
-#define FH_ABI_VERSION 8
+ * options matrix_slice, matrix_chunk_rows; 9: fh_batch_new_wide, the batch sketcher for k = 33..64) */
+#define FH_ABI_VERSION 9
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---
@@ -327,7 +327,8 @@ int fh_sketch_device_blocks(fh_sketcher *const *handles, const void *const *dev_
  * caller has staged with one copy, one launch of the sketch kernel over the files' tiles (fh_k2b.hip), one launch of the
  * epilogue (a workgroup per file: select, sort, to_vec straight into pinned host memory, state left reset) and one
  * synchronisation.  Mash sketches of 1..3000 hashes and Scaled sketches (size 0..FH_BATCH_SCALED_MAX, scale as fh_new takes
- * it), k = 1..32, any seed; everything else (AllCounts: FH_ERR_UNSUPPORTED here, see fh_batch_new_counts below) -- and every
+ * it), k = 1..32 (k = 33..64: fh_batch_new_wide below), any seed; everything else (AllCounts: FH_ERR_UNSUPPORTED here, see
+ * fh_batch_new_counts below) -- and every
  * file the batch path cannot vouch for -- goes through an fh_sketcher.
  * A Scaled file is sketched at max_hash itself (scaled.rs:22-34) and is taken iff it holds at least `size` and at most
  * FH_BATCH_SCALED_MAX distinct hashes at or below max_hash: then the reference's sketch is exactly those hashes, whatever
@@ -404,6 +405,18 @@ int fh_batch_counters(fh_batch *b, uint64_t *taken, uint64_t *not_taken);
  * rows -- and a failure of the batch as a whole by its return value.  A parked counts handle is handed out again by
  * fh_batch_new_counts only, for the same k, device and sizes; fh_batch_new never sees it. */
 fh_batch *fh_batch_new_counts(uint32_t k, int device, uint32_t max_files, uint64_t stage_bytes);
+/* Batches of files at k = 33..64 (two-word k-mers; fh_k2bw.hip): a handle of the same type, served by every fh_batch_*
+ * function above with the same staging rules, both input forms and the same meaning of "taken".  Mash (size 1..3000) and
+ * Scaled (size 0..FH_BATCH_SCALED_MAX, scale in (0, 1]) as fh_batch_new takes them, no test mask; k <= 32 is refused
+ * (FH_ERR_UNSUPPORTED) with a pointer to fh_batch_new, which in turn keeps refusing k > 32; k > 64, AllCounts and sizes beyond
+ * the limits are FH_ERR_UNSUPPORTED, an unknown kind or a scale outside (0, 1] FH_ERR_INVALID.  The parameter checks come
+ * before the device check.  On top of a partition the handle owns the high k-mer words of its table (256 KiB per file),
+ * and a result row is 40 bytes instead of 32.
+ * One more way for a file to be NOT TAKEN: with two-word k-mers the collision log also receives occurrences that are no
+ * collision -- one that raced the first occurrence's high word, and the 64-mers whose last 32 bases are all T -- and any
+ * record sends the file through an fh_sketcher (which resolves them).  That costs time, never a wrong sketch.
+ * A parked handle is handed out again by fh_batch_new_wide only. */
+fh_batch *fh_batch_new_wide(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes);
 
 /* --- measurement support (bench.py) --- */
 /* when enabled, every sketch-kernel launch is bracketed by HIP events on the handle's stream */

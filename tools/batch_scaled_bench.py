@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""finch_sketch_files with Scaled parameters over a directory of genomes, with and without the batch path; one JSON line.
+"""finch_sketch_files with Scaled (or Mash) parameters over a directory of genomes, with and without the batch path; one JSON line.
 
     python tools/batch_scaled_bench.py [--files 3000] [--distinct 500] [--reps 3] [--threads 0] [--dir DIR] [--only batch|one]
+                                       [--kind scaled|mash] [--k 21]
 
 Input: bench.py's configs[4] generator (synth_fasta_file: log-uniform 1-10 Mb genomes, 70-column lines); `--distinct` files
 are written to a temporary directory and the list of `--files` names cycles over them, so the page cache feeds every pass.
@@ -10,7 +11,11 @@ Sketched with SketchParams.scaled(1000, 21, 0.001): a 1-10 Mb genome has 1000-10
 sketcher of its own: what the library did for Scaled parameters before the batch path served them) and the default -- one
 warm-up pass, then the best of `--reps` passes: files/s, files taken / not taken by the batch path, the sketch kernels'
 time (HIP events: fh_batch_kernel_time / fh_kernel_time, summed over the workers) and the launches behind it.  Both modes'
-sketches are compared row for row.
+sketches are compared row for row.  The timed passes of the two modes alternate (one, batch, one, batch, ...), so that what
+else runs on the machine meanwhile weighs on both alike.
+`--kind mash` sketches with SketchParams.mash(1000, 1000, False, k, 0) instead, `--k` sets kmer_length for either kind (k = 51:
+the groups of two-word k-mers, docs/MEASUREMENTS_batch_wide.md).  With FH_LIB naming an older build of the library, symbols it
+does not have are left unbound: such a build is measured the same way (its `batch` mode is whatever it did for those parameters).
 
 The epilogue's time comes from a trace of its own (never in the timed passes):
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/batch_scaled_bench.py --files 256 --distinct 256 --reps 1 --only batch
@@ -25,6 +30,13 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+if os.environ.get("FH_LIB"):  # an older build of the library: what it does not export cannot be bound, and is not called here
+    import ctypes  # noqa: E402
+
+    from finch_rs_amd import _lib  # noqa: E402
+    _old = ctypes.CDLL(os.environ["FH_LIB"])
+    for _name in [n for n in _lib.SYMBOLS if not hasattr(_old, n)]:
+        _lib.SYMBOLS.pop(_name)
 import finch_rs_amd as F  # noqa: E402
 from finch_rs_amd import host as H  # noqa: E402
 from finch_rs_amd import sketch_schemes as S  # noqa: E402
@@ -40,6 +52,8 @@ def main():
     ap.add_argument("--threads", type=int, default=0, help="workers of finch_sketch_files (0: the library's choice)")
     ap.add_argument("--dir", default=None, help="where the files are written (default: a temporary directory, removed afterwards)")
     ap.add_argument("--only", choices=["batch", "one"], default=None)
+    ap.add_argument("--kind", choices=["scaled", "mash"], default="scaled")
+    ap.add_argument("--k", type=int, default=21, help="kmer_length")
     a = ap.parse_args()
     distinct = min(a.distinct, a.files)
     d = a.dir or tempfile.mkdtemp(prefix="finch_batch_scaled_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
@@ -54,27 +68,33 @@ def main():
             names.append(p)
         paths = [names[i % distinct] for i in range(a.files)]
         nbytes = sum(os.path.getsize(names[i % distinct]) for i in range(a.files))
-        params = S.SketchParams.scaled(1000, 21, 0.001)
-        out = {"files": a.files, "distinct": distinct, "text_gbytes": round(nbytes / 1e9, 3), "params": "scaled(1000, 21, 0.001)"}
+        if a.kind == "mash":
+            params, said = S.SketchParams.mash(1000, 1000, False, a.k, 0), "mash(1000, 1000, False, %d, 0)" % a.k
+        else:
+            params, said = S.SketchParams.scaled(1000, a.k, 0.001), "scaled(1000, %d, 0.001)" % a.k
+        out = {"files": a.files, "distinct": distinct, "text_gbytes": round(nbytes / 1e9, 3), "params": said}
         sketches = {}
-        for mode in ("one", "batch"):
-            if a.only and a.only != mode:
-                continue
+        modes = [m for m in ("one", "batch") if not a.only or a.only == m]
+        for mode in modes:
             F.debug_set(file_batch="0" if mode == "one" else None)
             H.sketch_files(names, params, H.FilterParams(None), n_threads=a.threads)  # warm-up: handles, page cache
-            best = None
-            for rep in range(a.reps):
+        bests, last = {}, {}
+        for rep in range(a.reps):
+            for mode in modes:
+                F.debug_set(file_batch="0" if mode == "one" else None)
                 t0, n0 = H.debug_file_batch()
                 H.debug_kernel_times(1)
                 w0 = time.perf_counter()
-                res = H.sketch_files(paths, params, H.FilterParams(None), n_threads=a.threads)
+                last[mode] = H.sketch_files(paths, params, H.FilterParams(None), n_threads=a.threads)
                 wall = time.perf_counter() - w0
                 ms, launches, positions = H.debug_kernel_times(0)
                 t1, n1 = H.debug_file_batch()
-                if best is None or wall < best[0]:
-                    best = (wall, ms, launches, positions, t1 - t0, n1 - n0)
+                if mode not in bests or wall < bests[mode][0]:
+                    bests[mode] = (wall, ms, launches, positions, t1 - t0, n1 - n0)
                 out.setdefault(mode + "_walls_s", []).append(round(wall, 4))
-            wall, ms, launches, positions, taken, not_taken = best
+        for mode in modes:
+            res = last[mode]
+            wall, ms, launches, positions, taken, not_taken = bests[mode]
             rows = [len(res.sketch(i).arrays[0]) for i in range(distinct)]
             out[mode] = {"files_per_s": round(a.files / wall, 1), "wall_s": round(wall, 4), "text_gbytes_per_s": round(nbytes / wall / 1e9, 2),
                          "taken": taken, "not_taken": not_taken, "sketch_kernel_ms": round(ms, 2), "sketch_kernel_launches": launches,

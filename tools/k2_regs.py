@@ -99,6 +99,9 @@ def pretty(name):
     m = re.match(r"_ZN2fh8k2_batchILi(\d+)ELb(\d)EEE", name)
     if m:
         return "k2_batch<%s,%s>" % (m.group(1), "S0" if m.group(2) == "1" else "--")
+    m = re.match(r"_ZN2fh10k2_batch_wILi(\d+)EEE", name)
+    if m:
+        return "k2_batch_w<%s>" % m.group(1)
     m = re.match(r"_ZN2fh12k2_sketch_wsILi(\d+)EEE", name)
     if m:
         return "k2_sketch_ws<%s>" % m.group(1)
@@ -132,9 +135,9 @@ def main():
         import glob
         objs = sorted(glob.glob(os.path.join(CSRC, "obj", "fh_k2_*.o")) + glob.glob(os.path.join(CSRC, "obj", "fh_k2w_*.o")) +
                       glob.glob(os.path.join(CSRC, "obj", "fh_k2s_*.o")) + glob.glob(os.path.join(CSRC, "obj", "fh_k2ws_*.o")) +
-                      glob.glob(os.path.join(CSRC, "obj", "fh_k2b_*.o")))
-        if len(objs) != 5 * B.NPARTS:
-            sys.exit("expected %d sketch-kernel objects under csrc/obj, found %d: build the library first" % (5 * B.NPARTS, len(objs)))
+                      glob.glob(os.path.join(CSRC, "obj", "fh_k2b_*.o")) + glob.glob(os.path.join(CSRC, "obj", "fh_k2bw_*.o")))
+        if len(objs) != 6 * B.NPARTS:
+            sys.exit("expected %d sketch-kernel objects under csrc/obj, found %d: build the library first" % (6 * B.NPARTS, len(objs)))
         for o in objs:
             rows += unbundle_object(o)
     elif args.k is not None:
