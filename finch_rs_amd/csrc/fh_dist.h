@@ -33,4 +33,19 @@ int dist_launch(DistDevice *d, int buf, uint32_t r0, uint32_t r1);
 int dist_wait(DistDevice *d, int buf, const uint32_t **out, double *kernel_ms);
 void dist_close(DistDevice *d);
 
+// ---- finch_search: the same counts, kept on the device and reduced there ----
+constexpr uint32_t SEARCH_TOP_MAX = 64; // top_n the device selects by rounds; 0 or more: every pair that passes goes to the host
+
+// as dist_open, for search_launch / search_wait (dist_close closes it): per buffer the counts (device only) and what the selection
+// leaves of them -- top mode (1 <= top_n <= SEARCH_TOP_MAX): top_n entries per query; all mode: up to max_pairs entries
+int search_open(int device, const DistSide &queries, const DistSide &refs, uint32_t slice, uint64_t max_pairs, uint32_t top_n,
+                double min_containment, DistDevice **out);
+// async on the handle's stream: the counts of every pair (q, r), r in [r0, r1), r0 < r1, then per query the selection among those
+// with c / j >= min_containment (0 where j = 0), ordered by c / j descending, then r ascending
+int search_launch(DistDevice *d, int buf, uint32_t r0, uint32_t r1);
+// waits for buffer `buf`.  Top mode: *entries = n_queries x top_n slots of 4 u32 (r, c, i, j), the first (*per_query)[q] of query
+// q's slots filled, in order; *n = the slots copied.  All mode: *per_query = nullptr, *entries = *n entries of 5 u32
+// (q, r, c, i, j), every pair that passed, in no order.  Valid until the buffer's next launch.
+int search_wait(DistDevice *d, int buf, const uint32_t **entries, const uint32_t **per_query, uint64_t *n, double *kernel_ms);
+
 } // namespace fh

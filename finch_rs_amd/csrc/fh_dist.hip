@@ -11,10 +11,14 @@
 //     and #{q < M} are one wave-uniform binary search each in the slice;
 //   * a query longer than a slice is walked slice by slice: the slices hold disjoint value ranges, so every count adds.
 // The per-reference sums live in LDS until the last slice; the result is 3 u32 per pair, written with plain stores.
+//
+// The search (finch_search) keeps those counts on the device: a second kernel per chunk, one workgroup per query,
+// selects from them by containment = c / j and only what it selected crosses to the host.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <new>
+#include <vector>
 
 #include "../../include/finch_hip.h"
 #include "fh_dist.h"
@@ -74,7 +78,10 @@ __device__ inline uint32_t wave_sum(uint32_t v) {
     return v;
 }
 
-// grid: x = query, y = block of RB references from a.r0; dynamic LDS: a.slice u64
+// grid: x = query, y = block of RB references from a.r0; dynamic LDS: a.slice u64.  The counts of pair (q, r) go to
+// ((r - r0) * nq + q) * 3, finch_dist's order, or -- QUERY_MAJOR, the search's -- to (q * (r1 - r0) + (r - r0)) * 3: there a query's
+// counts of the chunk are contiguous for k_search_top / k_search_all, and the stores below, which walk r across threads, coalesce.
+template <bool QUERY_MAJOR>
 __global__ void __launch_bounds__(THREADS) k_dist_counts(DistArgs a) {
     extern __shared__ uint64_t s_q[];
     __shared__ uint32_t s_acc[RB][5]; // c, #{q <= max R}, #{q < M}, #{r <= max Q}, #{r < M}
@@ -141,10 +148,97 @@ __global__ void __launch_bounds__(THREADS) k_dist_counts(DistArgs a) {
             i = max(i, acc[2]);
             j = max(j, acc[4]);
         }
-        uint32_t *o = a.out + ((uint64_t)(r - a.r0) * a.nq + q) * 3;
+        uint32_t *o = a.out + (QUERY_MAJOR ? (uint64_t)q * (a.r1 - a.r0) + (r - a.r0) : (uint64_t)(r - a.r0) * a.nq + q) * 3;
         o[0] = acc[0];
         o[1] = i;
         o[2] = j;
+    }
+}
+
+// ---- the search's selection: what of a chunk's counts the host gets to see ----
+struct SearchArgs {
+    const uint32_t *cnt; // the chunk's counts, query-major
+    uint32_t n, r0;      // references of the chunk, the first one's index
+    uint32_t top_n;      // top mode: entries per query
+    double min_c;
+    uint32_t *sel;       // top mode: nq x top_n entries (r, c, i, j); all mode: the chunk's list of entries (q, r, c, i, j)
+    uint32_t *count;     // top mode: nq, the entries each query got; all mode: the list's cursor (zero before the launch)
+};
+
+constexpr uint32_t NONE = 0xffffffffu;
+
+// distance.rs:109-113 on the device.  No fast-math flag in this build: the division is IEEE's, the double finch_distance gets on
+// the host; c <= j, so it is never negative and two of them order as their bit patterns do.
+__device__ inline double containment_of(uint32_t c, uint32_t j) { return j ? (double)c / (double)j : 0.0; }
+
+// is candidate (xb, xt) ahead of (yb, yt) in the search's order: containment descending, then index ascending; NONE loses
+__device__ inline bool ahead(uint64_t xb, uint32_t xt, uint64_t yb, uint32_t yt) {
+    return xt != NONE && (yt == NONE || xb > yb || (xb == yb && xt < yt));
+}
+
+// grid: x = query.  top_n rounds of a workgroup arg-max over the chunk's pairs with containment >= min_c; round k looks only at
+// what comes strictly after round k - 1's winner in that order, so nothing is marked and nothing depends on timing.
+__global__ void __launch_bounds__(THREADS) k_search_top(SearchArgs a) {
+    __shared__ uint64_t s_bits[WAVES];
+    __shared__ uint32_t s_t[WAVES];
+    const uint32_t q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t *cnt = a.cnt + (uint64_t)q * a.n * 3;
+    uint64_t prev_bits = ~0ull; // (above every double's pattern: the first round takes any)
+    uint32_t prev_t = 0, emitted = 0;
+    for (uint32_t k = 0; k < a.top_n; ++k) {
+        uint64_t best_bits = 0;
+        uint32_t best_t = NONE;
+        for (uint32_t t = threadIdx.x; t < a.n; t += THREADS) { // (t ascends: of equal containments the thread keeps its first)
+            const double x = containment_of(cnt[(uint64_t)t * 3], cnt[(uint64_t)t * 3 + 2]);
+            const uint64_t bits = (uint64_t)__double_as_longlong(x);
+            const bool after = bits < prev_bits || (bits == prev_bits && t > prev_t);
+            if (x >= a.min_c && after && (best_t == NONE || bits > best_bits)) best_bits = bits, best_t = t;
+        }
+        for (int o = 32; o; o >>= 1) {
+            const uint64_t ob = __shfl_xor(best_bits, o, 64);
+            const uint32_t ot = __shfl_xor(best_t, o, 64);
+            if (ahead(ob, ot, best_bits, best_t)) best_bits = ob, best_t = ot;
+        }
+        if (lane == 0) s_bits[wave] = best_bits, s_t[wave] = best_t;
+        __syncthreads();
+        best_bits = s_bits[0], best_t = s_t[0];
+        for (uint32_t w = 1; w < WAVES; ++w)
+            if (ahead(s_bits[w], s_t[w], best_bits, best_t)) best_bits = s_bits[w], best_t = s_t[w];
+        __syncthreads(); // (the next round writes s_bits again)
+        if (best_t == NONE) break; // the same in every thread
+        if (threadIdx.x == 0) {
+            const uint32_t *x = cnt + (uint64_t)best_t * 3;
+            *(uint4 *)(a.sel + ((uint64_t)q * a.top_n + k) * 4) = make_uint4(a.r0 + best_t, x[0], x[1], x[2]);
+        }
+        prev_bits = best_bits, prev_t = best_t, ++emitted;
+    }
+    if (threadIdx.x == 0) a.count[q] = emitted;
+}
+
+// grid: x = query.  Every pair of the chunk with containment >= min_c, appended to the chunk's list: a wave takes its places with
+// one atomic (ballot, the lanes' ranks by mbcnt), in no particular order -- the host sorts.
+__global__ void __launch_bounds__(THREADS) k_search_all(SearchArgs a) {
+    const uint32_t q = blockIdx.x;
+    const uint32_t *cnt = a.cnt + (uint64_t)q * a.n * 3;
+    for (uint32_t base = 0; base < a.n; base += THREADS) { // (whole waves go round: the ballot sees every lane)
+        const uint32_t t = base + threadIdx.x;
+        uint32_t c = 0, i = 0, j = 0;
+        bool pass = false;
+        if (t < a.n) {
+            const uint32_t *x = cnt + (uint64_t)t * 3;
+            c = x[0], i = x[1], j = x[2];
+            pass = containment_of(c, j) >= a.min_c;
+        }
+        const uint64_t mask = __ballot(pass);
+        if (!mask) continue;
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        uint32_t first = 0;
+        if (pass && rank == 0) first = atomicAdd(a.count, (uint32_t)__popcll(mask));
+        first = __shfl(first, __ffsll((unsigned long long)mask) - 1, 64);
+        if (pass) {
+            uint32_t *e = a.sel + (uint64_t)(first + rank) * 5;
+            e[0] = q, e[1] = a.r0 + t, e[2] = c, e[3] = i, e[4] = j;
+        }
     }
 }
 
@@ -161,6 +255,13 @@ struct DistDevice {
     uint32_t *out_d[2] = {}, *out_h[2] = {};
     hipEvent_t ev0[2] = {}, ev1[2] = {}, done[2] = {};
     uint32_t launched_pairs[2] = {};
+    // the search only (search_open): what the selection leaves per buffer, and where the host receives it
+    bool search = false, top_mode = false;
+    uint32_t top_n = 0;
+    double min_c = 0.;
+    uint32_t *sel_d[2] = {}, *count_d[2] = {}; // SearchArgs' sel and count
+    uint32_t *sel_h[2] = {}, *count_h[2] = {}; // pinned: the counts (all mode: the cursor); top mode: the entries too
+    std::vector<uint32_t> list_h[2];           // all mode: the entries, as many as the cursor says
 };
 
 static int upload(void **dst, const void *src, size_t bytes) {
@@ -179,6 +280,10 @@ void dist_close(DistDevice *d) {
         for (int b = 0; b < 2; ++b) {
             if (d->out_d[b]) (void)hipFree(d->out_d[b]);
             if (d->out_h[b]) (void)hipHostFree(d->out_h[b]);
+            if (d->sel_d[b]) (void)hipFree(d->sel_d[b]);
+            if (d->count_d[b]) (void)hipFree(d->count_d[b]);
+            if (d->sel_h[b]) (void)hipHostFree(d->sel_h[b]);
+            if (d->count_h[b]) (void)hipHostFree(d->count_h[b]);
             if (d->ev0[b]) (void)hipEventDestroy(d->ev0[b]);
             if (d->ev1[b]) (void)hipEventDestroy(d->ev1[b]);
             if (d->done[b]) (void)hipEventDestroy(d->done[b]);
@@ -205,7 +310,16 @@ static int open_into(DistDevice *d, const DistSide &q, const DistSide &r) {
     for (int b = 0; b < 2; ++b) {
         const size_t bytes = std::max<uint64_t>(d->max_pairs, 1) * 3 * sizeof(uint32_t);
         DHIP_TRY(api_dev_malloc((void **)&d->out_d[b], bytes));
-        DHIP_TRY(api_host_malloc((void **)&d->out_h[b], bytes));
+        if (d->search) { // the counts stay on the device
+            const size_t n_count = d->top_mode ? std::max(d->nq, 1u) : 1;
+            const size_t n_sel = d->top_mode ? (size_t)std::max(d->nq, 1u) * d->top_n * 4 : std::max<uint64_t>(d->max_pairs, 1) * 5;
+            DHIP_TRY(api_dev_malloc((void **)&d->sel_d[b], n_sel * sizeof(uint32_t)));
+            DHIP_TRY(api_dev_malloc((void **)&d->count_d[b], n_count * sizeof(uint32_t)));
+            DHIP_TRY(api_host_malloc((void **)&d->count_h[b], n_count * sizeof(uint32_t)));
+            if (d->top_mode) DHIP_TRY(api_host_malloc((void **)&d->sel_h[b], n_sel * sizeof(uint32_t)));
+        } else {
+            DHIP_TRY(api_host_malloc((void **)&d->out_h[b], bytes));
+        }
         DHIP_TRY(hipEventCreate(&d->ev0[b]));
         DHIP_TRY(hipEventCreate(&d->ev1[b]));
         DHIP_TRY(hipEventCreateWithFlags(&d->done[b], hipEventDisableTiming));
@@ -213,10 +327,15 @@ static int open_into(DistDevice *d, const DistSide &q, const DistSide &r) {
     return FH_OK;
 }
 
-int dist_open(int device, const DistSide &q, const DistSide &r, uint32_t slice, uint64_t max_pairs, DistDevice **out) {
+static int open_device(int device, const DistSide &q, const DistSide &r, uint32_t slice, uint64_t max_pairs, bool search, uint32_t top_n,
+                       double min_containment, DistDevice **out) {
     DistDevice *d = new (std::nothrow) DistDevice;
     if (!d) return api_fail(FH_ERR_CAPACITY, "out of host memory");
     d->device = device;
+    d->search = search;
+    d->top_mode = search && top_n >= 1 && top_n <= SEARCH_TOP_MAX;
+    d->top_n = d->top_mode ? top_n : 0;
+    d->min_c = min_containment;
     d->nq = q.n;
     d->slice = std::min(std::max(slice, 1u), DIST_MAX_SLICE);
     uint64_t longest = 1;
@@ -232,10 +351,16 @@ int dist_open(int device, const DistSide &q, const DistSide &r, uint32_t slice, 
     return FH_OK;
 }
 
-int dist_launch(DistDevice *d, int buf, uint32_t r0, uint32_t r1) {
-    if (r1 < r0 || (uint64_t)(r1 - r0) * d->nq > d->max_pairs || (r1 - r0 + RB - 1) / RB > 65535u)
-        return api_fail(FH_ERR_INVALID, "dist_launch: %u references do not fit the result buffer", r1 - r0);
-    DHIP_TRY(hipSetDevice(d->device));
+int dist_open(int device, const DistSide &q, const DistSide &r, uint32_t slice, uint64_t max_pairs, DistDevice **out) {
+    return open_device(device, q, r, slice, max_pairs, false, 0, 0., out);
+}
+
+int search_open(int device, const DistSide &q, const DistSide &r, uint32_t slice, uint64_t max_pairs, uint32_t top_n, double min_containment,
+                DistDevice **out) {
+    return open_device(device, q, r, slice, max_pairs, true, top_n, min_containment, out);
+}
+
+static DistArgs dist_args(const DistDevice *d, int buf, uint32_t r0, uint32_t r1) {
     DistArgs a;
     a.qh = (const uint64_t *)d->dev[0];
     a.qoff = (const uint64_t *)d->dev[1];
@@ -252,12 +377,21 @@ int dist_launch(DistDevice *d, int buf, uint32_t r0, uint32_t r1) {
     a.r1 = r1;
     a.slice = d->slice;
     a.out = d->out_d[buf];
+    return a;
+}
+
+int dist_launch(DistDevice *d, int buf, uint32_t r0, uint32_t r1) {
+    if (r1 < r0 || (uint64_t)(r1 - r0) * d->nq > d->max_pairs || (r1 - r0 + RB - 1) / RB > 65535u)
+        return api_fail(FH_ERR_INVALID, "dist_launch: %u references do not fit the result buffer", r1 - r0);
+    if (d->search) return api_fail(FH_ERR_STATE, "dist_launch on a search handle");
+    DHIP_TRY(hipSetDevice(d->device));
+    const DistArgs a = dist_args(d, buf, r0, r1);
     const uint64_t pairs = (uint64_t)(r1 - r0) * d->nq;
     d->launched_pairs[buf] = (uint32_t)pairs;
     DHIP_TRY(hipEventRecord(d->ev0[buf], d->stream));
     if (pairs) {
         const dim3 grid(d->nq, (r1 - r0 + RB - 1) / RB);
-        hipLaunchKernelGGL(k_dist_counts, grid, dim3(THREADS), d->lds_slice * sizeof(uint64_t), d->stream, a);
+        hipLaunchKernelGGL(k_dist_counts<false>, grid, dim3(THREADS), d->lds_slice * sizeof(uint64_t), d->stream, a);
         DHIP_TRY(hipGetLastError());
     }
     DHIP_TRY(hipEventRecord(d->ev1[buf], d->stream));
@@ -273,6 +407,63 @@ int dist_wait(DistDevice *d, int buf, const uint32_t **out, double *kernel_ms) {
     DHIP_TRY(hipEventElapsedTime(&ms, d->ev0[buf], d->ev1[buf]));
     *out = d->out_h[buf];
     if (kernel_ms) *kernel_ms = ms;
+    return FH_OK;
+}
+
+int search_launch(DistDevice *d, int buf, uint32_t r0, uint32_t r1) {
+    if (!d->search) return api_fail(FH_ERR_STATE, "search_launch on a handle of dist_open");
+    if (r1 <= r0 || d->nq == 0 || (uint64_t)(r1 - r0) * d->nq > d->max_pairs || (r1 - r0 + RB - 1) / RB > 65535u)
+        return api_fail(FH_ERR_INVALID, "search_launch: %u references do not fit the result buffer", r1 - r0);
+    DHIP_TRY(hipSetDevice(d->device));
+    const DistArgs a = dist_args(d, buf, r0, r1);
+    SearchArgs sa;
+    sa.cnt = d->out_d[buf];
+    sa.n = r1 - r0;
+    sa.r0 = r0;
+    sa.top_n = d->top_n;
+    sa.min_c = d->min_c;
+    sa.sel = d->sel_d[buf];
+    sa.count = d->count_d[buf];
+    d->launched_pairs[buf] = (uint32_t)((uint64_t)(r1 - r0) * d->nq);
+    DHIP_TRY(hipEventRecord(d->ev0[buf], d->stream));
+    if (!d->top_mode) DHIP_TRY(hipMemsetAsync(d->count_d[buf], 0, sizeof(uint32_t), d->stream));
+    hipLaunchKernelGGL(k_dist_counts<true>, dim3(d->nq, (r1 - r0 + RB - 1) / RB), dim3(THREADS), d->lds_slice * sizeof(uint64_t), d->stream, a);
+    DHIP_TRY(hipGetLastError());
+    if (d->top_mode) hipLaunchKernelGGL(k_search_top, dim3(d->nq), dim3(THREADS), 0, d->stream, sa);
+    else hipLaunchKernelGGL(k_search_all, dim3(d->nq), dim3(THREADS), 0, d->stream, sa);
+    DHIP_TRY(hipGetLastError());
+    DHIP_TRY(hipEventRecord(d->ev1[buf], d->stream));
+    if (d->top_mode) {
+        DHIP_TRY(hipMemcpyAsync(d->count_h[buf], d->count_d[buf], d->nq * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+        DHIP_TRY(hipMemcpyAsync(d->sel_h[buf], d->sel_d[buf], (size_t)d->nq * d->top_n * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    } else {
+        DHIP_TRY(hipMemcpyAsync(d->count_h[buf], d->count_d[buf], sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    }
+    DHIP_TRY(hipEventRecord(d->done[buf], d->stream));
+    return FH_OK;
+}
+
+int search_wait(DistDevice *d, int buf, const uint32_t **entries, const uint32_t **per_query, uint64_t *n, double *kernel_ms) {
+    DHIP_TRY(hipSetDevice(d->device));
+    DHIP_TRY(hipEventSynchronize(d->done[buf]));
+    float ms = 0.f;
+    DHIP_TRY(hipEventElapsedTime(&ms, d->ev0[buf], d->ev1[buf]));
+    if (kernel_ms) *kernel_ms = ms;
+    if (d->top_mode) {
+        *entries = d->sel_h[buf];
+        *per_query = d->count_h[buf];
+        *n = (uint64_t)d->nq * d->top_n;
+        return FH_OK;
+    }
+    const uint32_t cursor = d->count_h[buf][0];
+    if (cursor > d->launched_pairs[buf]) return api_fail(FH_ERR_STATE, "search: %u entries from %u pairs", cursor, d->launched_pairs[buf]);
+    std::vector<uint32_t> &list = d->list_h[buf];
+    list.resize((size_t)cursor * 5);
+    // (not on the handle's stream, where the next chunk's kernels may already wait: the entries are complete, `done` says so)
+    if (cursor) DHIP_TRY(hipMemcpy(list.data(), d->sel_d[buf], list.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *entries = list.data();
+    *per_query = nullptr;
+    *n = cursor;
     return FH_OK;
 }
 

@@ -5113,3 +5113,204 @@ int finch_minmer_matrix(const finch_sketches *refs, uint32_t ir, const finch_ske
 } FINCH_CATCH
 
 } // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// search (Multisketch.best_match / filter_to_matches, lib/src/python.rs:202-234): per query the references whose containment
+// is at least a threshold, best first.  The counts are finch_dist's, but they stay on the device, which also selects
+// (fh_dist.hip: k_search_top / k_search_all); only the selected candidates come here, to be merged over the chunks, sorted and
+// turned into rows by distance_from_counts.  DESIGN.md §3.10.
+// ---------------------------------------------------------------------------------------------
+struct finch_search_result {
+    std::vector<uint64_t> offsets; // n_queries + 1
+    std::vector<uint32_t> q, r;
+    std::vector<finch_distance_out> d;
+    double kernel_ms = 0.;
+    uint64_t launches = 0, copied = 0;
+};
+
+namespace {
+
+struct SearchCand {
+    uint32_t q, r, c, i, j;
+};
+
+} // namespace
+
+extern "C" {
+
+int finch_search(const finch_sketches *queries, const finch_sketches *refs, double min_containment, uint32_t top_n, const int *devices,
+                 uint32_t n_devices, finch_search_result **out) try {
+    if (!queries || !refs || !out || (n_devices && !devices)) return hfail(FH_ERR_INVALID, "null argument");
+    if (n_devices > DIST_MAX_ENTRIES) return hfail(FH_ERR_INVALID, "at most %u device entries (got %u)", DIST_MAX_ENTRIES, n_devices);
+    const std::vector<Sketch> &Qs = queries->v, &Rs = refs->v;
+    if (int rc = check_ascending(Qs, "query")) return rc;
+    if (int rc = check_ascending(Rs, "reference")) return rc;
+    const uint32_t nq = (uint32_t)Qs.size(), nr = (uint32_t)Rs.size();
+    auto res = std::make_unique<finch_search_result>();
+    res->offsets.assign((size_t)nq + 1, 0);
+    if (nq == 0 || nr == 0) {
+        *out = res.release();
+        return FH_OK;
+    }
+    const int ndev = fh_device_count();
+    if (ndev <= 0) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
+    std::vector<int> devs = n_devices ? std::vector<int>(devices, devices + n_devices) : std::vector<int>{0};
+    for (int d : devs)
+        if (d < 0 || d >= ndev) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device: device %d requested, %d visible", d, ndev);
+    struct RestoreDevice { // (this thread runs the first device entry)
+        int prev = fh::matrix_current_device();
+        ~RestoreDevice() { fh::matrix_restore_device(prev); }
+    } restore_device;
+
+    DistCsr qc, rc_;
+    qc.build(Qs, false);
+    rc_.build(Rs, false);
+    // (a chunk's list has a u32 cursor: no more than 2^31 pairs per launch, whatever the option says)
+    const uint64_t chunk_pairs = std::min<uint64_t>(std::max<uint64_t>(1, cfg_u64("dist_chunk_pairs", DIST_CHUNK_PAIRS)), 1ull << 31);
+    const uint32_t per_chunk = (uint32_t)std::min<uint64_t>({std::max<uint64_t>(1, chunk_pairs / nq), nr, 65535ull * 64});
+    const uint32_t n_chunks = (nr + per_chunk - 1) / per_chunk;
+    const uint32_t n_entries = (uint32_t)std::min<size_t>(devs.size(), n_chunks); // (an entry without a chunk opens nothing)
+    const uint32_t slice = (uint32_t)cfg_u64("dist_slice", 4096);
+    std::vector<std::vector<SearchCand>> found(n_chunks); // per chunk; top mode: by query, each query's best first
+
+    std::mutex err_mu;
+    int err_rc = FH_OK;
+    std::string err_msg;
+    std::atomic<bool> failed{false};
+    auto fail_with = [&](int rc, const std::string &msg) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (err_rc == FH_OK) err_rc = rc, err_msg = msg;
+        failed = true;
+    };
+    std::mutex stat_mu;
+
+    // one thread per device entry: chunks e, e + n_entries, ...; chunk m + 1's kernels run while chunk m's candidates are taken
+    fork_join(n_entries, [&](unsigned e) {
+        fh::DistDevice *dd = nullptr;
+        try {
+            if (int rc = fh::search_open(devs[e], qc.view(), rc_.view(), slice, (uint64_t)per_chunk * nq, top_n, min_containment, &dd)) {
+                fail_with(rc, fh_last_error());
+                return;
+            }
+            std::vector<uint32_t> mine;
+            for (uint32_t k = e; k < n_chunks; k += n_entries) mine.push_back(k);
+            auto launch = [&](size_t m) {
+                const uint32_t r0 = mine[m] * per_chunk;
+                return fh::search_launch(dd, (int)(m & 1), r0, std::min(nr, r0 + per_chunk));
+            };
+            double ms_sum = 0.;
+            uint64_t copied = 0;
+            int rc = launch(0);
+            for (size_t m = 0; rc == FH_OK && m < mine.size() && !failed; ++m) {
+                if (m + 1 < mine.size() && (rc = launch(m + 1)) != FH_OK) break;
+                const uint32_t *ent = nullptr, *per_query = nullptr;
+                uint64_t n = 0;
+                double ms = 0.;
+                if ((rc = fh::search_wait(dd, (int)(m & 1), &ent, &per_query, &n, &ms)) != FH_OK) break;
+                ms_sum += ms;
+                copied += n;
+                std::vector<SearchCand> &to = found[mine[m]];
+                if (per_query) { // n_queries x top_n slots of (r, c, i, j)
+                    const uint32_t slots = (uint32_t)(n / nq);
+                    for (uint32_t q = 0; q < nq; ++q)
+                        for (uint32_t s = 0; s < std::min(per_query[q], slots); ++s) {
+                            const uint32_t *x = ent + ((size_t)q * slots + s) * 4;
+                            to.push_back(SearchCand{q, x[0], x[1], x[2], x[3]});
+                        }
+                } else {
+                    to.resize(n);
+                    static_assert(sizeof(SearchCand) == 5 * sizeof(uint32_t), "the device's entry");
+                    if (n) memcpy(to.data(), ent, n * sizeof(SearchCand));
+                }
+            }
+            if (rc != FH_OK) fail_with(rc, fh_last_error());
+            std::lock_guard<std::mutex> g(stat_mu);
+            res->kernel_ms += ms_sum;
+            res->launches += mine.size();
+            res->copied += copied;
+        } catch (const std::bad_alloc &) {
+            fail_with(FH_ERR_CAPACITY, "out of host memory");
+        }
+        fh::dist_close(dd);
+    });
+    if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
+
+    // the candidates by query (chunks in reference order), each query's sorted by (containment descending, reference ascending)
+    // and cut to top_n; the doubles are distance_from_counts', as finch_distance has them
+    std::vector<uint64_t> at((size_t)nq + 1, 0);
+    for (const auto &f : found)
+        for (const SearchCand &x : f) {
+            if (x.q >= nq || x.r >= nr) return hfail(FH_ERR_STATE, "search: candidate (%u, %u) of %u x %u", x.q, x.r, nq, nr);
+            ++at[x.q + 1];
+        }
+    for (uint32_t q = 0; q < nq; ++q) at[q + 1] += at[q];
+    struct Row {
+        uint32_t r;
+        finch_distance_out d;
+    };
+    std::vector<Row> rows(at[nq]);
+    {
+        std::vector<uint64_t> fill(at.begin(), at.end() - 1);
+        for (auto &f : found) {
+            for (const SearchCand &x : f) {
+                Row &row = rows[fill[x.q]++];
+                row.r = x.r;
+                distance_from_counts(false, x.c, x.i, x.j, Qs[x.q].sketch_params.kmer_length, true, &row.d);
+            }
+            std::vector<SearchCand>().swap(f);
+        }
+    }
+    const unsigned T = (unsigned)std::min<uint64_t>(DIST_MAX_ENTRIES, std::max<uint64_t>(1, rows.size() >> 16));
+    const uint32_t per = (nq + T - 1) / T;
+    fork_join(T, [&](unsigned t) {
+        for (uint32_t q = std::min(nq, t * per); q < std::min<uint64_t>(nq, (uint64_t)(t + 1) * per); ++q)
+            std::sort(rows.begin() + at[q], rows.begin() + at[q + 1], [](const Row &a, const Row &b) {
+                return a.d.containment > b.d.containment || (a.d.containment == b.d.containment && a.r < b.r);
+            });
+    });
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint64_t have = at[q + 1] - at[q];
+        res->offsets[q + 1] = res->offsets[q] + (top_n ? std::min<uint64_t>(have, top_n) : have);
+    }
+    const uint64_t total = res->offsets[nq];
+    res->q.resize(total);
+    res->r.resize(total);
+    res->d.resize(total);
+    for (uint32_t q = 0; q < nq; ++q)
+        for (uint64_t o = res->offsets[q], s = at[q]; o < res->offsets[q + 1]; ++o, ++s) {
+            res->q[o] = q;
+            res->r[o] = rows[s].r;
+            res->d[o] = rows[s].d;
+        }
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+uint64_t finch_search_len(const finch_search_result *r) { return r ? r->d.size() : 0; }
+
+int finch_search_offsets(const finch_search_result *r, uint64_t *offsets) try {
+    if (!r || !offsets) return hfail(FH_ERR_INVALID, "null argument");
+    memcpy(offsets, r->offsets.data(), r->offsets.size() * sizeof(uint64_t));
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_search_copy(const finch_search_result *r, uint32_t *query_idx, uint32_t *ref_idx, finch_distance_out *rows) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    const size_t n = r->d.size();
+    if (query_idx && n) memcpy(query_idx, r->q.data(), n * sizeof(uint32_t));
+    if (ref_idx && n) memcpy(ref_idx, r->r.data(), n * sizeof(uint32_t));
+    if (rows && n) memcpy(rows, r->d.data(), n * sizeof(finch_distance_out));
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_search_stats(const finch_search_result *r, double *kernel_ms, uint64_t *launches, uint64_t *candidates_copied) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    if (kernel_ms) *kernel_ms = r->kernel_ms;
+    if (launches) *launches = r->launches;
+    if (candidates_copied) *candidates_copied = r->copied;
+    return FH_OK;
+} FINCH_CATCH
+
+void finch_search_free(finch_search_result *r) { delete r; }
+
+} // extern "C"

@@ -136,6 +136,12 @@ _SYMS["finch_dist_free"] = (None, [_P])
 _SYMS["finch_sketches_select"] = (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)])
 _SYMS["finch_minmer_matrix"] = (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_int), C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_double),
                                           C.POINTER(C.c_uint64)])
+_SYMS["finch_search"] = (C.c_int, [_P, _P, C.c_double, C.c_uint32, C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P)])
+_SYMS["finch_search_len"] = (C.c_uint64, [_P])
+_SYMS["finch_search_offsets"] = (C.c_int, [_P, _P])
+_SYMS["finch_search_copy"] = (C.c_int, [_P, _P, _P, _P])
+_SYMS["finch_search_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+_SYMS["finch_search_free"] = (None, [_P])
 _bound = None
 
 
@@ -596,6 +602,53 @@ def minmer_matrix(refs: Sketches, ir: int, sketches: Sketches, devices: Sequence
     if stats is not None:
         stats.update(kernel_ms=ms.value, launches=nl.value)
     return out
+
+
+def search(queries: Sketches, refs: Sketches, min_containment: float = 0.0, top_n: int = 0, devices: Sequence[int] = (0,),
+           stats: Optional[dict] = None):
+    """per query the references with containment >= min_containment, best first (containment descending, then reference index
+    ascending), at most top_n of them if top_n > 0 -> (offsets, rows): the DIST_DTYPE rows grouped by query in query order,
+    query q's being rows[offsets[q]:offsets[q + 1]]; each row is what distance() gives for the pair.  The selection runs on the
+    GPU; `stats`, if given, receives the kernels' time, the launches and the candidates that crossed to the host"""
+    L = lib()
+    devs = list(devices) if devices else [0]
+    darr = (C.c_int * len(devs))(*devs)
+    p = _P()
+    _check(L.finch_search(queries._p, refs._p, float(min_containment), int(top_n), darr, len(devs), C.byref(p)))
+    try:
+        n = L.finch_search_len(p)
+        offsets = np.zeros(len(queries) + 1, np.uint64)
+        _check(L.finch_search_offsets(p, offsets.ctypes.data))
+        qi, ri, d = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, _CDIST_DTYPE)
+        _check(L.finch_search_copy(p, qi.ctypes.data, ri.ctypes.data, d.ctypes.data))
+        if stats is not None:
+            ms, nl, nc = C.c_double(), C.c_uint64(), C.c_uint64()
+            _check(L.finch_search_stats(p, C.byref(ms), C.byref(nl), C.byref(nc)))
+            stats.update(kernel_ms=ms.value, launches=nl.value, candidates_copied=nc.value)
+    finally:
+        L.finch_search_free(p)
+    rows = np.empty(n, DIST_DTYPE)
+    rows["query"], rows["reference"] = qi, ri
+    for f in _CDIST_DTYPE.names:
+        rows[f] = d[f]
+    return offsets, rows
+
+
+def best_match(refs: Sketches, queries: Sketches, iq: int = 0, devices: Sequence[int] = (0,)) -> int:
+    """Multisketch.best_match (python.rs:202-216) of sketch iq of `queries` in the library `refs`: the index of the first
+    reference with the largest containment, 0 if no containment is above 0; FinchError on an empty library (the reference
+    indexes sketches[0] and panics)"""
+    if len(refs) == 0:
+        raise FinchError("best_match: the library has no sketches")
+    _, rows = search(select(queries, [iq]), refs, 0.0, 1, devices)
+    return int(rows["reference"][0])
+
+
+def filter_to_matches(refs: Sketches, queries: Sketches, iq: int, threshold: float, devices: Sequence[int] = (0,)) -> Sketches:
+    """Multisketch.filter_to_matches (python.rs:223-234): the references whose containment of sketch iq of `queries` is
+    >= threshold, in library order, as a collection of their own"""
+    _, rows = search(select(queries, [iq]), refs, threshold, 0, devices)
+    return select(refs, np.sort(rows["reference"]))
 
 
 def counts(sk: Sketches, i: int) -> np.ndarray:

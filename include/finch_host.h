@@ -179,6 +179,37 @@ int finch_sketches_select(const finch_sketches *s, const uint32_t *idx, uint32_t
 int finch_minmer_matrix(const finch_sketches *refs, uint32_t ir, const finch_sketches *sketches, const int *devices,
                         uint32_t n_devices, int32_t *out, uint64_t out_len, double *kernel_ms, uint64_t *launches);
 
+/* search (Multisketch.best_match and filter_to_matches, lib/src/python.rs:202-234: a loop of distance(query, sketch, false)
+ * over a library, judged by containment): for every query the references it looks like, best first.
+ *   Which rows: the rows of query q are the references r whose finch_distance(queries, q, refs, r, 0) containment is
+ *     >= min_containment.  A NaN threshold gives no rows (nothing is >= NaN); any threshold <= 0 keeps every pair.  No pair is
+ *     skipped -- best_match has no self-skip, so a query that is in the library matches itself -- and there is no old_mode.
+ *   Order: by containment descending, among equal containments (equal as doubles) by reference index ascending; only the
+ *     first top_n of a query are returned when top_n > 0, all of them when top_n = 0.  Rows are grouped by query, in query
+ *     order; finch_search_offsets gives the CSR over them (row range of query q: offsets[q] .. offsets[q + 1]).
+ *   Row values: every row is bit for bit what finch_distance returns for that pair, mash_distance included: the host makes the
+ *     doubles from the device's integer counts, as finch_dist does; the device's own doubles only decide the selection.
+ *   Where it runs: the counts are those of finch_dist (reference ranges dealt round-robin over `devices`, NULL/0 = device 0,
+ *     an entry may repeat, at most 16 entries; options dist_slice and dist_chunk_pairs apply), but they stay in device memory:
+ *     per launch the device picks each query's best top_n (1 <= top_n <= 64) or appends every pair that passes the threshold
+ *     to one list (top_n = 0 or > 64), and only those candidates cross to the host, which merges the launches.
+ *   Decided before any device is touched: FH_ERR_INVALID for a null argument, more than 16 device entries, a sketch whose
+ *     hashes are not strictly ascending (named in finch_last_error, as finch_dist names it); a sketch of 2^32 - 1 hashes or
+ *     more is refused as finch_dist refuses it; zero queries or zero references: FH_OK, no rows, no device needed.  Otherwise
+ *     FH_ERR_NO_DEVICE without a usable device.  The caller's current device is the same after the call.
+ * finch_search_stats: the kernels' time (HIP events, summed over the launches of every device entry), the launches, and
+ * candidates_copied = the candidate entries that crossed from device to host, summed over the launches (top_n slots per query
+ * and launch for 1 <= top_n <= 64, else exactly the pairs that passed the threshold); any pointer may be NULL. */
+typedef struct finch_search_result finch_search_result;
+int finch_search(const finch_sketches *queries, const finch_sketches *refs, double min_containment, uint32_t top_n,
+                 const int *devices, uint32_t n_devices, finch_search_result **out);
+uint64_t finch_search_len(const finch_search_result *r);
+int finch_search_offsets(const finch_search_result *r, uint64_t *offsets /* n_queries + 1 */);
+/* row i: query index, reference index, the distance; any pointer may be NULL */
+int finch_search_copy(const finch_search_result *r, uint32_t *query_idx, uint32_t *ref_idx, finch_distance_out *rows);
+int finch_search_stats(const finch_search_result *r, double *kernel_ms, uint64_t *launches, uint64_t *candidates_copied);
+void finch_search_free(finch_search_result *r);
+
 /* ---- pieces that need no GPU (unit-testable on the host) ---- */
 /* Build a one-sketch result from arrays (to exercise filtering / serialisation without a device).  FH_ERR_INVALID for
  * records no sketcher can emit: count == 0 or extra_count > count (mash.rs:45-56). */
