@@ -42,6 +42,7 @@
 #include "fh_pack2.h"
 #include "fh_dist.h"
 #include "fh_matrix.h"
+#include "fh_moments.h"
 #include "fh_slot_pipe.h"
 
 namespace fh {
@@ -5312,5 +5313,269 @@ int finch_search_stats(const finch_search_result *r, double *kernel_ms, uint64_t
 } FINCH_CATCH
 
 void finch_search_free(finch_search_result *r) { delete r; }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// compare_counts (Sketch.compare_counts, lib/src/python.rs:496-559): the merge walk with the summed counts of the shared hashes
+// and the moment recurrence over the query's counts of them.  finch_compare_counts_pair is the reference's loop as written, on
+// the host; finch_compare_counts gets the integers and m2, m3, m4 of many pairs from the device (fh_moments.hip), sorts the
+// records and finishes the three doubles with the function the pair call uses.  DESIGN.md §3.11.
+// ---------------------------------------------------------------------------------------------
+struct finch_compare_counts_result {
+    std::vector<uint32_t> q, r;
+    std::vector<finch_count_moments> rows;
+    double kernel_ms = 0.;
+    uint64_t launches = 0, copied = 0;
+};
+
+namespace {
+
+// The recurrence and the finishing doubles are IEEE arithmetic as written, with no fused multiply-add: baseline x86-64 has
+// none, and where a build targets a machine that has, these two functions still do not contract.
+#if defined(__clang__)
+#define FH_NO_CONTRACT_ATTR
+#define FH_NO_CONTRACT_BODY _Pragma("clang fp contract(off)")
+#elif defined(__GNUC__)
+#define FH_NO_CONTRACT_ATTR __attribute__((optimize("fp-contract=off")))
+#define FH_NO_CONTRACT_BODY
+#else
+#define FH_NO_CONTRACT_ATTR
+#define FH_NO_CONTRACT_BODY
+#endif
+
+// python.rs:545-547
+FH_NO_CONTRACT_ATTR void moments_finish(uint64_t common, double m2, double m3, double m4, finch_count_moments *out) {
+    FH_NO_CONTRACT_BODY
+    const double c = (double)common;
+    out->var = m2 / c;
+    out->skew = std::sqrt(c) * m3 / std::pow(m2, 1.5);
+    out->kurt = c * m4 / (m2 * m2) - 3.;
+}
+
+// python.rs:500-559, statement by statement
+FH_NO_CONTRACT_ATTR void compare_counts_walk(const std::vector<KmerCount> &reference, const std::vector<KmerCount> &query,
+                                             finch_count_moments *out) {
+    FH_NO_CONTRACT_BODY
+    uint64_t common = 0, ref_count = 0, query_count = 0;
+    size_t ref_pos = 0, query_pos = 0;
+    double query_mean = 0., query_m2 = 0., query_m3 = 0., query_m4 = 0.;
+    while (ref_pos < reference.size() && query_pos < query.size()) {
+        if (reference[ref_pos].hash < query[query_pos].hash) {
+            ref_pos += 1;
+        } else if (query[query_pos].hash < reference[ref_pos].hash) {
+            query_pos += 1;
+        } else {
+            ref_count += (uint64_t)reference[ref_pos].count;
+            query_count += (uint64_t)query[query_pos].count;
+            const double n = (double)common + 1.;
+            const double float_count = (double)query[query_pos].count;
+            const double delta = float_count - query_mean;
+            const double delta_n = delta / n;
+            const double delta_n2 = delta_n * delta_n;
+            const double term1 = delta * delta_n * (n - 1.);
+            query_mean += delta_n;
+            query_m4 += term1 * delta_n2 * (n * n - 3. * n + 3.) + 6. * delta_n2 * query_m2 - 4. * delta_n * query_m3;
+            query_m3 += term1 * delta_n * (n - 2.) - 3. * delta_n * query_m2;
+            query_m2 += term1;
+            ref_pos += 1;
+            query_pos += 1;
+            common += 1;
+        }
+    }
+    out->common = common;
+    out->ref_pos = ref_pos;
+    out->query_pos = query_pos;
+    out->ref_count = ref_count;
+    out->query_count = query_count;
+    moments_finish(common, query_m2, query_m3, query_m4, out);
+}
+
+// one side of a call in the device's form (fh_moments.h)
+struct MomentsCsr {
+    std::vector<uint64_t> hashes, offsets;
+    std::vector<uint32_t> counts;
+    void build(const std::vector<Sketch> &v) {
+        offsets.assign(1, 0);
+        size_t total = 0;
+        for (const Sketch &s : v) total += s.hashes.size();
+        hashes.reserve(total);
+        counts.reserve(total);
+        for (const Sketch &s : v) {
+            for (const KmerCount &h : s.hashes) hashes.push_back(h.hash), counts.push_back(h.count);
+            offsets.push_back(hashes.size());
+        }
+    }
+    fh::MomentsSide view() const { return fh::MomentsSide{hashes.data(), counts.data(), offsets.data(), (uint32_t)(offsets.size() - 1)}; }
+};
+
+constexpr uint64_t CMPC_CHUNK_PAIRS = 4u << 20; // pairs per launch: 256 MiB of records per list if every pair passes
+
+} // namespace
+
+extern "C" {
+
+int finch_compare_counts_pair(const finch_sketches *refs, uint32_t ir, const finch_sketches *queries, uint32_t iq,
+                              finch_count_moments *out) try {
+    if (!refs || !queries || !out) return hfail(FH_ERR_INVALID, "null argument");
+    if (ir >= refs->v.size()) return hfail(FH_ERR_INVALID, "reference sketch %u of %zu sketches", ir, refs->v.size());
+    if (iq >= queries->v.size()) return hfail(FH_ERR_INVALID, "query sketch %u of %zu sketches", iq, queries->v.size());
+    compare_counts_walk(refs->v[ir].hashes, queries->v[iq].hashes, out);
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_compare_counts(const finch_sketches *refs, const finch_sketches *queries, uint64_t min_common, const int *devices,
+                         uint32_t n_devices, finch_compare_counts_result **out) try {
+    if (!queries || !refs || !out || (n_devices && !devices)) return hfail(FH_ERR_INVALID, "null argument");
+    if (n_devices > DIST_MAX_ENTRIES) return hfail(FH_ERR_INVALID, "at most %u device entries (got %u)", DIST_MAX_ENTRIES, n_devices);
+    const std::vector<Sketch> &Qs = queries->v, &Rs = refs->v;
+    if (int rc = check_ascending(Qs, "query")) return rc;
+    if (int rc = check_ascending(Rs, "reference")) return rc;
+    const uint32_t nq = (uint32_t)Qs.size(), nr = (uint32_t)Rs.size();
+    auto res = std::make_unique<finch_compare_counts_result>();
+    if (nq == 0 || nr == 0) {
+        *out = res.release();
+        return FH_OK;
+    }
+    const int ndev = fh_device_count();
+    if (ndev <= 0) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
+    std::vector<int> devs = n_devices ? std::vector<int>(devices, devices + n_devices) : std::vector<int>{0};
+    for (int d : devs)
+        if (d < 0 || d >= ndev) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device: device %d requested, %d visible", d, ndev);
+    struct RestoreDevice { // (this thread runs the first device entry)
+        int prev = fh::matrix_current_device();
+        ~RestoreDevice() { fh::matrix_restore_device(prev); }
+    } restore_device;
+
+    MomentsCsr qc, rc_;
+    qc.build(Qs);
+    rc_.build(Rs);
+    // (a chunk's list has a u32 cursor: no more than 2^31 pairs per launch, whatever the option says)
+    const uint64_t chunk_pairs = std::min<uint64_t>(std::max<uint64_t>(1, cfg_u64("cmpc_chunk_pairs", CMPC_CHUNK_PAIRS)), 1ull << 31);
+    const uint32_t per_chunk = (uint32_t)std::min<uint64_t>({std::max<uint64_t>(1, chunk_pairs / nq), nr, 65535ull * 64});
+    if ((uint64_t)per_chunk * nq > (1ull << 31)) // (more than 2^31 queries cannot be: nq < 2^32 and per_chunk = 1 here)
+        return hfail(FH_ERR_UNSUPPORTED, "%u queries: more than 2^31 pairs per reference", nq);
+    const uint32_t n_chunks = (nr + per_chunk - 1) / per_chunk;
+    const uint32_t n_entries = (uint32_t)std::min<size_t>(devs.size(), n_chunks); // (an entry without a chunk opens nothing)
+    const uint32_t slice = (uint32_t)std::min<uint64_t>(cfg_u64("cmpc_slice", fh::MOMENTS_MAX_SLICE), fh::MOMENTS_MAX_SLICE);
+    // a sketch has fewer than 2^32 - 1 hashes, so no pair reaches a threshold above that
+    const uint32_t min_c = (uint32_t)std::min<uint64_t>(min_common, UINT32_MAX);
+    std::vector<std::vector<fh::MomentsRecord>> found(n_chunks);
+
+    std::mutex err_mu;
+    int err_rc = FH_OK;
+    std::string err_msg;
+    std::atomic<bool> failed{false};
+    auto fail_with = [&](int rc, const std::string &msg) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (err_rc == FH_OK) err_rc = rc, err_msg = msg;
+        failed = true;
+    };
+    std::mutex stat_mu;
+
+    // one thread per device entry: chunks e, e + n_entries, ...; chunk m + 1's kernel runs while chunk m's records are taken
+    fork_join(n_entries, [&](unsigned e) {
+        fh::MomentsDevice *md = nullptr;
+        try {
+            if (int rc = fh::moments_open(devs[e], qc.view(), rc_.view(), slice, (uint64_t)per_chunk * nq, min_c, &md)) {
+                fail_with(rc, fh_last_error());
+                return;
+            }
+            std::vector<uint32_t> mine;
+            for (uint32_t k = e; k < n_chunks; k += n_entries) mine.push_back(k);
+            auto launch = [&](size_t m) {
+                const uint32_t r0 = mine[m] * per_chunk;
+                return fh::moments_launch(md, (int)(m & 1), r0, std::min(nr, r0 + per_chunk));
+            };
+            double ms_sum = 0.;
+            uint64_t copied = 0;
+            int rc = launch(0);
+            for (size_t m = 0; rc == FH_OK && m < mine.size() && !failed; ++m) {
+                if (m + 1 < mine.size() && (rc = launch(m + 1)) != FH_OK) break;
+                const fh::MomentsRecord *recs = nullptr;
+                uint64_t n = 0;
+                double ms = 0.;
+                if ((rc = fh::moments_wait(md, (int)(m & 1), &recs, &n, &ms)) != FH_OK) break;
+                ms_sum += ms;
+                copied += n;
+                found[mine[m]].assign(recs, recs + n);
+            }
+            if (rc != FH_OK) fail_with(rc, fh_last_error());
+            std::lock_guard<std::mutex> g(stat_mu);
+            res->kernel_ms += ms_sum;
+            res->launches += mine.size();
+            res->copied += copied;
+        } catch (const std::bad_alloc &) {
+            fail_with(FH_ERR_CAPACITY, "out of host memory");
+        }
+        fh::moments_close(md);
+    });
+    if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
+
+    // the device's lists have no order: the records by query (a counting pass), each query's by reference index
+    std::vector<uint64_t> at((size_t)nq + 1, 0);
+    for (uint32_t k = 0; k < n_chunks; ++k) {
+        const uint32_t r0 = k * per_chunk, r1 = std::min(nr, r0 + per_chunk);
+        for (const fh::MomentsRecord &x : found[k]) {
+            if (x.q >= nq || x.r < r0 || x.r >= r1) return hfail(FH_ERR_STATE, "compare_counts: record (%u, %u) in chunk %u of %u x %u", x.q, x.r, k, nq, nr);
+            ++at[x.q + 1];
+        }
+    }
+    for (uint32_t q = 0; q < nq; ++q) at[q + 1] += at[q];
+    const uint64_t total = at[nq];
+    std::vector<fh::MomentsRecord> recs(total);
+    {
+        std::vector<uint64_t> fill(at.begin(), at.end() - 1);
+        for (auto &f : found) {
+            for (const fh::MomentsRecord &x : f) recs[fill[x.q]++] = x;
+            std::vector<fh::MomentsRecord>().swap(f);
+        }
+    }
+    res->q.resize(total);
+    res->r.resize(total);
+    res->rows.resize(total);
+    const unsigned T = (unsigned)std::min<uint64_t>(DIST_MAX_ENTRIES, std::max<uint64_t>(1, total >> 16));
+    const uint32_t per = (nq + T - 1) / T;
+    fork_join(T, [&](unsigned t) {
+        for (uint32_t q = std::min(nq, t * per); q < std::min<uint64_t>(nq, (uint64_t)(t + 1) * per); ++q) {
+            std::sort(recs.begin() + at[q], recs.begin() + at[q + 1], [](const fh::MomentsRecord &a, const fh::MomentsRecord &b) { return a.r < b.r; });
+            for (uint64_t o = at[q]; o < at[q + 1]; ++o) {
+                const fh::MomentsRecord &x = recs[o];
+                finch_count_moments &row = res->rows[o];
+                res->q[o] = x.q;
+                res->r[o] = x.r;
+                row.common = x.common;
+                row.ref_pos = x.ref_pos;
+                row.query_pos = x.query_pos;
+                row.ref_count = x.ref_count;
+                row.query_count = x.query_count;
+                moments_finish(x.common, x.m2, x.m3, x.m4, &row);
+            }
+        }
+    });
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+uint64_t finch_compare_counts_len(const finch_compare_counts_result *r) { return r ? r->rows.size() : 0; }
+
+int finch_compare_counts_copy(const finch_compare_counts_result *r, uint32_t *ref_idx, uint32_t *query_idx, finch_count_moments *rows) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    const size_t n = r->rows.size();
+    if (ref_idx && n) memcpy(ref_idx, r->r.data(), n * sizeof(uint32_t));
+    if (query_idx && n) memcpy(query_idx, r->q.data(), n * sizeof(uint32_t));
+    if (rows && n) memcpy(rows, r->rows.data(), n * sizeof(finch_count_moments));
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_compare_counts_stats(const finch_compare_counts_result *r, double *kernel_ms, uint64_t *launches, uint64_t *records_copied) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    if (kernel_ms) *kernel_ms = r->kernel_ms;
+    if (launches) *launches = r->launches;
+    if (records_copied) *records_copied = r->copied;
+    return FH_OK;
+} FINCH_CATCH
+
+void finch_compare_counts_free(finch_compare_counts_result *r) { delete r; }
 
 } // extern "C"

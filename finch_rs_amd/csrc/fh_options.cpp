@@ -87,6 +87,9 @@ const OptDef DEFS[] = {
     // --- finch_minmer_matrix ---
     {"matrix_slice", "sketch entries per LDS slice of the count-matrix kernel, 1..4096 (default 4096; tests: many slices per sketch)"},
     {"matrix_chunk_rows", "rows (sketches) per count-matrix launch, at most 65535 (default: 64 MiB of cells per result buffer; tests: many chunks)"},
+    // --- finch_compare_counts ---
+    {"cmpc_slice", "query entries per LDS slice of the compare-counts kernel, 1..4096 (default 4096; tests: many slices per query)"},
+    {"cmpc_chunk_pairs", "pairs per compare-counts launch, at most 2^31 (default 4 M; tests: many reference chunks)"},
 };
 constexpr int N_OPTS = (int)(sizeof(DEFS) / sizeof(DEFS[0]));
 

@@ -142,6 +142,19 @@ _SYMS["finch_search_offsets"] = (C.c_int, [_P, _P])
 _SYMS["finch_search_copy"] = (C.c_int, [_P, _P, _P, _P])
 _SYMS["finch_search_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _SYMS["finch_search_free"] = (None, [_P])
+
+
+class CCountMoments(C.Structure):
+    _fields_ = [("common", C.c_uint64), ("ref_pos", C.c_uint64), ("query_pos", C.c_uint64), ("ref_count", C.c_uint64),
+                ("query_count", C.c_uint64), ("var", C.c_double), ("skew", C.c_double), ("kurt", C.c_double)]
+
+
+_SYMS["finch_compare_counts_pair"] = (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(CCountMoments)])
+_SYMS["finch_compare_counts"] = (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P)])
+_SYMS["finch_compare_counts_len"] = (C.c_uint64, [_P])
+_SYMS["finch_compare_counts_copy"] = (C.c_int, [_P, _P, _P, _P])
+_SYMS["finch_compare_counts_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+_SYMS["finch_compare_counts_free"] = (None, [_P])
 _bound = None
 
 
@@ -649,6 +662,47 @@ def filter_to_matches(refs: Sketches, queries: Sketches, iq: int, threshold: flo
     >= threshold, in library order, as a collection of their own"""
     _, rows = search(select(queries, [iq]), refs, threshold, 0, devices)
     return select(refs, np.sort(rows["reference"]))
+
+
+# one row of finch_compare_counts: the indices of the pair, then finch_count_moments' fields
+_CMOMENTS_DTYPE = np.dtype([("common", np.uint64), ("ref_pos", np.uint64), ("query_pos", np.uint64), ("ref_count", np.uint64),
+                            ("query_count", np.uint64), ("var", np.float64), ("skew", np.float64), ("kurt", np.float64)])
+COUNTS_DTYPE = np.dtype([("query", np.uint32), ("reference", np.uint32)] + _CMOMENTS_DTYPE.descr)
+
+
+def compare_counts_pair(refs: Sketches, ir: int, queries: Sketches, iq: int):
+    """Sketch.compare_counts (python.rs:496-559) of one pair on the host, the reference's loop as written ->
+    (common, ref_pos, query_pos, ref_count, query_count, var, skew, kurt)"""
+    m = CCountMoments()
+    _check(lib().finch_compare_counts_pair(refs._p, ir, queries._p, iq, C.byref(m)))
+    return (m.common, m.ref_pos, m.query_pos, m.ref_count, m.query_count, m.var, m.skew, m.kurt)
+
+
+def compare_counts(refs: Sketches, queries: Sketches, min_common: int = 0, devices: Sequence[int] = (0,),
+                   stats: Optional[dict] = None) -> np.ndarray:
+    """Sketch.compare_counts for every (query, reference) pair with common >= min_common, on the GPU: COUNTS_DTYPE rows ordered by
+    query, then by reference index; each row's values are what compare_counts_pair gives for the pair.  `stats`, if given,
+    receives the kernels' time, the launches and the records that crossed to the host"""
+    L = lib()
+    devs = list(devices) if devices else [0]
+    darr = (C.c_int * len(devs))(*devs)
+    p = _P()
+    _check(L.finch_compare_counts(refs._p, queries._p, int(min_common), darr, len(devs), C.byref(p)))
+    try:
+        n = L.finch_compare_counts_len(p)
+        qi, ri, m = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, _CMOMENTS_DTYPE)
+        _check(L.finch_compare_counts_copy(p, ri.ctypes.data, qi.ctypes.data, m.ctypes.data))
+        if stats is not None:
+            ms, nl, nc = C.c_double(), C.c_uint64(), C.c_uint64()
+            _check(L.finch_compare_counts_stats(p, C.byref(ms), C.byref(nl), C.byref(nc)))
+            stats.update(kernel_ms=ms.value, launches=nl.value, records_copied=nc.value)
+    finally:
+        L.finch_compare_counts_free(p)
+    rows = np.empty(n, COUNTS_DTYPE)
+    rows["query"], rows["reference"] = qi, ri
+    for f in _CMOMENTS_DTYPE.names:
+        rows[f] = m[f]
+    return rows
 
 
 def counts(sk: Sketches, i: int) -> np.ndarray:

@@ -81,8 +81,10 @@ const char *fh_last_error(void);
  * additions fh_set_record_stride, fh_debug_segments, fh_process_records_in, fh_debug_add_counts, fh_debug_gzip_feed_timeouts;
  * 6: FH_KIND_ALL_COUNTS, the AllCounts sketcher; 7: fh_batch_new_counts; 8: finch_minmer_matrix in finch_host.h and the
  * options matrix_slice, matrix_chunk_rows; 9: fh_batch_new_wide, the batch sketcher for k = 33..64;
- * 10: fh_batch_new_wide and the rest of 9 unchanged, plus finch_search and its accessors in finch_host.h) */
-#define FH_ABI_VERSION 10
+ * 10: fh_batch_new_wide and the rest of 9 unchanged, plus finch_search and its accessors in finch_host.h;
+ * 11: fh_batch_new_wide and the rest of 10 unchanged, plus finch_compare_counts, finch_compare_counts_pair and their accessors in
+ * finch_host.h and the options cmpc_slice, cmpc_chunk_pairs) */
+#define FH_ABI_VERSION 11
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---

@@ -210,6 +210,44 @@ int finch_search_copy(const finch_search_result *r, uint32_t *query_idx, uint32_
 int finch_search_stats(const finch_search_result *r, double *kernel_ms, uint64_t *launches, uint64_t *candidates_copied);
 void finch_search_free(finch_search_result *r);
 
+/* compare_counts (Sketch.compare_counts, lib/src/python.rs:496-559): the merge walk of a reference sketch and a query sketch
+ * that also sums the abundances of the shared hashes and runs the one-pass recurrence for the higher moments of the query's
+ * abundances over them.  The eight values are the reference's tuple, in its order:
+ *   common = |Q n R|; ref_pos / query_pos = where the walk stopped on each side (#{r <= max Q}, #{q <= max R}; both 0 if either
+ *   sketch is empty); ref_count / query_count = the summed `count` of the shared hashes on each side (u64); var = m2 / common,
+ *   skew = sqrt(common) * m3 / pow(m2, 1.5), kurt = common * m4 / (m2 * m2) - 3, where m2, m3, m4 come from the recurrence of
+ *   python.rs:524-535 run over the shared hashes in ascending hash order, in IEEE doubles without fused multiply-adds.
+ *   common = 0, common = 1 or all shared counts equal give NaNs, as the reference does: that is the contract, not an error.
+ * finch_compare_counts_pair: one pair on the host, the reference's loop as written (any input the reference's loop takes).
+ * FH_ERR_INVALID for a null argument or an index out of range.
+ * finch_compare_counts: every (query, reference) pair with common >= min_common (0 keeps every pair), on the devices: one row
+ *   per pair, ordered by query index, then by reference index ascending; every value of a row is bit for bit what
+ *   finch_compare_counts_pair returns for that pair (two NaNs count as equal).  The integers and m2, m3, m4 are made on the device
+ *   -- the recurrence included, in hash order --, the three finishing doubles on the host, by the function the pair call uses.
+ *   Reference ranges are dealt round-robin over `devices` (as finch_dist: NULL/0 = device 0, an entry may repeat, at most 16
+ *   entries; options cmpc_slice and cmpc_chunk_pairs apply); per launch only the pairs that pass cross to the host.
+ *   Decided before any device is touched: FH_ERR_INVALID for a null argument, more than 16 device entries, a sketch whose hashes
+ *   are not strictly ascending (named in finch_last_error, as finch_dist names it); a sketch of 2^32 - 1 hashes or more is refused
+ *   as finch_dist refuses it; zero queries or zero references: FH_OK, no rows, no device needed.  Otherwise FH_ERR_NO_DEVICE
+ *   without a usable device.  The caller's current device is the same after the call.
+ * finch_compare_counts_stats: the kernels' time (HIP events, summed over the launches of every device entry), the launches, and
+ * records_copied = the records that crossed from device to host, summed over the launches: exactly the pairs that passed; any
+ * pointer may be NULL. */
+typedef struct finch_count_moments {
+    uint64_t common, ref_pos, query_pos, ref_count, query_count;
+    double var, skew, kurt;
+} finch_count_moments;
+int finch_compare_counts_pair(const finch_sketches *refs, uint32_t ir, const finch_sketches *queries, uint32_t iq,
+                              finch_count_moments *out);
+typedef struct finch_compare_counts_result finch_compare_counts_result;
+int finch_compare_counts(const finch_sketches *refs, const finch_sketches *queries, uint64_t min_common, const int *devices,
+                         uint32_t n_devices, finch_compare_counts_result **out);
+uint64_t finch_compare_counts_len(const finch_compare_counts_result *r);
+/* row i: reference index, query index, the eight values; any pointer may be NULL */
+int finch_compare_counts_copy(const finch_compare_counts_result *r, uint32_t *ref_idx, uint32_t *query_idx, finch_count_moments *rows);
+int finch_compare_counts_stats(const finch_compare_counts_result *r, double *kernel_ms, uint64_t *launches, uint64_t *records_copied);
+void finch_compare_counts_free(finch_compare_counts_result *r);
+
 /* ---- pieces that need no GPU (unit-testable on the host) ---- */
 /* Build a one-sketch result from arrays (to exercise filtering / serialisation without a device).  FH_ERR_INVALID for
  * records no sketcher can emit: count == 0 or extra_count > count (mash.rs:45-56). */
