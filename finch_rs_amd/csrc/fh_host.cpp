@@ -43,6 +43,7 @@
 #include "fh_dist.h"
 #include "fh_matrix.h"
 #include "fh_moments.h"
+#include "fh_merge_lib.h"
 #include "fh_slot_pipe.h"
 
 namespace fh {
@@ -5577,5 +5578,337 @@ int finch_compare_counts_stats(const finch_compare_counts_result *r, double *ker
 } FINCH_CATCH
 
 void finch_compare_counts_free(finch_compare_counts_result *r) { delete r; }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// merge (Sketch.merge: merge_sketches, lib/src/python.rs:24-100): the walk over two sketches that stops when either runs out,
+// one record per hash with the counts of a shared hash added (u32, wrapping: a release build of the reference), clipped by
+// (size, the first sketch's scale).  finch_merge_pair is the reference's loop as written, on the host; finch_merge_groups folds
+// ordered groups of sketches on the device (fh_merge_lib.hip), one workgroup per group, and takes the k-mer text of every
+// result record from the host's own sketches by the record's provenance.  DESIGN.md §3.12.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// SketchParams::check_compatibility (mod.rs:185-212) of a pair: "" or the reference's words for the first difference
+std::string merge_incompatible(const finch_sketch_params &a, const finch_sketch_params &b) {
+    auto hash_type = [](const finch_sketch_params &p) { return p.kind == 2 ? "None" : "MurmurHash3_x64_128"; };
+    auto hash_bits = [](const finch_sketch_params &p) { return p.kind == 2 ? 0u : 64u; };
+    auto hash_seed = [](const finch_sketch_params &p) { return p.kind == 2 ? 0ull : (unsigned long long)p.hash_seed; };
+    char buf[256];
+    buf[0] = 0;
+    if (a.kmer_length != b.kmer_length)
+        snprintf(buf, sizeof buf, "First sketch has k %u, but second sketch has k %u", a.kmer_length, b.kmer_length);
+    else if (strcmp(hash_type(a), hash_type(b)) != 0)
+        snprintf(buf, sizeof buf, "First sketch has hash type %s, but second sketch has hash type %s", hash_type(a), hash_type(b));
+    else if (hash_bits(a) != hash_bits(b))
+        snprintf(buf, sizeof buf, "First sketch has hash bits %u, but second sketch has hash bits %u", hash_bits(a), hash_bits(b));
+    else if (hash_seed(a) != hash_seed(b))
+        snprintf(buf, sizeof buf, "First sketch has hash seed %llu, but second sketch has hash seed %llu", hash_seed(a), hash_seed(b));
+    return buf;
+}
+
+// the clip's share of the first sketch: hash_info().3 and max_hash = u64::MAX / ((1. / sc) as u64) (python.rs:70-83)
+struct MergeClip {
+    bool has_scale = false;
+    uint64_t max_hash = 0;
+};
+
+// false: the divisor (1. / sc) as u64 is 0 -- a scale above 1, below 0 or NaN --, where the reference panics
+bool merge_clip_of(const finch_sketch_params &p, MergeClip *c) {
+    c->has_scale = p.kind == 1;
+    c->max_hash = 0;
+    if (!c->has_scale) return true;
+    if (!(1. / p.scale >= 1.)) return false;
+    c->max_hash = fh::api_scaled_max_hash(p.scale); // (the same expression wherever the divisor is not 0)
+    return true;
+}
+
+// python.rs:44-98, statement by statement; `out` is neither input
+void merge_walk(const std::vector<KmerCount> &sketch1, const std::vector<KmerCount> &sketch2, const uint64_t *size, const MergeClip &clip,
+                std::vector<KmerCount> &out) {
+    out.clear();
+    out.reserve(sketch1.size() + sketch2.size());
+    size_t i = 0, j = 0;
+    while (i < sketch1.size() && j < sketch2.size()) {
+        if (sketch1[i].hash < sketch2[j].hash) {
+            out.push_back(sketch1[i]);
+            i += 1;
+        } else if (sketch2[j].hash < sketch1[i].hash) {
+            out.push_back(sketch2[j]);
+            j += 1;
+        } else {
+            out.push_back(KmerCount{sketch1[i].hash, sketch1[i].kmer, (uint32_t)(sketch1[i].count + sketch2[j].count),
+                                    (uint32_t)(sketch1[i].extra_count + sketch2[j].extra_count), sketch1[i].label});
+            i += 1;
+            j += 1;
+        }
+    }
+    size_t keep = out.size();
+    if (size && clip.has_scale) {
+        for (keep = 0; keep < out.size() && (out[keep].hash <= clip.max_hash || keep < *size); ++keep) {}
+    } else if (clip.has_scale) {
+        for (keep = 0; keep < out.size() && out[keep].hash <= clip.max_hash; ++keep) {}
+    } else if (size) {
+        keep = (size_t)std::min<uint64_t>(*size, out.size());
+    }
+    out.resize(keep);
+}
+
+// a named member as the device reads it: strictly ascending, fewer than 2^32 - 1 hashes
+int merge_check_member(const Sketch &sk, uint32_t idx, uint32_t g, uint64_t m) {
+    const std::vector<KmerCount> &h = sk.hashes;
+    if (h.size() >= UINT32_MAX)
+        return hfail(FH_ERR_INVALID, "group %u member %llu: merge sketch %u (%s) has %zu hashes (at most 2^32 - 2)", g, (unsigned long long)m, idx,
+                     sk.name.c_str(), h.size());
+    for (size_t j = 1; j < h.size(); ++j)
+        if (!(h[j - 1].hash < h[j].hash))
+            return hfail(FH_ERR_INVALID, "group %u member %llu: merge sketch %u (%s): hashes not strictly ascending at %zu", g,
+                         (unsigned long long)m, idx, sk.name.c_str(), j);
+    return FH_OK;
+}
+
+double merge_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+constexpr uint64_t MERGE_CHUNK_RECORDS = 4u << 20; // records per launch: 96 MiB for each of a buffer set's three lists
+constexpr uint32_t MERGE_MAX_LAUNCH_GROUPS = 1u << 20;
+
+} // namespace
+
+extern "C" {
+
+int finch_merge_pair(const finch_sketches *a, uint32_t ia, const finch_sketches *b, uint32_t ib, const uint64_t *size,
+                     finch_sketches **out) try {
+    if (!a || !b || !out) return hfail(FH_ERR_INVALID, "null argument");
+    if (ia >= a->v.size()) return hfail(FH_ERR_INVALID, "first sketch %u of %zu sketches", ia, a->v.size());
+    if (ib >= b->v.size()) return hfail(FH_ERR_INVALID, "second sketch %u of %zu sketches", ib, b->v.size());
+    const Sketch &sketch = a->v[ia], &other = b->v[ib];
+    const std::string bad = merge_incompatible(sketch.sketch_params, other.sketch_params);
+    if (!bad.empty()) return hfail(FH_ERR_INVALID, "%s", bad.c_str());
+    MergeClip clip;
+    if (!merge_clip_of(sketch.sketch_params, &clip))
+        return hfail(FH_ERR_INVALID, "first sketch %u (%s) has scale %g: 1 / scale as an integer is 0", ia, sketch.name.c_str(), sketch.sketch_params.scale);
+    auto res = std::make_unique<finch_sketches>();
+    res->v.resize(1);
+    Sketch &o = res->v[0];
+    o.name = sketch.name;
+    o.comment = sketch.comment;
+    o.sketch_params = sketch.sketch_params;
+    o.filter_params = sketch.filter_params;
+    o.seq_length = sketch.seq_length + other.seq_length; // (u64: wraps)
+    o.num_valid_kmers = sketch.num_valid_kmers + other.num_valid_kmers;
+    merge_walk(sketch.hashes, other.hashes, size, clip, o.hashes);
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_merge_groups(const finch_sketches *s, const uint64_t *offsets, const uint32_t *members, uint32_t n_groups, const uint64_t *size,
+                       const int *devices, uint32_t n_devices, finch_sketches **out, double *kernel_ms, uint64_t *launches,
+                       uint64_t *records_copied, double *phase_ms) try {
+    if (kernel_ms) *kernel_ms = 0.;
+    if (launches) *launches = 0;
+    if (records_copied) *records_copied = 0;
+    if (phase_ms) phase_ms[0] = phase_ms[1] = phase_ms[2] = 0.;
+    if (!s || !offsets || !out || (n_groups && !members) || (n_devices && !devices)) return hfail(FH_ERR_INVALID, "null argument");
+    if (n_devices > DIST_MAX_ENTRIES) return hfail(FH_ERR_INVALID, "at most %u device entries (got %u)", DIST_MAX_ENTRIES, n_devices);
+    const std::vector<Sketch> &S = s->v;
+    auto res = std::make_unique<finch_sketches>();
+    if (n_groups == 0) {
+        *out = res.release();
+        return FH_OK;
+    }
+
+    // everything that is decided without a device
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        if (offsets[g + 1] < offsets[g]) return hfail(FH_ERR_INVALID, "group %u: the offsets do not ascend (%llu after %llu)", g,
+                                                      (unsigned long long)offsets[g + 1], (unsigned long long)offsets[g]);
+        if (offsets[g + 1] == offsets[g]) return hfail(FH_ERR_INVALID, "group %u is empty", g);
+    }
+    std::vector<uint8_t> checked(S.size(), 0);
+    std::vector<MergeClip> clips(n_groups);
+    std::vector<uint64_t> total(n_groups, 0);
+    std::vector<uint32_t> multi; // the groups of two members or more
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        const uint32_t *mem = members + offsets[g];
+        const uint64_t nm = offsets[g + 1] - offsets[g];
+        for (uint64_t m = 0; m < nm; ++m) {
+            if (mem[m] >= S.size()) return hfail(FH_ERR_INVALID, "group %u member %llu: sketch %u of %zu sketches", g, (unsigned long long)m, mem[m], S.size());
+            if (m > 0) {
+                const std::string bad = merge_incompatible(S[mem[0]].sketch_params, S[mem[m]].sketch_params);
+                if (!bad.empty()) return hfail(FH_ERR_INVALID, "group %u member %llu: %s", g, (unsigned long long)m, bad.c_str());
+            }
+            if (!checked[mem[m]]) {
+                if (int rc = merge_check_member(S[mem[m]], mem[m], g, m)) return rc;
+                checked[mem[m]] = 1;
+            }
+            total[g] += S[mem[m]].hashes.size();
+            if (total[g] > UINT32_MAX) return hfail(FH_ERR_INVALID, "group %u: its members have 2^32 records or more together", g);
+        }
+        if (nm >= 2) {
+            if (nm > UINT32_MAX) return hfail(FH_ERR_INVALID, "group %u has %llu members (at most 2^32 - 1)", g, (unsigned long long)nm);
+            if (!merge_clip_of(S[mem[0]].sketch_params, &clips[g]))
+                return hfail(FH_ERR_INVALID, "group %u member 0: sketch %u (%s) has scale %g: 1 / scale as an integer is 0", g, mem[0],
+                             S[mem[0]].name.c_str(), S[mem[0]].sketch_params.scale);
+            multi.push_back(g);
+        }
+    }
+
+    // what does not need the walk: the first member's name, comment and parameters, the wrapping u64 sums; a group of one member
+    // is that member
+    res->v.resize(n_groups);
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        const uint32_t *mem = members + offsets[g];
+        const Sketch &first = S[mem[0]];
+        Sketch &o = res->v[g];
+        o.name = first.name;
+        o.comment = first.comment;
+        o.sketch_params = first.sketch_params;
+        o.filter_params = first.filter_params;
+        for (uint64_t m = 0; m < offsets[g + 1] - offsets[g]; ++m) o.seq_length += S[mem[m]].seq_length, o.num_valid_kmers += S[mem[m]].num_valid_kmers;
+        if (offsets[g + 1] - offsets[g] == 1) o.hashes = first.hashes;
+    }
+    if (multi.empty()) {
+        *out = res.release();
+        return FH_OK;
+    }
+
+    const int ndev = fh_device_count();
+    if (ndev <= 0) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
+    std::vector<int> devs = n_devices ? std::vector<int>(devices, devices + n_devices) : std::vector<int>{0};
+    for (int d : devs)
+        if (d < 0 || d >= ndev) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device: device %d requested, %d visible", d, ndev);
+    struct RestoreDevice { // (this thread runs the first device entry)
+        int prev = fh::matrix_current_device();
+        ~RestoreDevice() { fh::matrix_restore_device(prev); }
+    } restore_device;
+
+    const uint64_t budget = std::min<uint64_t>(std::max<uint64_t>(1, cfg_u64("merge_chunk_records", MERGE_CHUNK_RECORDS)), 1ull << 31);
+    const uint32_t tile = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, cfg_u64("merge_tile", 1024)), fh::MERGE_LIB_MAX_TILE);
+    const uint32_t n_entries = (uint32_t)std::min<size_t>(devs.size(), multi.size()); // (an entry without a group opens nothing)
+
+    std::mutex err_mu;
+    int err_rc = FH_OK;
+    std::string err_msg;
+    std::atomic<bool> failed{false};
+    auto fail_with = [&](int rc, const std::string &msg) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (err_rc == FH_OK) err_rc = rc, err_msg = msg;
+        failed = true;
+    };
+    std::mutex stat_mu;
+    double st_kernel = 0., st_upload = 0., st_copy = 0., st_gather = 0.;
+    uint64_t st_launches = 0, st_copied = 0;
+
+    // one thread per device entry: the groups multi[e], multi[e + n_entries], ... in launches of at most `budget` records;
+    // launch m + 1's kernel runs while launch m's records are copied back and given their k-mer text
+    fork_join(n_entries, [&](unsigned e) {
+        fh::MergeLibDevice *md = nullptr;
+        try {
+            // the sketches this entry's groups name, once each
+            std::vector<uint32_t> slot_of(S.size(), UINT32_MAX);
+            std::vector<uint64_t> in_h, in_off(1, 0);
+            std::vector<uint32_t> in_c, in_e;
+            struct Launch {
+                std::vector<fh::MergeLibGroup> groups;
+                std::vector<uint32_t> members, gids;
+                uint64_t records = 0;
+            };
+            std::vector<Launch> L;
+            for (size_t k = e; k < multi.size(); k += n_entries) {
+                const uint32_t g = multi[k];
+                const uint32_t *mem = members + offsets[g];
+                const uint32_t nm = (uint32_t)(offsets[g + 1] - offsets[g]);
+                // a bound on the accumulator after every step that needs no merging: the members' lengths together; with a size
+                // and no scale every step ends truncated to the size
+                uint64_t cap = total[g];
+                if (size && !clips[g].has_scale) cap = std::min<uint64_t>(cap, std::max<uint64_t>(S[mem[0]].hashes.size(), *size));
+                if (L.empty() || L.back().records + cap > budget || L.back().groups.size() >= MERGE_MAX_LAUNCH_GROUPS ||
+                    L.back().members.size() + nm > UINT32_MAX)
+                    L.emplace_back();
+                Launch &l = L.back();
+                l.groups.push_back(fh::MergeLibGroup{l.records, clips[g].max_hash, (uint32_t)l.members.size(), nm, (uint32_t)cap, clips[g].has_scale ? 1u : 0u});
+                l.gids.push_back(g);
+                l.records += cap;
+                for (uint32_t m = 0; m < nm; ++m) {
+                    if (slot_of[mem[m]] == UINT32_MAX) {
+                        slot_of[mem[m]] = (uint32_t)(in_off.size() - 1);
+                        for (const KmerCount &h : S[mem[m]].hashes) in_h.push_back(h.hash), in_c.push_back(h.count), in_e.push_back(h.extra_count);
+                        in_off.push_back(in_h.size());
+                    }
+                    l.members.push_back(slot_of[mem[m]]);
+                }
+            }
+            uint32_t max_groups = 1;
+            uint64_t max_members = 2, max_records = 1;
+            for (const Launch &l : L) {
+                max_groups = std::max<uint32_t>(max_groups, (uint32_t)l.groups.size());
+                max_members = std::max<uint64_t>(max_members, l.members.size());
+                max_records = std::max(max_records, l.records);
+            }
+            double upload_ms = 0.;
+            const fh::MergeLibInput in{in_h.data(), in_c.data(), in_e.data(), in_off.data(), (uint32_t)(in_off.size() - 1)};
+            if (int rc = fh::merge_lib_open(devs[e], in, max_groups, max_members, max_records, tile, size, &md, &upload_ms)) {
+                fail_with(rc, fh_last_error());
+                return;
+            }
+            auto launch = [&](size_t m) {
+                return fh::merge_lib_launch(md, (int)(m & 1), L[m].groups.data(), (uint32_t)L[m].groups.size(), L[m].members.data(), L[m].members.size());
+            };
+            double ms_sum = 0., copy_sum = 0., gather_sum = 0.;
+            uint64_t copied = 0;
+            int rc = launch(0);
+            for (size_t m = 0; rc == FH_OK && m < L.size() && !failed; ++m) {
+                if (m + 1 < L.size() && (rc = launch(m + 1)) != FH_OK) break;
+                const fh::MergeLibOut *outs = nullptr;
+                const fh::MergeLibRecord *recs = nullptr;
+                uint64_t n = 0;
+                double ms = 0., copy_ms = 0.;
+                if ((rc = fh::merge_lib_wait(md, (int)(m & 1), &outs, &recs, &n, &ms, &copy_ms)) != FH_OK) break;
+                ms_sum += ms;
+                copy_sum += copy_ms;
+                copied += n;
+                // the k-mer text (and label) of every record from the member and position it came from
+                const double t0 = merge_now_ms();
+                for (size_t k = 0; k < L[m].gids.size(); ++k) {
+                    const uint32_t g = L[m].gids[k];
+                    const uint32_t *mem = members + offsets[g];
+                    const uint64_t nm = offsets[g + 1] - offsets[g];
+                    std::vector<KmerCount> &h = res->v[g].hashes;
+                    h.resize(outs[k].len);
+                    const fh::MergeLibRecord *r = recs + outs[k].place;
+                    for (uint32_t x = 0; x < outs[k].len; ++x) {
+                        if (r[x].slot >= nm || r[x].pos >= S[mem[r[x].slot]].hashes.size() || S[mem[r[x].slot]].hashes[r[x].pos].hash != r[x].hash) {
+                            fail_with(FH_ERR_STATE, "merge: record " + std::to_string(x) + " of group " + std::to_string(g) + " names no entry with its hash");
+                            rc = FH_ERR_STATE;
+                            break;
+                        }
+                        const KmerCount &src = S[mem[r[x].slot]].hashes[r[x].pos];
+                        h[x] = KmerCount{r[x].hash, src.kmer, r[x].count, r[x].extra, src.label};
+                    }
+                    if (rc != FH_OK) break;
+                }
+                gather_sum += merge_now_ms() - t0;
+            }
+            if (rc != FH_OK && !failed) fail_with(rc, fh_last_error());
+            std::lock_guard<std::mutex> g(stat_mu);
+            st_kernel += ms_sum;
+            st_upload += upload_ms;
+            st_copy += copy_sum;
+            st_gather += gather_sum;
+            st_launches += L.size();
+            st_copied += copied;
+        } catch (const std::bad_alloc &) {
+            fail_with(FH_ERR_CAPACITY, "out of host memory");
+        }
+        fh::merge_lib_close(md);
+    });
+    if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
+    if (kernel_ms) *kernel_ms = st_kernel;
+    if (launches) *launches = st_launches;
+    if (records_copied) *records_copied = st_copied;
+    if (phase_ms) phase_ms[0] = st_upload, phase_ms[1] = st_copy, phase_ms[2] = st_gather;
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
 
 } // extern "C"

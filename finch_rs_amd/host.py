@@ -155,6 +155,9 @@ _SYMS["finch_compare_counts_len"] = (C.c_uint64, [_P])
 _SYMS["finch_compare_counts_copy"] = (C.c_int, [_P, _P, _P, _P])
 _SYMS["finch_compare_counts_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _SYMS["finch_compare_counts_free"] = (None, [_P])
+_SYMS["finch_merge_pair"] = (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(_P)])
+_SYMS["finch_merge_groups"] = (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)])
 _bound = None
 
 
@@ -703,6 +706,38 @@ def compare_counts(refs: Sketches, queries: Sketches, min_common: int = 0, devic
     for f in _CMOMENTS_DTYPE.names:
         rows[f] = m[f]
     return rows
+
+
+def merge_pair(a: Sketches, ia: int, b: Sketches, ib: int, size: Optional[int] = None) -> Sketches:
+    """Sketch.merge (merge_sketches, python.rs:24-100) of one pair on the host, the reference's loop as written: a one-sketch
+    collection holding sketch ia of `a` merged with sketch ib of `b` and clipped by (size, the first sketch's scale)"""
+    out = _P()
+    sz = C.c_uint64(size) if size is not None else None
+    _check(lib().finch_merge_pair(a._p, ia, b._p, ib, C.byref(sz) if sz is not None else None, C.byref(out)))
+    return Sketches(out, a.params)
+
+
+def merge(sketches: Sketches, groups: Sequence[Sequence[int]], size: Optional[int] = None, devices: Sequence[int] = (0,),
+          stats: Optional[dict] = None) -> Sketches:
+    """Sketch.merge folded over groups of sketches on the GPU: result g is sketches[groups[g][0]] merged with groups[g][1], then
+    with groups[g][2], ..., each merge with the same `size` -- what folding merge_pair gives, field by field; a group of one
+    member is that member.  `stats`, if given, receives the kernels' time, the launches, the records that crossed to the host
+    and the wall times of the upload, the copies back and the k-mer gather"""
+    offsets = np.zeros(len(groups) + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(g) for g in groups], dtype=np.uint64) if len(groups) else []
+    flat = [int(i) for g in groups for i in g]
+    if any(not 0 <= i < 2 ** 32 for i in flat):
+        raise FinchError("merge: a member index is not a u32")
+    mem = np.asarray(flat, np.uint32) if flat else np.zeros(1, np.uint32)
+    devs = list(devices) if devices else [0]
+    darr = (C.c_int * len(devs))(*devs)
+    sz = C.c_uint64(size) if size is not None else None
+    out, ms, nl, nc, ph = _P(), C.c_double(), C.c_uint64(), C.c_uint64(), (C.c_double * 3)()
+    _check(lib().finch_merge_groups(sketches._p, offsets.ctypes.data, mem.ctypes.data, len(groups), C.byref(sz) if sz is not None else None,
+                                    darr, len(devs), C.byref(out), C.byref(ms), C.byref(nl), C.byref(nc), ph))
+    if stats is not None:
+        stats.update(kernel_ms=ms.value, launches=nl.value, records_copied=nc.value, upload_ms=ph[0], copy_ms=ph[1], gather_ms=ph[2])
+    return Sketches(out, sketches.params)
 
 
 def counts(sk: Sketches, i: int) -> np.ndarray:

@@ -83,8 +83,10 @@ const char *fh_last_error(void);
  * options matrix_slice, matrix_chunk_rows; 9: fh_batch_new_wide, the batch sketcher for k = 33..64;
  * 10: fh_batch_new_wide and the rest of 9 unchanged, plus finch_search and its accessors in finch_host.h;
  * 11: fh_batch_new_wide and the rest of 10 unchanged, plus finch_compare_counts, finch_compare_counts_pair and their accessors in
- * finch_host.h and the options cmpc_slice, cmpc_chunk_pairs) */
-#define FH_ABI_VERSION 11
+ * finch_host.h and the options cmpc_slice, cmpc_chunk_pairs;
+ * 12: fh_batch_new_wide and the rest of 11 unchanged, plus finch_merge_pair and finch_merge_groups in finch_host.h and the
+ * options merge_tile, merge_chunk_records) */
+#define FH_ABI_VERSION 12
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---

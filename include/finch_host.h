@@ -248,6 +248,46 @@ int finch_compare_counts_copy(const finch_compare_counts_result *r, uint32_t *re
 int finch_compare_counts_stats(const finch_compare_counts_result *r, double *kernel_ms, uint64_t *launches, uint64_t *records_copied);
 void finch_compare_counts_free(finch_compare_counts_result *r);
 
+/* merge (Sketch.merge: merge_sketches, lib/src/python.rs:24-100).  Not fh_merge, the sharded sketcher's union of partial
+ * sketches, which saturates, keeps the bottom n and both tails.  merge(first, second, size) is, in this order:
+ *   1. seq_length and num_valid_kmers of the two added (u64, wrapping);
+ *   2. a refusal if SketchParams::check_compatibility (mod.rs:185-212: k, hash type, hash bits, hash seed, in that order; not
+ *      the variant, the scale or the sizes) finds a difference: "First sketch has <what> <v1>, but second sketch has <what> <v2>";
+ *   3. one walk over the two hash lists that STOPS WHEN EITHER LIST IS EXHAUSTED (the tail of the longer list is dropped); equal
+ *      hashes give one record with the first list's k-mer and label, count = count1 + count2, extra_count = extra1 + extra2.
+ *      The two sums are u32 and WRAP (a release build of the reference; a debug build panics); nothing saturates;
+ *   4. the clip by (size, scale), scale = that of the FIRST sketch if it is Scaled, max_hash = u64::MAX / ((1. / scale) as u64):
+ *      size and scale: the longest prefix whose records have hash <= max_hash or index < size; scale alone: the prefix with
+ *      hash <= max_hash; size alone: the first size records; neither: everything.  A scale whose divisor (1. / scale) as u64 is
+ *      0 (above 1, negative, NaN), where the reference panics, is refused;
+ *   5. name, comment, sketch parameters and filter parameters stay the first sketch's.
+ * finch_merge_pair: one pair on the host, the reference's loop as written (any input it takes; size == NULL is None): *out holds
+ *   the one merged sketch.  FH_ERR_INVALID for a null argument, an index out of range, step 2's refusal, step 4's refusal.
+ * finch_merge_groups: n_groups groups in CSR form: group g = members[offsets[g] .. offsets[g + 1]) of s, in that order; *out
+ *   holds n_groups sketches.  A group's result is the left fold: a copy of its first member merged with the second, the result
+ *   with the third, ..., each with the same size -- field by field (hashes, counts, extra counts, k-mer bytes, labels, name,
+ *   comment, both parameter structs, seq_length, num_valid_kmers) what folding finch_merge_pair returns.  A group of one member
+ *   is that member, unchanged and unclipped.  With a scale the result depends on the order of the members; the order given is
+ *   the contract.  A sketch may be in several groups and more than once in one.  The fold runs on the devices, one workgroup
+ *   per group (fh_merge_lib.hip); the k-mer bytes never leave the host.  Groups of two members or more are dealt round-robin over
+ *   `devices` (as finch_dist: NULL/0 = device 0, an entry may repeat, at most 16 entries; options merge_tile and
+ *   merge_chunk_records apply).  The caller's current device is the same after the call.
+ *   Decided before any device is touched, FH_ERR_INVALID with the group and member named in finch_last_error: a null argument,
+ *   more than 16 device entries, an empty group, offsets that do not ascend, a member index out of range, a member incompatible
+ *   with its group's first member (the words of step 2), a member whose hashes are not strictly ascending (every named sketch is
+ *   checked, named as finch_dist names it), a member of 2^32 - 1 hashes or more, a group whose members have 2^32 records or more
+ *   together, a first member of a group of two or more with a scale whose divisor is 0.  FH_OK with no device needed: n_groups ==
+ *   0, or every group has one member.  Otherwise FH_ERR_NO_DEVICE without a usable device.
+ *   Statistics are out-parameters, as finch_minmer_matrix's are (any may be NULL): *kernel_ms = the kernels' time (HIP events,
+ *   summed over the launches of every device entry), *launches, *records_copied = the records that crossed from device to host:
+ *   exactly the total length of the results of the groups of two members or more; phase_ms[0..3) = wall milliseconds, summed
+ *   over the device entries, of the upload of the sketches, of the copies back, and of the k-mer gather on the host. */
+int finch_merge_pair(const finch_sketches *a, uint32_t ia, const finch_sketches *b, uint32_t ib, const uint64_t *size,
+                     finch_sketches **out);
+int finch_merge_groups(const finch_sketches *s, const uint64_t *offsets, const uint32_t *members, uint32_t n_groups, const uint64_t *size,
+                       const int *devices, uint32_t n_devices, finch_sketches **out, double *kernel_ms, uint64_t *launches,
+                       uint64_t *records_copied, double *phase_ms);
+
 /* ---- pieces that need no GPU (unit-testable on the host) ---- */
 /* Build a one-sketch result from arrays (to exercise filtering / serialisation without a device).  FH_ERR_INVALID for
  * records no sketcher can emit: count == 0 or extra_count > count (mash.rs:45-56). */
