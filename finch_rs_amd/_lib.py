@@ -11,6 +11,7 @@ SO_PATH = os.environ.get("FH_LIB", os.path.join(_HERE, "libfinch_hip.so"))
 FH_OK = 0
 FH_ERR_INVALID, FH_ERR_NO_DEVICE, FH_ERR_HIP, FH_ERR_STATE, FH_ERR_CAPACITY, FH_ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 KIND_MASH, KIND_SCALED, KIND_ALL_COUNTS = 0, 1, 2
+LARGE_MAX_N = 16384  # FH_BATCH_LARGE_MAX_N (include/finch_hip.h): hashes of a Mash sketch fh_batch_new_large serves
 
 
 class FhParams(C.Structure):
@@ -78,6 +79,8 @@ SYMBOLS = {
     "fh_batch_new": (_P, [C.POINTER(FhParams), C.c_int, C.c_uint32, C.c_uint64]),
     "fh_batch_new_counts": (_P, [C.c_uint32, C.c_int, C.c_uint32, C.c_uint64]),
     "fh_batch_new_wide": (_P, [C.POINTER(FhParams), C.c_int, C.c_uint32, C.c_uint64]),
+    "fh_batch_new_large": (_P, [C.POINTER(FhParams), C.c_int, C.c_uint32, C.c_uint64]),
+    "fh_batch_parked": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fh_batch_free": (None, [_P]),
     "fh_batch_stage": (C.c_int, [_P, C.c_int, C.POINTER(_P), _U64P]),
     "fh_batch_submit": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint32]),

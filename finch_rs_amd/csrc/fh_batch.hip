@@ -35,6 +35,11 @@
 // for "taken" is unchanged; what is new is that the collision log also receives occurrences that are no collision
 // (wide_kmer_update, fh_k2_common.h: one that raced the claimer's high word, and the 64-mers whose low word is all ones), and
 // any record sends the file the long way, where fh_finish resolves it.
+//
+// Mash sizes 3001..FH_BATCH_LARGE_MAX_N, k = 1..32 (fh_batch_new_large): the same handle and the same k2_batch -- which takes a
+// partition's geometry from its control block at run time -- over LARGER partitions, sized for the handle's n (large_geometry
+// below), and k_batch_epilogue_large (fh_batch_large.hip) in k_batch_epilogue's place: a file's ~4 n live entries no longer fit
+// a workgroup's LDS, so its select runs over a key scratch in device memory, one per file.  The rule for "taken" is unchanged.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -67,6 +72,24 @@ constexpr uint32_t PART_LIVE = 16384;     // live / dead list entries per file (
 constexpr uint32_t PART_SHARD_CAP = 512;  // entries per shard list (inserts are dealt over the 256 lists drain by drain)
 constexpr uint32_t PART_CLOG = 64;        // collision records per file (any collision sends the file the long way)
 constexpr uint64_t BATCH_MAX_N = 3000;    // kmers_to_sketch the in-LDS selection serves (fh_api.hip SMALL_N_MAX)
+constexpr uint64_t BATCH_LARGE_MAX_N = FH_BATCH_LARGE_MAX_N; // ... and the selection over device memory (fh_batch_large.hip)
+static_assert(BATCH_LARGE_MAX_N == (uint64_t)LARGE_MAX_ROWS, "the large epilogue keeps that many sorted keys in LDS");
+constexpr uint64_t LARGE_WANT = 4;        // a large file's threshold: LARGE_WANT x n hashes expected below it (option batch_large_want)
+// A large handle's partitions.  With every position a distinct k-mer and uniform hashes, the number of a file's hashes below its
+// threshold is Binomial(len, want n / len): mean 4 n, standard deviation below sqrt(4 n) = 256 at n = 16 384.  The live and
+// dropped-slot lists (and the key scratch) hold 4 n + 8192 -- 32 standard deviations at the largest n, more at every smaller
+// one -- rounded up to 1024; the table twice that, so it is at most half full; a shard list eight times its mean share
+// (live_cap / 32 against live_cap / 256: the small partitions' 512 against 48 is the same order).
+struct LargeGeometry {
+    uint32_t cap, live_cap, shard_cap;
+};
+LargeGeometry large_geometry(uint64_t n) {
+    LargeGeometry g;
+    g.live_cap = (uint32_t)((LARGE_WANT * n + 8192 + 1023) & ~1023ull);
+    g.cap = 2 * g.live_cap;
+    g.shard_cap = g.live_cap / 32;
+    return g;
+}
 // rows of a Scaled sketch: what the epilogue's workgroup holds the keys of in LDS.  The partition does not bind it: its table is
 // 37 % full at that many entries, its live and dropped-slot lists hold PART_LIVE, and the 256 shard lists take 512 each of
 // inserts that are dealt over them drain by drain (48 on average).
@@ -86,6 +109,9 @@ uint64_t expected_below(uint64_t n) { return n <= 2000 ? 4 * n : 3 * n; }
 struct fh_batch {
     fh_params p{};
     bool counts = false;   // made by fh_batch_new_counts: p.kind == FH_KIND_ALL_COUNTS, p.k = 1..7, the rest of p unused
+    bool large = false;    // made by fh_batch_new_large: Mash, 3000 < p.size <= FH_BATCH_LARGE_MAX_N, partitions of large_geometry(p.size)
+    uint32_t cap = PART_CAP, live_cap = PART_LIVE, shard_cap = PART_SHARD_CAP; // a partition's table, lists and shard lists
+    uint64_t dev_bytes = 0; // large: device memory the handle holds (what parking it costs, fh_batch_free)
     uint64_t max_hash = 0; // FH_KIND_SCALED: the threshold of every file (EMPTY64 at scale 1: everything is admitted)
     int device = 0;
     hipStream_t stream = nullptr;
@@ -99,11 +125,13 @@ struct fh_batch {
     uint32_t *live = nullptr, *dead = nullptr, *shard_cnt = nullptr, *shard_buf = nullptr;
     CollRec *clog = nullptr;
     uint64_t *kmer_hi = nullptr; // k > 32: max_files x PART_CAP high k-mer words (EMPTY64 = not written)
+    uint64_t *keys = nullptr;    // large: max_files x live_cap words of key scratch
     BatchPartition *d_parts = nullptr;
     uint32_t *ac_tables = nullptr; // counts: max_files tables of 4^k forward counts, zero between batches
     struct Slot {
         uint8_t *h_stage = nullptr, *d_stage = nullptr;
         EpiArgs *d_epi = nullptr;
+        EpiLargeArgs *d_epi_large = nullptr; // large: in d_epi's place
         Ctl *h_ctl = nullptr;
         AcBatchResult *h_res = nullptr; // counts: rows and total_kmers per file, in place of h_ctl
         uint64_t *h_out = nullptr;      // counts: three u32 columns per file (ix | count | extra_count)
@@ -130,6 +158,7 @@ void destroy(fh_batch *b) {
         if (s.h_stage) (void)hipHostFree(s.h_stage);
         if (s.d_stage) (void)hipFree(s.d_stage);
         if (s.d_epi) (void)hipFree(s.d_epi);
+        if (s.d_epi_large) (void)hipFree(s.d_epi_large);
         if (s.h_ctl) (void)hipHostFree(s.h_ctl);
         if (s.h_res) (void)hipHostFree(s.h_res);
         if (s.h_out) (void)hipHostFree(s.h_out);
@@ -145,6 +174,7 @@ void destroy(fh_batch *b) {
     if (b->shard_buf) (void)hipFree(b->shard_buf);
     if (b->clog) (void)hipFree(b->clog);
     if (b->kmer_hi) (void)hipFree(b->kmer_hi);
+    if (b->keys) (void)hipFree(b->keys);
     if (b->d_parts) (void)hipFree(b->d_parts);
     if (b->ac_tables) (void)hipFree(b->ac_tables);
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -154,31 +184,33 @@ void destroy(fh_batch *b) {
 int build(fh_batch *b) {
     const uint32_t F = b->max_files;
     const bool wide = b->p.k > 32;
+    const uint32_t PCAP = b->cap, PLIVE = b->live_cap, PSHARD = b->shard_cap; // (the small geometry unless the handle is large)
     BHIP_TRY(hipSetDevice(b->device));
     BHIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    if (wide) BHIP_TRY(api_dev_malloc((void **)&b->kmer_hi, (size_t)F * PART_CAP * sizeof(uint64_t)));
+    if (wide) BHIP_TRY(api_dev_malloc((void **)&b->kmer_hi, (size_t)F * PCAP * sizeof(uint64_t)));
+    if (b->large) BHIP_TRY(api_dev_malloc((void **)&b->keys, (size_t)F * PLIVE * sizeof(uint64_t)));
     BHIP_TRY(api_dev_malloc((void **)&b->ctls, (size_t)F * sizeof(Ctl)));
-    BHIP_TRY(api_dev_malloc((void **)&b->tables, (size_t)F * PART_CAP * sizeof(Entry)));
-    BHIP_TRY(api_dev_malloc((void **)&b->live, (size_t)F * PART_LIVE * sizeof(uint32_t)));
-    BHIP_TRY(api_dev_malloc((void **)&b->dead, (size_t)F * PART_LIVE * sizeof(uint32_t)));
+    BHIP_TRY(api_dev_malloc((void **)&b->tables, (size_t)F * PCAP * sizeof(Entry)));
+    BHIP_TRY(api_dev_malloc((void **)&b->live, (size_t)F * PLIVE * sizeof(uint32_t)));
+    BHIP_TRY(api_dev_malloc((void **)&b->dead, (size_t)F * PLIVE * sizeof(uint32_t)));
     BHIP_TRY(api_dev_malloc((void **)&b->shard_cnt, (size_t)F * N_SHARDS * SHARD_STRIDE * sizeof(uint32_t)));
-    BHIP_TRY(api_dev_malloc((void **)&b->shard_buf, (size_t)F * N_SHARDS * PART_SHARD_CAP * sizeof(uint32_t)));
+    BHIP_TRY(api_dev_malloc((void **)&b->shard_buf, (size_t)F * N_SHARDS * PSHARD * sizeof(uint32_t)));
     BHIP_TRY(api_dev_malloc((void **)&b->clog, (size_t)F * PART_CLOG * sizeof(CollRec)));
     BHIP_TRY(api_dev_malloc((void **)&b->d_parts, (size_t)F * sizeof(BatchPartition)));
     std::vector<BatchPartition> parts(F);
     for (uint32_t f = 0; f < F; ++f) {
         BatchPartition &q = parts[f];
         q.ctl = b->ctls + f;
-        q.table = b->tables + (size_t)f * PART_CAP;
-        q.live = b->live + (size_t)f * PART_LIVE;
+        q.table = b->tables + (size_t)f * PCAP;
+        q.live = b->live + (size_t)f * PLIVE;
         q.shard_cnt = b->shard_cnt + (size_t)f * N_SHARDS * SHARD_STRIDE;
-        q.shard_buf = b->shard_buf + (size_t)f * N_SHARDS * PART_SHARD_CAP;
+        q.shard_buf = b->shard_buf + (size_t)f * N_SHARDS * PSHARD;
         q.clog = b->clog + (size_t)f * PART_CLOG;
-        q.cap = PART_CAP;
-        q.live_cap = PART_LIVE;
+        q.cap = PCAP;
+        q.live_cap = PLIVE;
         q.clog_cap = PART_CLOG;
-        q.shard_cap = PART_SHARD_CAP;
-        q.kmer_hi = wide ? b->kmer_hi + (size_t)f * PART_CAP : nullptr;
+        q.shard_cap = PSHARD;
+        q.kmer_hi = wide ? b->kmer_hi + (size_t)f * PCAP : nullptr;
     }
     BHIP_TRY(hipMemcpyAsync(b->d_parts, parts.data(), (size_t)F * sizeof(BatchPartition), hipMemcpyHostToDevice, b->stream));
     const bool scaled = b->p.kind == FH_KIND_SCALED;
@@ -186,27 +218,52 @@ int build(fh_batch *b) {
     // a sketch's columns as fh_finish lays them out: hash | k-mer | first position | [k > 32: high k-mer word] | count | extra,
     // out_stride entries apart
     // (a Scaled sketch has up to BATCH_SCALED_MAX rows whatever its size)
-    const uint64_t rows = scaled ? BATCH_SCALED_MAX : std::min<uint64_t>(b->p.size + 1, (uint64_t)SMALL_MAX);
+    const uint64_t rows = scaled ? BATCH_SCALED_MAX : std::min<uint64_t>(b->p.size + 1, b->large ? BATCH_LARGE_MAX_N + 1 : (uint64_t)SMALL_MAX);
     b->out_stride = (uint32_t)(((size_t)rows + 2) & ~(size_t)1);
     b->out_words = (size_t)b->out_stride * (wide ? 5 : 4); // (3 or 4) x 8 + 2 x 4 bytes per entry
     b->header_bytes = (((uint64_t)F * sizeof(BatchFile)) + 4095) & ~4095ull;
     for (auto &s : b->slot) {
         BHIP_TRY(api_host_malloc((void **)&s.h_stage, b->header_bytes + b->data_bytes + 64));
         BHIP_TRY(api_dev_malloc((void **)&s.d_stage, b->header_bytes + b->data_bytes + 64));
-        BHIP_TRY(api_dev_malloc((void **)&s.d_epi, (size_t)F * sizeof(EpiArgs)));
+        if (b->large) BHIP_TRY(api_dev_malloc((void **)&s.d_epi_large, (size_t)F * sizeof(EpiLargeArgs)));
+        else BHIP_TRY(api_dev_malloc((void **)&s.d_epi, (size_t)F * sizeof(EpiArgs)));
         BHIP_TRY(api_host_malloc((void **)&s.h_ctl, (size_t)F * sizeof(Ctl)));
         BHIP_TRY(api_host_malloc((void **)&s.h_out, (size_t)F * b->out_words * sizeof(uint64_t)));
         BHIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
         BHIP_TRY(hipEventCreate(&s.k0));
         BHIP_TRY(hipEventCreate(&s.k1));
-        std::vector<EpiArgs> epi(F);
-        for (uint32_t f = 0; f < F; ++f) {
+        std::vector<EpiLargeArgs> epi_large(b->large ? F : 0);
+        for (uint32_t f = 0; f < F && b->large; ++f) {
+            EpiLargeArgs &e = epi_large[f];
+            e = EpiLargeArgs{};
+            e.table = parts[f].table;
+            e.live = parts[f].live;
+            e.dead = b->dead + (size_t)f * PLIVE;
+            e.shard_cnt = parts[f].shard_cnt;
+            e.shard_buf = parts[f].shard_buf;
+            e.keys = b->keys + (size_t)f * PLIVE;
+            e.ctl = parts[f].ctl;
+            e.size = b->p.size;
+            e.cap = PCAP;
+            e.live_cap = PLIVE;
+            e.dead_cap = PLIVE;
+            e.shard_cap = PSHARD;
+            e.out = s.h_out + (size_t)f * b->out_words;
+            e.out_stride = b->out_stride;
+            e.h_ctl = s.h_ctl + f;
+        }
+        if (b->large) {
+            BHIP_TRY(hipMemcpyAsync(s.d_epi_large, epi_large.data(), (size_t)F * sizeof(EpiLargeArgs), hipMemcpyHostToDevice, b->stream));
+            BHIP_TRY(hipStreamSynchronize(b->stream)); // (epi_large is a local)
+        }
+        std::vector<EpiArgs> epi(b->large ? 0 : F);
+        for (uint32_t f = 0; f < F && !b->large; ++f) {
             EpiArgs &e = epi[f];
             e = EpiArgs{};
             e.table = parts[f].table;
             e.live = parts[f].live;
-            e.dead = b->dead + (size_t)f * PART_LIVE;
-            e.dead_cap = PART_LIVE;
+            e.dead = b->dead + (size_t)f * PLIVE;
+            e.dead_cap = PLIVE;
             e.ctl = parts[f].ctl;
             e.kind = b->p.kind;
             e.size = b->p.size;
@@ -222,13 +279,18 @@ int build(fh_batch *b) {
             e.wide = wide ? 1u : 0u;
             e.h_ctl = s.h_ctl + f;
         }
-        BHIP_TRY(hipMemcpyAsync(s.d_epi, epi.data(), (size_t)F * sizeof(EpiArgs), hipMemcpyHostToDevice, b->stream));
-        BHIP_TRY(hipStreamSynchronize(b->stream)); // (epi / parts are locals)
+        if (!b->large) {
+            BHIP_TRY(hipMemcpyAsync(s.d_epi, epi.data(), (size_t)F * sizeof(EpiArgs), hipMemcpyHostToDevice, b->stream));
+            BHIP_TRY(hipStreamSynchronize(b->stream)); // (epi / parts are locals)
+        }
         s.tau.resize(F);
         s.len.resize(F);
         s.status.resize(F);
     }
     BHIP_TRY(hipStreamSynchronize(b->stream));
+    b->dev_bytes = (uint64_t)F * ((uint64_t)PCAP * (sizeof(Entry) + (wide ? 8 : 0)) + (uint64_t)PLIVE * (8 + (b->large ? 8 : 0)) +
+                                  (uint64_t)N_SHARDS * (PSHARD + SHARD_STRIDE) * 4 + sizeof(Ctl) + PART_CLOG * sizeof(CollRec)) +
+                   2 * (b->header_bytes + b->data_bytes + 64);
     return FH_OK;
 }
 
@@ -302,7 +364,7 @@ static fh_batch *batch_new_checked(const fh_params *params, int device, uint32_t
         std::lock_guard<std::mutex> g(g_pool_mu);
         for (size_t i = 0; i < g_pool.size(); ++i) {
             fh_batch *c = g_pool[i];
-            if (!c->counts && c->device == device && c->max_files == max_files && c->data_bytes == ((stage_bytes + 4095) & ~4095ull) &&
+            if (!c->counts && !c->large && c->device == device && c->max_files == max_files && c->data_bytes == ((stage_bytes + 4095) & ~4095ull) &&
                 c->p.k == params->k && c->p.size == params->size && c->p.seed == params->seed && c->p.kind == params->kind &&
                 (!scaled || c->p.scale == params->scale)) {
                 g_pool.erase(g_pool.begin() + (long)i);
@@ -352,8 +414,8 @@ fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, 
     if (params->k < 1 || params->k > 32 || params->hash_mask != 0 ||
         (scaled ? params->size > BATCH_SCALED_MAX : (params->size < 1 || params->size > BATCH_MAX_N))) {
         api_fail(FH_ERR_UNSUPPORTED,
-                 "the batch sketcher serves Mash sketches of 1..%llu hashes and Scaled sketches of size 0..%llu, k = 1..32, no test mask (k = 33..64: fh_batch_new_wide)",
-                 (unsigned long long)BATCH_MAX_N, (unsigned long long)BATCH_SCALED_MAX);
+                 "the batch sketcher serves Mash sketches of 1..%llu hashes and Scaled sketches of size 0..%llu, k = 1..32, no test mask (k = 33..64: fh_batch_new_wide; Mash sketches of 3001..%u hashes: fh_batch_new_large)",
+                 (unsigned long long)BATCH_MAX_N, (unsigned long long)BATCH_SCALED_MAX, (unsigned)BATCH_LARGE_MAX_N);
         return nullptr;
     }
     if (scaled && !(params->scale > 0.0 && params->scale <= 1.0)) { // (as fh_new)
@@ -361,6 +423,86 @@ fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, 
         return nullptr;
     }
     return batch_new_checked(params, device, max_files, stage_bytes);
+}
+
+fh_batch *fh_batch_new_large(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
+    if (!params) {
+        api_fail(FH_ERR_INVALID, "null params");
+        return nullptr;
+    }
+    if (params->kind == FH_KIND_SCALED || params->kind == FH_KIND_ALL_COUNTS) {
+        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_large serves Mash sketches only: %s", params->kind == FH_KIND_SCALED
+                 ? "Scaled (kind 1) batches are fh_batch_new's (k = 1..32) and fh_batch_new_wide's"
+                 : "AllCounts (kind 2) batches are fh_batch_new_counts");
+        return nullptr;
+    }
+    if (params->kind != FH_KIND_MASH) {
+        api_fail(FH_ERR_INVALID, "unknown sketch kind %u (fh_batch_new_large: 0 Mash)", params->kind);
+        return nullptr;
+    }
+    if (params->size <= BATCH_MAX_N) {
+        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_large serves Mash sketches of %llu..%u hashes: size %llu is fh_batch_new's (1..%llu)",
+                 (unsigned long long)BATCH_MAX_N + 1, (unsigned)BATCH_LARGE_MAX_N, (unsigned long long)params->size, (unsigned long long)BATCH_MAX_N);
+        return nullptr;
+    }
+    if (params->size > BATCH_LARGE_MAX_N) {
+        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_large serves Mash sketches of %llu..%u hashes (FH_BATCH_LARGE_MAX_N): size %llu goes through an fh_sketcher",
+                 (unsigned long long)BATCH_MAX_N + 1, (unsigned)BATCH_LARGE_MAX_N, (unsigned long long)params->size);
+        return nullptr;
+    }
+    if (params->k < 1 || params->k > 32) {
+        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_large serves k = 1..32: k = %u goes through an fh_sketcher", params->k);
+        return nullptr;
+    }
+    if (params->hash_mask != 0) {
+        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher takes no test mask (hash_mask must be 0)");
+        return nullptr;
+    }
+    // (the bound of fh_batch_new_counts: a slot of fewer than 2^21 tiles of the two-bit form, so a file has fewer than 2^32 positions)
+    if (max_files < 1 || max_files > BATCH_MAX_FILES || stage_bytes < 4096 || stage_bytes > COUNTS_MAX_STAGE) {
+        api_fail(FH_ERR_INVALID, "max_files 1..%u, stage_bytes 4 KiB..%llu (a slot of fewer than 2^21 tiles of the two-bit form)", BATCH_MAX_FILES,
+                 (unsigned long long)COUNTS_MAX_STAGE);
+        return nullptr;
+    }
+    if (!device_ok(device)) return nullptr;
+    const uint64_t data_bytes = (stage_bytes + 4095) & ~4095ull;
+    {
+        // a parked handle: large, the same n (the partitions are sized for it), k and seed; never one of the other constructors'
+        std::lock_guard<std::mutex> g(g_pool_mu);
+        for (size_t i = 0; i < g_pool.size(); ++i) {
+            fh_batch *c = g_pool[i];
+            if (c->large && c->device == device && c->max_files == max_files && c->data_bytes == data_bytes && c->p.k == params->k &&
+                c->p.size == params->size && c->p.seed == params->seed) {
+                g_pool.erase(g_pool.begin() + (long)i);
+                return c;
+            }
+        }
+    }
+    fh_batch *b = new (std::nothrow) fh_batch;
+    if (!b) {
+        api_fail(FH_ERR_CAPACITY, "out of host memory");
+        return nullptr;
+    }
+    b->p = *params;
+    b->large = true;
+    const LargeGeometry geo = large_geometry(params->size);
+    b->cap = geo.cap;
+    b->live_cap = geo.live_cap;
+    b->shard_cap = geo.shard_cap;
+    b->device = device;
+    b->max_files = max_files;
+    b->data_bytes = data_bytes;
+    try {
+        if (build(b) != FH_OK) {
+            destroy(b);
+            return nullptr;
+        }
+    } catch (...) {
+        destroy(b);
+        api_fail(FH_ERR_CAPACITY, "out of host memory");
+        return nullptr;
+    }
+    return b;
 }
 
 fh_batch *fh_batch_new_wide(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
@@ -460,9 +602,31 @@ fh_batch *fh_batch_new_counts(uint32_t k, int device, uint32_t max_files, uint64
 void fh_batch_free(fh_batch *b) {
     if (!b) return;
     bool idle = !b->slot[0].in_flight && !b->slot[1].in_flight;
+    // a large handle is parked only within the options `pool` (handles; 0 = none) and `pool_bytes` (device memory, the default
+    // of the sketchers' pool: the smaller of 24 GiB and a tenth of the device), counted over the parked large handles
+    uint64_t large_max = 0, large_max_bytes = 0;
+    if (idle && b->large) {
+        large_max = cfg_u64("pool", 64);
+        if (cfg("pool_bytes")) {
+            large_max_bytes = cfg_u64("pool_bytes", 0);
+        } else {
+            size_t free_b = 0, total_b = 0;
+            large_max_bytes = 24ull << 30;
+            if (hipSetDevice(b->device) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b)
+                large_max_bytes = std::min<uint64_t>(large_max_bytes, (uint64_t)total_b / 10);
+            else (void)hipGetLastError();
+        }
+    }
     if (idle) {
         std::lock_guard<std::mutex> g(g_pool_mu);
-        if (g_pool.size() < BATCH_POOL_MAX) {
+        bool room = g_pool.size() < BATCH_POOL_MAX;
+        if (b->large) {
+            uint64_t n_large = 0, bytes = b->dev_bytes;
+            for (const fh_batch *c : g_pool)
+                if (c->large) n_large++, bytes += c->dev_bytes;
+            room = room && n_large < large_max && bytes <= large_max_bytes;
+        }
+        if (room) {
             b->profiling = false;
             b->prof_ms = 0.0;
             b->prof_launches = b->prof_positions = 0;
@@ -473,6 +637,17 @@ void fh_batch_free(fh_batch *b) {
         }
     }
     destroy(b);
+}
+
+int fh_batch_parked(uint64_t *handles, uint64_t *large_handles, uint64_t *large_device_bytes) {
+    std::lock_guard<std::mutex> g(g_pool_mu);
+    uint64_t n_large = 0, bytes = 0;
+    for (const fh_batch *c : g_pool)
+        if (c->large) n_large++, bytes += c->dev_bytes;
+    if (handles) *handles = g_pool.size();
+    if (large_handles) *large_handles = n_large;
+    if (large_device_bytes) *large_device_bytes = bytes;
+    return FH_OK;
 }
 
 int fh_batch_stage(fh_batch *b, int slot, uint8_t **buf, uint64_t *cap) {
@@ -508,7 +683,8 @@ static int batch_submit(fh_batch *b, int slot, const uint64_t *offsets, const ui
         d.len = lens[f];
         d.ctl = b->counts ? nullptr : b->ctls + f;
         // the threshold below which E of the file's positions' hashes are expected (every position a distinct k-mer, hashes uniform)
-        const uint64_t E = expected_below(b->p.size);
+        // (large: option batch_large_want in place of the factor -- tests force a short guess or a full live list with it)
+        const uint64_t E = b->large ? std::max<uint64_t>(1, cfg_u64("batch_large_want", LARGE_WANT)) * b->p.size : expected_below(b->p.size);
         uint64_t tau = EMPTY64;
         if (b->counts) {
             tau = 0; // (not looked at)
@@ -569,7 +745,7 @@ static int batch_submit(fh_batch *b, int slot, const uint64_t *offsets, const ui
         BHIP_TRY(wide ? launch_k2bw((int)b->p.k, a, (uint32_t)waves, b->stream) : launch_k2b((int)b->p.k, a, (uint32_t)waves, b->stream));
         if (b->profiling) BHIP_TRY(hipEventRecord(s.k1, b->stream));
     }
-    BHIP_TRY(launch_batch_epilogue(s.d_epi, n_files, 1u, b->stream));
+    BHIP_TRY(b->large ? launch_batch_epilogue_large(s.d_epi_large, n_files, 1u, b->stream) : launch_batch_epilogue(s.d_epi, n_files, 1u, b->stream));
     BHIP_TRY(hipEventRecord(s.done, b->stream));
     s.in_flight = true;
     return FH_OK;

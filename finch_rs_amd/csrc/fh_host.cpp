@@ -4010,6 +4010,9 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     // what a batch of genomes is: Mash sketches of <= 3000 hashes (after the cut to final_size the small sketcher makes),
     // k <= 64 (above 32 through a handle of fh_batch_new_wide), no filtering (the default for FASTA, lib.rs:70-76), regular
     // uncompressed files that begin with '>'.
+    // Mash sketches of 3001..FH_BATCH_LARGE_MAX_N hashes at k <= 32 (`-n 10000`): through a handle of fh_batch_new_large, whose
+    // partitions are several MiB a file -- such groups hold `batch_large_files` files (default 16), not 64.  k = 33..64 at those
+    // sizes keeps going one by one.
     // Anything else, and every file the batch path reports as not taken, goes through sketch_stream as before.
     // Scaled sketches (kind 1) likewise: a file is sketched at max_hash and taken iff it holds between kmers_to_sketch and
     // FH_BATCH_SCALED_MAX distinct hashes at or below it (fh_batch.hip); process_post_filter leaves a Scaled sketch as it is.
@@ -4019,7 +4022,8 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     const bool group_scaled = sp->kind == 1;
     const uint64_t group_n = group_scaled ? sp->kmers_to_sketch
                                           : ((sp->final_size >= 1 && sp->final_size < sp->kmers_to_sketch) ? sp->final_size : sp->kmers_to_sketch);
-    const bool group_ok = batch && (group_counts ? sp->kmer_length <= 7 : group_scaled ? (group_n <= FH_BATCH_SCALED_MAX && sp->scale > 0.0 && sp->scale <= 1.0) : (sp->kind == 0 && group_n >= 1 && group_n <= 3000)) &&
+    const bool group_large = sp->kind == 0 && group_n > 3000 && group_n <= FH_BATCH_LARGE_MAX_N && sp->kmer_length <= 32;
+    const bool group_ok = batch && (group_counts ? sp->kmer_length <= 7 : group_scaled ? (group_n <= FH_BATCH_SCALED_MAX && sp->scale > 0.0 && sp->scale <= 1.0) : (sp->kind == 0 && group_n >= 1 && (group_n <= 3000 || group_large))) &&
                           sp->kmer_length >= 1 && sp->kmer_length <= 64 && filters->filter_on <= 0 && file_batch_enabled();
     // A Scaled file whose size says it cannot fit is not staged at all (sending it would cost a wasted pass): if every byte began
     // a distinct k-mer, st_size x max_hash / 2^64 hashes would lie at or below max_hash.  Margin: staged up to 5/4 of the cap --
@@ -4029,7 +4033,9 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     const uint64_t group_max_hash = group_scaled && group_ok ? fh::api_scaled_max_hash(sp->scale) : 0;
     const uint64_t group_max_expect = (uint64_t)FH_BATCH_SCALED_MAX + FH_BATCH_SCALED_MAX / 4;
     constexpr uint64_t GROUP_STAGE = 32ull << 20;
-    constexpr uint32_t GROUP_FILES = 64;
+    // files per group, and per handle: 64, or what a large handle's memory allows (6 MiB of device memory a file at n = 10 000,
+    // include/finch_hip.h: 16 files are 161 MiB a worker, and sixteen workgroups of the epilogue a launch)
+    const uint32_t GROUP_FILES = group_large ? (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, cfg_u64("batch_large_files", 16))) : 64u;
     const size_t READ_PIECE = std::max<uint64_t>(4096, cfg_u64("batch_read_piece", 256u << 10)); // bytes of a file read and packed at a time
     auto worker = [&](uint32_t w) {
         HandleSet handles;
@@ -4167,6 +4173,7 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
                 fh_params bp = to_fh(*sp, 0);
                 bp.size = group_n;
                 bt = group_counts ? fh_batch_new_counts(sp->kmer_length, handles.device, GROUP_FILES, GROUP_STAGE)
+                                  : group_large ? fh_batch_new_large(&bp, handles.device, GROUP_FILES, GROUP_STAGE)
                                   : sp->kmer_length > 32 ? fh_batch_new_wide(&bp, handles.device, GROUP_FILES, GROUP_STAGE) // (two-word k-mers: fh_k2bw.hip)
                                                          : fh_batch_new(&bp, handles.device, GROUP_FILES, GROUP_STAGE);
                 if (bt && (fh_batch_stage(bt, 0, &stage[0], &stage_cap) != FH_OK || fh_batch_stage(bt, 1, &stage[1], &stage_cap) != FH_OK)) {

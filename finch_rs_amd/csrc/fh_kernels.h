@@ -98,6 +98,25 @@ hipError_t launch_small_epilogue(const EpiArgs &a, hipStream_t st);
 // FIN_OK_RESET (an overflow somewhere), sweeps file f's whole partition so that the next batch finds it clean all the same.
 // read_first: what the reset control block's admit path is told (Ctl::read_first).
 hipError_t launch_batch_epilogue(const EpiArgs *args, uint32_t n_files, uint32_t read_first, hipStream_t st);
+// the epilogue of a batch of Mash files of 3001..LARGE_MAX_ROWS hashes (fh_batch_large.hip, fh_batch_new_large): workgroup f
+// finishes file f out of device memory where k_batch_epilogue works in LDS -- flatten, the keys gathered once into the file's key
+// scratch, radix select, the survivors sorted chunk by chunk and ranked, rows and mirrored control block to the host, the
+// partition left reset (swept as a whole if the file is not taken).  The descriptor repeats the partition's geometry
+// (BatchPartition below), so the kernel reads it from nothing it writes.
+constexpr uint32_t LARGE_MAX_ROWS = 16384;
+struct EpiLargeArgs {
+    Entry *table;
+    uint32_t *live, *dead;          // live_cap entries each
+    uint32_t *shard_cnt, *shard_buf;
+    uint64_t *keys;                 // the file's key scratch: live_cap words
+    Ctl *ctl;
+    uint64_t size;
+    uint32_t cap, live_cap, dead_cap, shard_cap;
+    uint64_t *out;                  // hash | k-mer | first position | count | extra columns, out_stride entries apart (pinned)
+    uint32_t out_stride;
+    Ctl *h_ctl;                     // pinned host mirror of the control block, written last
+};
+hipError_t launch_batch_epilogue_large(const EpiLargeArgs *args, uint32_t n_files, uint32_t read_first, hipStream_t st);
 // one workgroup per file: table partition filled with empty entries, control block initialised and pointed at the partition
 struct BatchPartition {
     Ctl *ctl;

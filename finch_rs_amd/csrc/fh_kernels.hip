@@ -13,6 +13,7 @@
 
 #include "fh_core.h"
 #include "fh_device.h"
+#include "fh_epilogue_dev.h"
 #include "fh_kernels.h"
 
 namespace fh {
@@ -221,31 +222,6 @@ struct SmallLds {
 };
 constexpr size_t SMALL_LDS_BYTES = (size_t)SMALL_MAX * 8 + (size_t)SMALL_SORT_MAX * 12;
 constexpr u32 PRUNE_DECLINED = 0xFFFFFFFFu;
-
-// The all-LDS bitonic network over N (a power of two, <= SMALL_SORT_MAX) (key, slot) pairs, ascending; the caller has padded
-// [n, N) with EMPTY64 keys and put a barrier behind its writes.  Ends on a barrier.
-__device__ __forceinline__ void bitonic_lds(u64 *skeys, u32 *sslots, u32 N) {
-    const u32 tid = threadIdx.x, nthr = blockDim.x;
-    for (u32 kk = 2; kk <= N; kk <<= 1) {
-        for (u32 jj = kk >> 1; jj > 0; jj >>= 1) {
-            for (u32 i = tid; i < N; i += nthr) {
-                const u32 ixj = i ^ jj;
-                if (ixj > i) {
-                    const bool up = (i & kk) == 0;
-                    const u64 a = skeys[i], b = skeys[ixj];
-                    if ((a > b) == up) {
-                        skeys[i] = b;
-                        skeys[ixj] = a;
-                        const u32 sa = sslots[i];
-                        sslots[i] = sslots[ixj];
-                        sslots[ixj] = sa;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
 
 // More rows than the network holds (a Scaled file of a batch: SMALL_SORT_MAX < M <= SMALL_MAX, every live entry a row, nothing
 // to select).  keys[0, M) are the hashes in live-list order and fill the LDS block's first 96 KiB; the 48 KiB behind them hold
@@ -520,9 +496,6 @@ hipError_t launch_prune_small(Entry *table, u32 *live, u32 *dead, u32 dead_cap, 
 // synchronisation; a pass over 50 Gbases queues its speculative prefix, the verdict, the gated main launch and the finish
 // back to back.  The host checks the mirrored control block afterwards and falls back to the step-by-step path whenever
 // something did not go as queued (speculation failed, launch stopped early, more live entries than the LDS holds).
-__device__ __forceinline__ void clear_entry(Entry *e);
-__device__ __forceinline__ void init_ctl_dev(Ctl *ctl, u64 tau0, u32 keep_text_bases, u64 sel_size, u64 tau_floor, u32 hist_on);
-
 // (the body of k_small_epilogue and of k_batch_epilogue's workgroups; returns what the gather reported: 0, FIN_OK or FIN_OK_RESET)
 __device__ __forceinline__ u32 small_epilogue_body(const EpiArgs &a, unsigned char *smem, u32 *s_hist, u32 *s_wsum, u64 *s_bcast,
                                                    u32 *s_cnt, u32 *s_off, u32 &s_live) {
@@ -880,14 +853,6 @@ hipError_t launch_fill_table(Entry *table, u64 cap, hipStream_t st) {
     return hipGetLastError();
 }
 
-__device__ __forceinline__ void clear_entry(Entry *e) {
-    e->hash = EMPTY64;
-    e->kmer = EMPTY64;
-    e->pos = EMPTY64;
-    e->count = 0;
-    e->extra = 0;
-}
-
 // reset support: clear exactly the slots this run touched; a full sweep only if the dropped-slot list overflowed
 __global__ void k_clear_slots(Entry *table, u64 cap, const u32 *live, const u32 *dead, const Ctl *ctl) {
     const u64 stride = (u64)gridDim.x * blockDim.x;
@@ -989,40 +954,6 @@ hipError_t launch_live_flatten(Ctl *ctl, hipStream_t st) {
     hipLaunchKernelGGL(k_live_flatten, dim3(N_SHARDS), dim3(256), 0, st, ctl);
     hipLaunchKernelGGL(k_live_commit, dim3(1), dim3(256), 0, st, ctl);
     return hipGetLastError();
-}
-
-__device__ __forceinline__ void init_ctl_dev(Ctl *ctl, u64 tau0, u32 keep_text_bases, u64 sel_size, u64 tau_floor, u32 hist_on) {
-    if (threadIdx.x == 0) {
-        ctl->tau = tau0;
-        ctl->inserted_total = 0;
-        ctl->n_live = 0;
-        ctl->overflow = 0;
-        ctl->n_coll = 0;
-        ctl->need_big = 0;
-        ctl->sorted = 1;
-        ctl->spec_ok = 0;
-        ctl->n_dead = 0;
-        ctl->hist_on = hist_on;
-        ctl->sel_size = sel_size;
-        ctl->tau_floor = tau_floor;
-        ctl->next_unit = 0;
-        ctl->left_in_pos = 0;
-        ctl->n_left_out = 0;
-        ctl->stopped = 0;
-        ctl->soft_limit = 0xFFFFFFFFu;
-        ctl->shard_soft = 0xFFFFFFFFu;
-        ctl->read_first = 0;
-        ctl->dbg_flush_cycles = ctl->dbg_flush_calls = ctl->dbg_flush_entries = ctl->dbg_wave_cycles = 0;
-        ctl->sp_count = 0;
-        ctl->sp_extra = 0;
-        ctl->sp_pos = EMPTY64;
-        ctl->sp_kmer = EMPTY64;
-        if (!keep_text_bases) ctl->text_bases = 0;
-    }
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) {
-        ctl->kmer_counts[i] = 0;
-        ctl->hist[i] = 0;
-    }
 }
 
 __global__ void k_init_ctl(Ctl *ctl, u64 tau0, u32 keep_text_bases, u64 sel_size, u64 tau_floor, u32 hist_on) {

@@ -77,6 +77,8 @@ const OptDef DEFS[] = {
     {"file_batch", "0 = every file of a finch_sketch_files batch through a sketcher of its own (no many-per-launch groups)"},
     {"batch_two_bit", "0 = a group's files cross the link as bytes, not in the two-bit form (fh_batch_submit_packed)"},
     {"batch_read_piece", "bytes of a file a worker reads and packs at a time (default 256 KiB: stays in the core's L2; tests: many pieces)"},
+    {"batch_large_want", "Mash groups of 3001..16384 hashes: target live-set size of a file's threshold, in units of n (default 4; tests: 1 = a short guess, large = a full live list)"},
+    {"batch_large_files", "files per group of Mash sketches of 3001..16384 hashes in finch_sketch_files, 1..64 (default 16)"},
     {"pack_scalar", "the two-bit packer's form (tests): 1 = portable, 2 = two passes with AVX2 (no BMI2); default: one pass with AVX2 + BMI2 where the CPU has them"},
     // --- FASTQ text in host memory ---
     {"fastq_host_strip", "0 = FASTQ text always goes to the device-side splitter; 1 = stripped on the host whatever the read threads (default: from 8 read threads on)"},

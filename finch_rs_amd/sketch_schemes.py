@@ -252,11 +252,13 @@ class BatchSketcher:
     launch, finished by one epilogue launch, one synchronisation -- what a worker of sketch_files (lib.rs:29-49) does with
     the files it has staged.  Mash (1..3000 hashes) or Scaled (kind=KIND_SCALED, size 0..SCALED_MAX_ROWS, scale in (0, 1]: a
     file is taken iff it holds between `size` and SCALED_MAX_ROWS distinct hashes at or below max_hash), k <= 32;
-    `BatchSketcher.wide(...)` makes one for k = 33..64.
+    `BatchSketcher.wide(...)` makes one for k = 33..64, `BatchSketcher.large(...)` one for Mash sketches of 3001..LARGE_MAX_N
+    hashes (k <= 32).
     `sketch_many(blocks)` -> per block either (records, kmers, first_pos, total_kmers) or None ("not taken": sketch that
     block through a HipSketcher)."""
 
     SCALED_MAX_ROWS = 12288  # FH_BATCH_SCALED_MAX (include/finch_hip.h): rows of a Scaled sketch the batch path serves
+    LARGE_MAX_N = _lib.LARGE_MAX_N  # FH_BATCH_LARGE_MAX_N: hashes of a Mash sketch `BatchSketcher.large` serves
 
     def __init__(self, size: int, kmer_length: int, seed: int = 0, device: int = 0, max_files: int = 64,
                  stage_bytes: int = 64 << 20, kind: int = KIND_MASH, scale: float = 0.0):
@@ -299,6 +301,29 @@ class BatchSketcher:
         if not self._h:
             raise FinchHipError(-1, (self._L.fh_last_error() or b"").decode(errors="replace"))
         return self
+
+    @classmethod
+    def large(cls, size: int, kmer_length: int, seed: int = 0, device: int = 0, max_files: int = 16, stage_bytes: int = 32 << 20):
+        """A batch sketcher for Mash sketches of 3001..LARGE_MAX_N hashes, k = 1..32 (fh_batch_new_large): partitions sized for
+        `size`, the selection out of device memory (fh_batch_large.hip); the same stage / submit / pack / wait / result /
+        sketch_many / counters in both input forms and the same meaning of "not taken"."""
+        self = cls.__new__(cls)
+        self._L = _lib.load()
+        self.size, self.kmer_length, self.seed, self.device = size, kmer_length, seed, device
+        self.max_files = max_files
+        self.kind, self.scale = KIND_MASH, 0.0
+        p = FhParams(KIND_MASH, kmer_length, size, seed, 0.0, 0, 0, 0)
+        self._h = self._L.fh_batch_new_large(C.byref(p), device, max_files, stage_bytes)
+        if not self._h:
+            raise FinchHipError(-1, (self._L.fh_last_error() or b"").decode(errors="replace"))
+        return self
+
+    @staticmethod
+    def parked():
+        """batch handles fh_batch_free has parked: (all, the large ones among them, device bytes those hold)"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(_lib.load().fh_batch_parked(C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def close(self):
         if getattr(self, "_h", None):

@@ -85,8 +85,10 @@ const char *fh_last_error(void);
  * 11: fh_batch_new_wide and the rest of 10 unchanged, plus finch_compare_counts, finch_compare_counts_pair and their accessors in
  * finch_host.h and the options cmpc_slice, cmpc_chunk_pairs;
  * 12: fh_batch_new_wide and the rest of 11 unchanged, plus finch_merge_pair and finch_merge_groups in finch_host.h and the
- * options merge_tile, merge_chunk_records) */
-#define FH_ABI_VERSION 12
+ * options merge_tile, merge_chunk_records;
+ * 13: fh_batch_new_wide and the rest of 12 unchanged, plus fh_batch_new_large (batches of Mash sketches of 3001..16384 hashes),
+ * fh_batch_parked and the options batch_large_want, batch_large_files) */
+#define FH_ABI_VERSION 13
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---
@@ -332,7 +334,7 @@ int fh_sketch_device_blocks(fh_sketcher *const *handles, const void *const *dev_
  * caller has staged with one copy, one launch of the sketch kernel over the files' tiles (fh_k2b.hip), one launch of the
  * epilogue (a workgroup per file: select, sort, to_vec straight into pinned host memory, state left reset) and one
  * synchronisation.  Mash sketches of 1..3000 hashes and Scaled sketches (size 0..FH_BATCH_SCALED_MAX, scale as fh_new takes
- * it), k = 1..32 (k = 33..64: fh_batch_new_wide below), any seed; everything else (AllCounts: FH_ERR_UNSUPPORTED here, see
+ * it), k = 1..32 (k = 33..64: fh_batch_new_wide below; Mash sketches of 3001..16384 hashes: fh_batch_new_large below), any seed; everything else (AllCounts: FH_ERR_UNSUPPORTED here, see
  * fh_batch_new_counts below) -- and every
  * file the batch path cannot vouch for -- goes through an fh_sketcher.
  * A Scaled file is sketched at max_hash itself (scaled.rs:22-34) and is taken iff it holds at least `size` and at most
@@ -422,6 +424,30 @@ fh_batch *fh_batch_new_counts(uint32_t k, int device, uint32_t max_files, uint64
  * record sends the file through an fh_sketcher (which resolves them).  That costs time, never a wrong sketch.
  * A parked handle is handed out again by fh_batch_new_wide only. */
 fh_batch *fh_batch_new_wide(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes);
+/* Batches of files at Mash sizes above 3000 (`mash sketch -s 10000`): 3000 < size <= FH_BATCH_LARGE_MAX_N, k = 1..32, any seed.
+ * A handle of the same type, served by every fh_batch_* function above with the same staging rules, both input forms and the
+ * same meaning of "taken": a file is sketched at the threshold below which 4 x size of its positions' hashes are expected
+ * (option batch_large_want: another factor), the epilogue keeps the `size` smallest, and a file with fewer than `size`
+ * distinct hashes below its threshold, a 64-bit collision or any overflow is NOT TAKEN.  What differs is behind the door: the
+ * partitions are sized for the handle's `size` (live list 4 x size + 8192, rounded up to 1024; table twice that), and the
+ * epilogue (fh_batch_large.hip) selects out of a key scratch in device memory, because 4 x size hashes do not fit a workgroup's
+ * LDS.  Refused with FH_ERR_UNSUPPORTED, by name and before the device check: size <= 3000 (those are fh_batch_new's), size >
+ * FH_BATCH_LARGE_MAX_N, Scaled and AllCounts, k = 0 or k > 32, a test mask; with FH_ERR_INVALID: an unknown kind, max_files
+ * outside 1..4096, stage_bytes outside 4 KiB .. 2^21 x 768 - 4096 (a slot of fewer than 2^21 tiles of the two-bit form, as for
+ * fh_batch_new_counts).
+ * Memory: per file a handle holds 128 x live_cap bytes + 38 KiB of device memory -- 9.0 MiB at size 16 384, 6.0 MiB at
+ * 10 000, 3.5 MiB at 5 000 -- and 32 x (size + 2) bytes of pinned result columns per slot, on top of the two staging buffers
+ * and their device twins.  At the 16 files and 32 MiB that finch_sketch_files uses: 161 MiB of device and 74 MiB of pinned
+ * memory at size 10 000 (209 / 80 MiB at 16 384); 64 files at 16 384 would be 642 MiB of device memory a worker, which is
+ * why those groups are smaller than the 64 of the small ones.
+ * Parking: fh_batch_free parks an idle large handle only within the options `pool` (parked large handles; 0 = none) and
+ * `pool_bytes` (their device memory together; default the smaller of 24 GiB and a tenth of the device); a parked one is handed
+ * out again by fh_batch_new_large only, for the same size, k, seed, device and sizes -- never to fh_batch_new or
+ * fh_batch_new_wide, nor one of theirs to it.  fh_batch_parked: the batch handles parked now, the large ones among them and
+ * the device memory those hold (any pointer may be NULL). */
+#define FH_BATCH_LARGE_MAX_N 16384u /* hashes of a Mash sketch the batch path serves (what the large epilogue sorts through one workgroup's LDS) */
+fh_batch *fh_batch_new_large(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes);
+int fh_batch_parked(uint64_t *handles, uint64_t *large_handles, uint64_t *large_device_bytes);
 
 /* --- measurement support (bench.py) --- */
 /* when enabled, every sketch-kernel launch is bracketed by HIP events on the handle's stream */
