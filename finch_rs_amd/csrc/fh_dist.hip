@@ -410,6 +410,21 @@ int dist_wait(DistDevice *d, int buf, const uint32_t **out, double *kernel_ms) {
     return FH_OK;
 }
 
+int dist_counts_query_major(const DistDeviceArrays &v, uint32_t r0, uint32_t r1, uint32_t *out, void *stream) {
+    if (r1 <= r0 || v.nq == 0 || v.slice == 0 || v.slice > DIST_MAX_SLICE || (r1 - r0 + RB - 1) / RB > 65535u)
+        return api_fail(FH_ERR_INVALID, "dist_counts_query_major: %u references, slice %u", r1 - r0, v.slice);
+    DistArgs a;
+    a.qh = v.qh, a.qoff = v.qoff, a.rh = v.rh, a.roff = v.roff;
+    a.qmax = a.rmax = nullptr; // (read only where a flag's bit 1 is set)
+    a.qscale = a.rscale = nullptr;
+    a.qflag = v.qflag, a.rflag = v.rflag;
+    a.nq = v.nq, a.r0 = r0, a.r1 = r1, a.slice = v.slice;
+    a.out = out;
+    hipLaunchKernelGGL(k_dist_counts<true>, dim3(v.nq, (r1 - r0 + RB - 1) / RB), dim3(THREADS), v.slice * sizeof(uint64_t), (hipStream_t)stream, a);
+    DHIP_TRY(hipGetLastError());
+    return FH_OK;
+}
+
 int search_launch(DistDevice *d, int buf, uint32_t r0, uint32_t r1) {
     if (!d->search) return api_fail(FH_ERR_STATE, "search_launch on a handle of dist_open");
     if (r1 <= r0 || d->nq == 0 || (uint64_t)(r1 - r0) * d->nq > d->max_pairs || (r1 - r0 + RB - 1) / RB > 65535u)

@@ -5325,6 +5325,318 @@ void finch_search_free(finch_search_result *r) { delete r; }
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------
+// gather: the greedy decomposition of a query over a library (the contract is finch_host.h's comment; not in the reference).
+// Plain set semantics over the hashes as stored -- deliberately not raw_distance's walk.  finch_gather_query is the loop as the
+// contract reads, on the host; finch_gather keeps the loop on the device (fh_gather.hip): the candidate list and the records
+// come here, to be put in order and given their doubles by the function the host loop uses.  DESIGN.md §3.13.
+// ---------------------------------------------------------------------------------------------
+struct finch_gather_result {
+    std::vector<uint64_t> offsets; // n_queries + 1
+    std::vector<finch_gather_row> rows;
+    double kernel_ms = 0.;
+    uint64_t launches = 0, candidates = 0, copied = 0;
+};
+
+namespace {
+
+// the five doubles of a row from its integers and the sum of all of the query's counts: plain IEEE divisions, nothing guarded
+void gather_row_doubles(finch_gather_row *row, uint64_t query_count_sum) {
+    row->f_unique_to_query = (double)row->overlap / (double)row->query_len;
+    row->f_orig_query = (double)row->common / (double)row->query_len;
+    row->f_match = (double)row->common / (double)row->ref_len;
+    row->average_abund = (double)row->abund / (double)row->overlap;
+    row->f_unique_weighted = (double)row->abund / (double)query_count_sum;
+}
+
+uint64_t gather_count_sum(const Sketch &q) {
+    uint64_t s = 0;
+    for (const KmerCount &h : q.hashes) s += h.count;
+    return s;
+}
+
+// what both entry points make of their arguments: min_overlap below 1 is 1; no sketch has 2^32 - 1 hashes, so neither number
+// means anything else above that
+uint32_t gather_clamp(uint64_t v, uint64_t least) { return (uint32_t)std::min<uint64_t>(std::max(v, least), UINT32_MAX); }
+
+int gather_check_ascending(const Sketch &s, const char *what, size_t idx) {
+    const std::vector<KmerCount> &h = s.hashes;
+    for (size_t j = 1; j < h.size(); ++j)
+        if (!(h[j - 1].hash < h[j].hash))
+            return hfail(FH_ERR_INVALID, "%s sketch %zu (%s): hashes not strictly ascending at %zu", what, idx, s.name.c_str(), j);
+    return FH_OK;
+}
+
+// the contract's loop for one query: `in` marks S_t over the query's positions; c_j(t) and the sum of counts by looking every
+// hash of H_j up in Q
+void gather_on_host(const std::vector<Sketch> &Rs, const Sketch &Q, uint32_t iq, uint32_t min_overlap, uint32_t max_rounds,
+                    std::vector<finch_gather_row> &rows) {
+    const std::vector<KmerCount> &q = Q.hashes;
+    std::vector<uint8_t> in(q.size(), 1);
+    auto walk = [&](const Sketch &R, bool remove, uint64_t *abund) {
+        uint64_t c = 0;
+        for (const KmerCount &x : R.hashes) {
+            auto it = std::lower_bound(q.begin(), q.end(), x.hash, [](const KmerCount &a, uint64_t h) { return a.hash < h; });
+            if (it == q.end() || it->hash != x.hash || !in[it - q.begin()]) continue;
+            ++c;
+            if (abund) *abund += it->count;
+            if (remove) in[it - q.begin()] = 0;
+        }
+        return c;
+    };
+    std::vector<uint64_t> c0(Rs.size());
+    const uint64_t count_sum = gather_count_sum(Q);
+    uint64_t remaining = q.size();
+    for (uint64_t t = 0; max_rounds == 0 || t < max_rounds; ++t) {
+        uint64_t best = 0;
+        size_t w = 0;
+        for (size_t j = 0; j < Rs.size(); ++j) {
+            const uint64_t c = walk(Rs[j], false, nullptr);
+            if (t == 0) c0[j] = c;
+            if (c > best) best = c, w = j; // (among equal counts the smallest j)
+        }
+        if (best < min_overlap) break;
+        finch_gather_row row{};
+        row.query = iq, row.reference = w, row.round = t, row.overlap = best, row.common = c0[w];
+        row.ref_len = Rs[w].hashes.size(), row.query_len = q.size();
+        walk(Rs[w], true, &row.abund);
+        remaining -= best;
+        row.remaining = remaining;
+        gather_row_doubles(&row, count_sum);
+        rows.push_back(row);
+    }
+}
+
+constexpr uint64_t GATHER_POS_BYTES = 1ull << 30; // a chunk's position arrays: a design choice, not a measurement
+
+} // namespace
+
+extern "C" {
+
+int finch_gather_query(const finch_sketches *refs, const finch_sketches *queries, uint32_t iq, uint64_t min_overlap, uint64_t max_rounds,
+                       finch_gather_row *rows, uint64_t cap, uint64_t *n) try {
+    if (!refs || !queries || !n || (cap && !rows)) return hfail(FH_ERR_INVALID, "null argument");
+    if (iq >= queries->v.size()) return hfail(FH_ERR_INVALID, "query sketch %u of %zu sketches", iq, queries->v.size());
+    if (int rc = gather_check_ascending(queries->v[iq], "query", iq)) return rc;
+    for (size_t j = 0; j < refs->v.size(); ++j)
+        if (int rc = gather_check_ascending(refs->v[j], "reference", j)) return rc;
+    std::vector<finch_gather_row> out;
+    gather_on_host(refs->v, queries->v[iq], iq, gather_clamp(min_overlap, 1), gather_clamp(max_rounds, 0), out);
+    for (size_t i = 0; i < out.size() && i < cap; ++i) rows[i] = out[i];
+    *n = out.size();
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_gather(const finch_sketches *queries, const finch_sketches *refs, uint64_t min_overlap, uint64_t max_rounds, const int *devices,
+                 uint32_t n_devices, finch_gather_result **out) try {
+    if (!queries || !refs || !out || (n_devices && !devices)) return hfail(FH_ERR_INVALID, "null argument");
+    if (n_devices > DIST_MAX_ENTRIES) return hfail(FH_ERR_INVALID, "at most %u device entries (got %u)", DIST_MAX_ENTRIES, n_devices);
+    const std::vector<Sketch> &Qs = queries->v, &Rs = refs->v;
+    if (int rc = check_ascending(Qs, "query")) return rc;
+    if (int rc = check_ascending(Rs, "reference")) return rc;
+    for (size_t q = 0; q < Qs.size(); ++q)
+        if (Qs[q].hashes.size() > fh::GATHER_MAX_QUERY)
+            return hfail(FH_ERR_UNSUPPORTED, "query sketch %zu (%s) has %zu hashes (a gather takes at most %u: one bit each in the rounds kernel's LDS)",
+                         q, Qs[q].name.c_str(), Qs[q].hashes.size(), fh::GATHER_MAX_QUERY);
+    const uint32_t nq = (uint32_t)Qs.size(), nr = (uint32_t)Rs.size();
+    auto res = std::make_unique<finch_gather_result>();
+    res->offsets.assign((size_t)nq + 1, 0);
+    if (nq == 0 || nr == 0) {
+        *out = res.release();
+        return FH_OK;
+    }
+    const int ndev = fh_device_count();
+    if (ndev <= 0) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
+    std::vector<int> devs = n_devices ? std::vector<int>(devices, devices + n_devices) : std::vector<int>{0};
+    for (int d : devs)
+        if (d < 0 || d >= ndev) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device: device %d requested, %d visible", d, ndev);
+    struct RestoreDevice { // (this thread runs the first device entry)
+        int prev = fh::matrix_current_device();
+        ~RestoreDevice() { fh::matrix_restore_device(prev); }
+    } restore_device;
+
+    const uint32_t min_ov = gather_clamp(min_overlap, 1), max_r = gather_clamp(max_rounds, 0);
+    const uint32_t n_entries = (uint32_t)std::min<size_t>(devs.size(), nq); // (an entry without a query opens nothing)
+    const uint64_t chunk_pairs = std::min<uint64_t>(std::max<uint64_t>(1, cfg_u64("dist_chunk_pairs", DIST_CHUNK_PAIRS)), 1ull << 31);
+    const uint32_t dist_slice = (uint32_t)std::min<uint64_t>(cfg_u64("dist_slice", 4096), UINT32_MAX);
+    const uint32_t gather_slice = (uint32_t)std::min<uint64_t>(cfg_u64("gather_slice", fh::GATHER_MAX_SLICE), UINT32_MAX);
+    const uint64_t pos_bytes = cfg_u64("gather_pos_bytes", GATHER_POS_BYTES);
+    // the references once, for every entry
+    std::vector<uint64_t> rh, roff(1, 0);
+    {
+        size_t total = 0;
+        for (const Sketch &s : Rs) total += s.hashes.size();
+        rh.reserve(total);
+        roff.reserve((size_t)nr + 1);
+    }
+    for (const Sketch &s : Rs) {
+        for (const KmerCount &h : s.hashes) rh.push_back(h.hash);
+        roff.push_back(rh.size());
+    }
+    std::vector<std::vector<finch_gather_row>> rows_of(nq);
+
+    std::mutex err_mu;
+    int err_rc = FH_OK;
+    std::string err_msg;
+    auto fail_with = [&](int rc, const std::string &msg) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (err_rc == FH_OK) err_rc = rc, err_msg = msg;
+    };
+    std::mutex stat_mu;
+
+    // one thread per device entry: the queries e, e + n_entries, ...
+    fork_join(n_entries, [&](unsigned e) {
+        fh::GatherDevice *gd = nullptr;
+        try {
+            std::vector<uint32_t> mine; // local query -> the caller's index
+            for (uint32_t q = e; q < nq; q += n_entries) mine.push_back(q);
+            const uint32_t nqe = (uint32_t)mine.size();
+            std::vector<uint64_t> qh, qoff(1, 0);
+            std::vector<uint32_t> qcnt;
+            {
+                size_t total = 0;
+                for (uint32_t q : mine) total += Qs[q].hashes.size();
+                qh.reserve(total);
+                qcnt.reserve(total);
+                qoff.reserve((size_t)nqe + 1);
+            }
+            for (uint32_t q : mine) {
+                for (const KmerCount &h : Qs[q].hashes) qh.push_back(h.hash), qcnt.push_back(h.count);
+                qoff.push_back(qh.size());
+            }
+            const uint32_t per_chunk = (uint32_t)std::min<uint64_t>({std::max<uint64_t>(1, chunk_pairs / nqe), nr, 65535ull * 64});
+            if ((uint64_t)per_chunk * nqe > (1ull << 31)) { // (per_chunk = 1 here: more than 2^31 queries on one entry)
+                fail_with(FH_ERR_UNSUPPORTED, "a device entry has " + std::to_string(nqe) + " queries: more than 2^31 pairs per reference");
+                return;
+            }
+            const fh::GatherSide qside{qh.data(), qcnt.data(), qoff.data(), nqe}, rside{rh.data(), nullptr, roff.data(), nr};
+            if (int rc = fh::gather_open(devs[e], qside, rside, dist_slice, gather_slice, (uint64_t)per_chunk * nqe, min_ov, &gd)) {
+                fail_with(rc, fh_last_error());
+                return;
+            }
+            double ms = 0.;
+            uint64_t launches = 0, copied = 0;
+            int rc = FH_OK;
+            bool bad_record = false; // (already reported)
+            // 1. the candidates of every query of this entry, reference chunk by reference chunk
+            std::vector<fh::GatherCand> cands;
+            for (uint32_t r0 = 0; rc == FH_OK && r0 < nr; r0 += per_chunk) rc = fh::gather_count(gd, r0, std::min(nr, r0 + per_chunk), &cands, &ms, &launches);
+            if (rc != FH_OK) {
+                fail_with(rc, fh_last_error());
+                fh::gather_close(gd);
+                return;
+            }
+            for (const fh::GatherCand &c : cands)
+                if (c.q >= nqe || c.r >= nr) {
+                    fail_with(FH_ERR_STATE, "gather: candidate (" + std::to_string(c.q) + ", " + std::to_string(c.r) + ")");
+                    fh::gather_close(gd);
+                    return;
+                }
+            std::sort(cands.begin(), cands.end(), [](const fh::GatherCand &a, const fh::GatherCand &b) { return a.q < b.q || (a.q == b.q && a.r < b.r); });
+            std::vector<uint64_t> first((size_t)nqe + 1, 0), need(nqe, 0); // each query's candidates, the bytes of their positions
+            for (const fh::GatherCand &c : cands) ++first[c.q + 1], need[c.q] += (uint64_t)c.common * sizeof(uint32_t);
+            for (uint32_t q = 0; q < nqe; ++q) first[q + 1] += first[q];
+            for (uint32_t q = 0; q < nqe; ++q)
+                if (need[q] > pos_bytes) {
+                    char msg[512];
+                    snprintf(msg, sizeof msg, "query sketch %u (%s): the positions of its %llu candidates take %llu bytes (option gather_pos_bytes: %llu)",
+                             mine[q], Qs[mine[q]].name.c_str(), (unsigned long long)(first[q + 1] - first[q]), (unsigned long long)need[q],
+                             (unsigned long long)pos_bytes);
+                    fail_with(FH_ERR_UNSUPPORTED, msg);
+                    fh::gather_close(gd);
+                    return;
+                }
+            // 2. chunks of queries whose position arrays fit the budget: positions, then every round, one launch each
+            std::vector<fh::GatherRecord> recs;
+            for (uint32_t q0 = 0; rc == FH_OK && !bad_record && q0 < nqe;) {
+                uint32_t q1 = q0;
+                uint64_t bytes = 0;
+                while (q1 < nqe && (q1 == q0 || (bytes + need[q1] <= pos_bytes && first[q1 + 1] - first[q0] < (1ull << 30)))) bytes += need[q1++];
+                const uint64_t n = first[q1] - first[q0];
+                recs.clear();
+                if (n) rc = fh::gather_rounds(gd, q0, q1, cands.data() + first[q0], n, max_r, &recs, &ms, &launches);
+                if (rc != FH_OK) break;
+                copied += recs.size();
+                // the records of the chunk, each at its round
+                for (const fh::GatherRecord &x : recs) {
+                    const uint64_t nc = x.q >= q0 && x.q < q1 ? first[x.q + 1] - first[x.q] : 0;
+                    if (x.round >= nc || x.cand >= nc || cands[first[x.q] + x.cand].r != x.r) {
+                        fail_with(FH_ERR_STATE, "gather: a record of query " + std::to_string(x.q) + ", round " + std::to_string(x.round));
+                        bad_record = true;
+                        break;
+                    }
+                    std::vector<finch_gather_row> &to = rows_of[mine[x.q]];
+                    if (to.size() <= x.round) to.resize((size_t)x.round + 1, finch_gather_row{0, 0, UINT64_MAX, 0, 0, 0, 0, 0, 0, 0., 0., 0., 0., 0.});
+                    finch_gather_row &row = to[x.round];
+                    if (row.round != UINT64_MAX) {
+                        fail_with(FH_ERR_STATE, "gather: two records of query " + std::to_string(x.q) + ", round " + std::to_string(x.round));
+                        bad_record = true;
+                        break;
+                    }
+                    row.query = mine[x.q], row.reference = x.r, row.round = x.round, row.overlap = x.overlap, row.common = x.common;
+                    row.ref_len = x.ref_len, row.query_len = x.query_len, row.abund = x.abund, row.remaining = x.remaining;
+                }
+                q0 = q1;
+            }
+            if (rc != FH_OK) fail_with(rc, fh_last_error());
+            std::lock_guard<std::mutex> g(stat_mu);
+            res->kernel_ms += ms;
+            res->launches += launches;
+            res->candidates += cands.size();
+            res->copied += copied;
+        } catch (const std::bad_alloc &) {
+            fail_with(FH_ERR_CAPACITY, "out of host memory");
+        }
+        fh::gather_close(gd);
+    });
+    if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
+
+    for (uint32_t q = 0; q < nq; ++q) res->offsets[q + 1] = res->offsets[q] + rows_of[q].size();
+    res->rows.reserve(res->offsets[nq]);
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint64_t count_sum = gather_count_sum(Qs[q]);
+        for (finch_gather_row &row : rows_of[q]) {
+            if (row.round == UINT64_MAX) return hfail(FH_ERR_STATE, "gather: query %u has a round without a record", q);
+            gather_row_doubles(&row, count_sum);
+            res->rows.push_back(row);
+        }
+    }
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+uint64_t finch_gather_len(const finch_gather_result *r) { return r ? r->rows.size() : 0; }
+
+int finch_gather_offsets(const finch_gather_result *r, uint64_t *offsets) try {
+    if (!r || !offsets) return hfail(FH_ERR_INVALID, "null argument");
+    memcpy(offsets, r->offsets.data(), r->offsets.size() * sizeof(uint64_t));
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_gather_copy(const finch_gather_result *r, uint32_t *query_idx, uint32_t *ref_idx, finch_gather_row *rows) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    const size_t n = r->rows.size();
+    for (size_t i = 0; i < n; ++i) {
+        if (query_idx) query_idx[i] = (uint32_t)r->rows[i].query;
+        if (ref_idx) ref_idx[i] = (uint32_t)r->rows[i].reference;
+    }
+    if (rows && n) memcpy(rows, r->rows.data(), n * sizeof(finch_gather_row));
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_gather_stats(const finch_gather_result *r, double *kernel_ms, uint64_t *launches, uint64_t *candidates, uint64_t *records_copied) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    if (kernel_ms) *kernel_ms = r->kernel_ms;
+    if (launches) *launches = r->launches;
+    if (candidates) *candidates = r->candidates;
+    if (records_copied) *records_copied = r->copied;
+    return FH_OK;
+} FINCH_CATCH
+
+void finch_gather_free(finch_gather_result *r) { delete r; }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
 // compare_counts (Sketch.compare_counts, lib/src/python.rs:496-559): the merge walk with the summed counts of the shared hashes
 // and the moment recurrence over the query's counts of them.  finch_compare_counts_pair is the reference's loop as written, on
 // the host; finch_compare_counts gets the integers and m2, m3, m4 of many pairs from the device (fh_moments.hip), sorts the

@@ -92,6 +92,9 @@ const OptDef DEFS[] = {
     // --- finch_compare_counts ---
     {"cmpc_slice", "query entries per LDS slice of the compare-counts kernel, 1..4096 (default 4096; tests: many slices per query)"},
     {"cmpc_chunk_pairs", "pairs per compare-counts launch, at most 2^31 (default 4 M; tests: many reference chunks)"},
+    // --- finch_gather ---
+    {"gather_slice", "query hashes per LDS slice of the gather's positions kernel, 1..4096 (default 4096; tests: many slices per query)"},
+    {"gather_pos_bytes", "bytes of position arrays per chunk of queries of a gather (default 1 GiB; tests: one query per chunk, a query that does not fit)"},
     // --- finch_merge_groups ---
     {"merge_tile", "output positions per tile of a merge step, 1..4096 (default 1024; tests: many tiles per step)"},
     {"merge_chunk_records", "accumulator records per merge launch, at most 2^31 (default 4 M; tests: many launches)"},

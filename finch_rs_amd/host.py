@@ -142,6 +142,13 @@ _SYMS["finch_search_offsets"] = (C.c_int, [_P, _P])
 _SYMS["finch_search_copy"] = (C.c_int, [_P, _P, _P, _P])
 _SYMS["finch_search_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _SYMS["finch_search_free"] = (None, [_P])
+_SYMS["finch_gather_query"] = (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)])
+_SYMS["finch_gather"] = (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P)])
+_SYMS["finch_gather_len"] = (C.c_uint64, [_P])
+_SYMS["finch_gather_offsets"] = (C.c_int, [_P, _P])
+_SYMS["finch_gather_copy"] = (C.c_int, [_P, _P, _P, _P])
+_SYMS["finch_gather_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+_SYMS["finch_gather_free"] = (None, [_P])
 
 
 class CCountMoments(C.Structure):
@@ -665,6 +672,50 @@ def filter_to_matches(refs: Sketches, queries: Sketches, iq: int, threshold: flo
     >= threshold, in library order, as a collection of their own"""
     _, rows = search(select(queries, [iq]), refs, threshold, 0, devices)
     return select(refs, np.sort(rows["reference"]))
+
+
+# one row of finch_gather / finch_gather_query: finch_gather_row's nine integers and five doubles
+GATHER_DTYPE = np.dtype([(f, np.uint64) for f in ("query", "reference", "round", "overlap", "common", "ref_len", "query_len", "abund",
+                                                   "remaining")] +
+                        [(f, np.float64) for f in ("f_unique_to_query", "f_orig_query", "f_match", "average_abund", "f_unique_weighted")])
+
+
+def gather_query(refs: Sketches, queries: Sketches, iq: int, min_overlap: int = 1, max_rounds: int = 0) -> np.ndarray:
+    """the greedy decomposition of sketch iq of `queries` over the library `refs` on the host, the loop as the contract
+    (include/finch_host.h) reads -> GATHER_DTYPE rows in round order: round t takes the reference that shares the most hashes
+    with what is left of the query (ties: the lowest index), at least min_overlap (below 1: 1) of them, and removes its hashes
+    from the query; at most max_rounds rounds if max_rounds > 0"""
+    rows = np.zeros(len(refs), GATHER_DTYPE)  # (a reference is never taken twice)
+    n = C.c_uint64()
+    _check(lib().finch_gather_query(refs._p, queries._p, int(iq), int(min_overlap), int(max_rounds), rows.ctypes.data if len(rows) else None,
+                                    len(rows), C.byref(n)))
+    return rows[:n.value]
+
+
+def gather(queries: Sketches, refs: Sketches, min_overlap: int = 1, max_rounds: int = 0, devices: Sequence[int] = (0,),
+           stats: Optional[dict] = None):
+    """gather_query for every query, the loop on the GPU -> (offsets, rows): the GATHER_DTYPE rows grouped by query in query order,
+    query q's being rows[offsets[q]:offsets[q + 1]] in round order; every field is what gather_query gives.  `stats`, if given,
+    receives the kernels' time, the kernel launches, the candidates (pairs that share at least min_overlap hashes) and the records
+    that crossed to the host (exactly the rows)"""
+    L = lib()
+    devs = list(devices) if devices else [0]
+    darr = (C.c_int * len(devs))(*devs)
+    p = _P()
+    _check(L.finch_gather(queries._p, refs._p, int(min_overlap), int(max_rounds), darr, len(devs), C.byref(p)))
+    try:
+        n = L.finch_gather_len(p)
+        offsets = np.zeros(len(queries) + 1, np.uint64)
+        _check(L.finch_gather_offsets(p, offsets.ctypes.data))
+        rows = np.empty(n, GATHER_DTYPE)
+        _check(L.finch_gather_copy(p, None, None, rows.ctypes.data))
+        if stats is not None:
+            ms, nl, nc, nrec = C.c_double(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+            _check(L.finch_gather_stats(p, C.byref(ms), C.byref(nl), C.byref(nc), C.byref(nrec)))
+            stats.update(kernel_ms=ms.value, launches=nl.value, candidates=nc.value, records_copied=nrec.value)
+    finally:
+        L.finch_gather_free(p)
+    return offsets, rows
 
 
 # one row of finch_compare_counts: the indices of the pair, then finch_count_moments' fields

@@ -87,8 +87,10 @@ const char *fh_last_error(void);
  * 12: fh_batch_new_wide and the rest of 11 unchanged, plus finch_merge_pair and finch_merge_groups in finch_host.h and the
  * options merge_tile, merge_chunk_records;
  * 13: fh_batch_new_wide and the rest of 12 unchanged, plus fh_batch_new_large (batches of Mash sketches of 3001..16384 hashes),
- * fh_batch_parked and the options batch_large_want, batch_large_files) */
-#define FH_ABI_VERSION 13
+ * fh_batch_parked and the options batch_large_want, batch_large_files;
+ * 14: fh_batch_new_wide and the rest of 13 unchanged, plus finch_gather, finch_gather_query and their accessors in finch_host.h
+ * and the options gather_slice, gather_pos_bytes) */
+#define FH_ABI_VERSION 14
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---

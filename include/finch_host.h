@@ -210,6 +210,59 @@ int finch_search_copy(const finch_search_result *r, uint32_t *query_idx, uint32_
 int finch_search_stats(const finch_search_result *r, double *kernel_ms, uint64_t *launches, uint64_t *candidates_copied);
 void finch_search_free(finch_search_result *r);
 
+/* gather: the greedy decomposition of a query sketch over a library -- what follows a search whose best-first list is full of
+ * near-duplicates.  Not in the reference; the contract is this comment (tests/gather_model.py states it twice in Python).
+ *   gather(Q, refs, min_overlap, max_rounds) for one query sketch Q and the library refs[0 .. R):
+ *     min_overlap below 1 is taken as 1 (a reference that shares nothing explains nothing); max_rounds = 0 means no cap.
+ *     S_0 = the set of Q's hashes.  PLAIN SET SEMANTICS over the hashes as stored: no max_hash cut, no early stop of a merge
+ *     walk -- deliberately not raw_distance's walk (distance.rs:66-126); callers compare like with like.
+ *     Round t = 0, 1, ...: c_j(t) = |S_t n H_j| for every reference j; the winner w has the largest c_j(t), among equal counts
+ *     the smallest j.  Stop if c_w(t) < min_overlap, or if t == max_rounds and max_rounds > 0.  Otherwise one row, and
+ *     S_{t+1} = S_t \ H_w.  c_j(t) never grows with t and a chosen reference has c = 0 afterwards, so a query has at most as
+ *     many rows as it has references with c_j(0) >= min_overlap.
+ *   Row integers: query, reference = w, round = t, overlap = c_w(t), common = c_w(0), ref_len = |H_w|, query_len = |Q|,
+ *     abund = the u64 sum of Q's `count` over S_t n H_w, remaining = |S_{t+1}|.
+ *   Row doubles, made on the host by one function for both entry points, plain IEEE divisions of the integers as doubles,
+ *     nothing guarded: f_unique_to_query = overlap / query_len, f_orig_query = common / query_len, f_match = common / ref_len,
+ *     average_abund = abund / overlap, f_unique_weighted = abund / (the u64 sum of all of Q's counts).
+ *   Rows of a query are in round order; queries are independent.
+ * finch_gather_query: query iq of `queries` on the host, the loop as written above: up to `cap` rows into rows[] (NULL with cap
+ *   0), *n = the rows the query has (never more than the library has sketches).  Any hash lists that ascend strictly.
+ *   FH_ERR_INVALID for a null argument, an index out of range, hashes that do not ascend strictly.
+ * finch_gather: every query, on the devices; rows grouped by query in query order, finch_gather_offsets gives the CSR over them
+ *   as finch_search_offsets does.  Every field of every row is bit for bit what finch_gather_query gives (two NaNs count as
+ *   equal).  Queries are dealt round-robin over `devices` (as finch_dist: NULL/0 = device 0, an entry may repeat, at most 16
+ *   entries).  Per device entry: the counting pass of finch_search over reference chunks (options dist_slice and
+ *   dist_chunk_pairs apply), whose counts stay on the device -- only the pairs with c_j(0) >= min_overlap cross, as a list --,
+ *   then per chunk of queries the positions of every candidate's shared hashes in its query (option gather_slice: query hashes
+ *   per LDS slice) and all rounds of every query in one launch; a chunk's position arrays hold at most gather_pos_bytes bytes
+ *   (default 1 GiB; 4 bytes per shared hash of a candidate).  Down the link go the candidate list and the rows, nothing else.
+ *   Decided before any device is touched: FH_ERR_INVALID for a null argument, more than 16 device entries, a sketch whose hashes
+ *   are not strictly ascending (named in finch_last_error, as finch_dist names it); a sketch of 2^32 - 1 hashes or more is
+ *   refused as finch_dist refuses it; FH_ERR_UNSUPPORTED for a query of more than 1 048 576 hashes (named, with the limit: one
+ *   bit per query hash in the rounds kernel's 128 KiB of LDS); zero queries or zero references: FH_OK, no rows, no device
+ *   needed.  Otherwise FH_ERR_NO_DEVICE without a usable device.  After the counting pass: FH_ERR_UNSUPPORTED for a query whose
+ *   positions alone exceed gather_pos_bytes (named, with the bytes it needs).  FH_ERR_STATE, never a wrong row, if the device's
+ *   positions disagree with its counts.  The caller's current device is the same after the call.
+ * finch_gather_stats: the kernels' time (HIP events, summed over the launches of every device entry), the kernel launches,
+ * candidates = the pairs with c_j(0) >= min_overlap (exactly the list entries that crossed to the host), records_copied = the
+ * records that crossed: exactly the rows; any pointer may be NULL. */
+typedef struct finch_gather_row {
+    uint64_t query, reference, round, overlap, common, ref_len, query_len, abund, remaining;
+    double f_unique_to_query, f_orig_query, f_match, average_abund, f_unique_weighted;
+} finch_gather_row;
+int finch_gather_query(const finch_sketches *refs, const finch_sketches *queries, uint32_t iq, uint64_t min_overlap, uint64_t max_rounds,
+                       finch_gather_row *rows, uint64_t cap, uint64_t *n);
+typedef struct finch_gather_result finch_gather_result;
+int finch_gather(const finch_sketches *queries, const finch_sketches *refs, uint64_t min_overlap, uint64_t max_rounds, const int *devices,
+                 uint32_t n_devices, finch_gather_result **out);
+uint64_t finch_gather_len(const finch_gather_result *r);
+int finch_gather_offsets(const finch_gather_result *r, uint64_t *offsets /* n_queries + 1 */);
+/* row i: query index, reference index, the row; any pointer may be NULL */
+int finch_gather_copy(const finch_gather_result *r, uint32_t *query_idx, uint32_t *ref_idx, finch_gather_row *rows);
+int finch_gather_stats(const finch_gather_result *r, double *kernel_ms, uint64_t *launches, uint64_t *candidates, uint64_t *records_copied);
+void finch_gather_free(finch_gather_result *r);
+
 /* compare_counts (Sketch.compare_counts, lib/src/python.rs:496-559): the merge walk of a reference sketch and a query sketch
  * that also sums the abundances of the shared hashes and runs the one-pass recurrence for the higher moments of the query's
  * abundances over them.  The eight values are the reference's tuple, in its order:
