@@ -225,6 +225,10 @@ static hipError_t sort_pairs(void *tmp, size_t tmp_bytes, u64 *keys, u64 *keys_t
     return hipGetLastError();
 }
 
+hipError_t big_sort_pairs(void *tmp, size_t tmp_bytes, u64 *keys, u64 *keys_tmp, u32 *vals, u32 *vals_tmp, u32 M, hipStream_t st) {
+    return sort_pairs(tmp, tmp_bytes, keys, keys_tmp, vals, vals_tmp, M, st);
+}
+
 hipError_t launch_big_prune(Entry *table, u32 *live, u32 *dead, u32 dead_cap, Ctl *ctl, u32 M, u32 n_dead_now, u32 kind,
                             u64 size, u64 max_hash, u64 *keys_a, u64 *keys_b, u32 *slots_a, u32 *slots_b, void *tmp,
                             size_t tmp_bytes, u32 *keep_dev, hipStream_t st) {

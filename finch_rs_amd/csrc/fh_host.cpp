@@ -41,6 +41,7 @@
 #include "fh_fqstrip.h"
 #include "fh_pack2.h"
 #include "fh_dist.h"
+#include "fh_index.h"
 #include "fh_matrix.h"
 #include "fh_moments.h"
 #include "fh_merge_lib.h"
@@ -5135,6 +5136,8 @@ struct finch_search_result {
     std::vector<finch_distance_out> d;
     double kernel_ms = 0.;
     uint64_t launches = 0, copied = 0;
+    bool from_index = false; // made by finch_index_search: `touched` = the pairs its device counted
+    uint64_t touched = 0;
 };
 
 namespace {
@@ -5142,6 +5145,59 @@ namespace {
 struct SearchCand {
     uint32_t q, r, c, i, j;
 };
+
+// what finch_search and finch_index_search do with the candidates the device left (`found`: lists in any order, emptied here):
+// by query, each query's sorted by (containment descending, reference ascending) and cut to top_n; the doubles are
+// distance_from_counts', as finch_distance has them.  res->offsets: n_queries + 1 zeros on entry.
+int search_finish(std::vector<std::vector<SearchCand>> &found, const std::vector<Sketch> &Qs, uint32_t nr, uint32_t top_n, finch_search_result *res) {
+    const uint32_t nq = (uint32_t)Qs.size();
+    std::vector<uint64_t> at((size_t)nq + 1, 0);
+    for (const auto &f : found)
+        for (const SearchCand &x : f) {
+            if (x.q >= nq || x.r >= nr) return hfail(FH_ERR_STATE, "search: candidate (%u, %u) of %u x %u", x.q, x.r, nq, nr);
+            ++at[x.q + 1];
+        }
+    for (uint32_t q = 0; q < nq; ++q) at[q + 1] += at[q];
+    struct Row {
+        uint32_t r;
+        finch_distance_out d;
+    };
+    std::vector<Row> rows(at[nq]);
+    {
+        std::vector<uint64_t> fill(at.begin(), at.end() - 1);
+        for (auto &f : found) {
+            for (const SearchCand &x : f) {
+                Row &row = rows[fill[x.q]++];
+                row.r = x.r;
+                distance_from_counts(false, x.c, x.i, x.j, Qs[x.q].sketch_params.kmer_length, true, &row.d);
+            }
+            std::vector<SearchCand>().swap(f);
+        }
+    }
+    const unsigned T = (unsigned)std::min<uint64_t>(DIST_MAX_ENTRIES, std::max<uint64_t>(1, rows.size() >> 16));
+    const uint32_t per = (nq + T - 1) / T;
+    fork_join(T, [&](unsigned t) {
+        for (uint32_t q = std::min(nq, t * per); q < std::min<uint64_t>(nq, (uint64_t)(t + 1) * per); ++q)
+            std::sort(rows.begin() + at[q], rows.begin() + at[q + 1], [](const Row &a, const Row &b) {
+                return a.d.containment > b.d.containment || (a.d.containment == b.d.containment && a.r < b.r);
+            });
+    });
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint64_t have = at[q + 1] - at[q];
+        res->offsets[q + 1] = res->offsets[q] + (top_n ? std::min<uint64_t>(have, top_n) : have);
+    }
+    const uint64_t total = res->offsets[nq];
+    res->q.resize(total);
+    res->r.resize(total);
+    res->d.resize(total);
+    for (uint32_t q = 0; q < nq; ++q)
+        for (uint64_t o = res->offsets[q], s = at[q]; o < res->offsets[q + 1]; ++o, ++s) {
+            res->q[o] = q;
+            res->r[o] = rows[s].r;
+            res->d[o] = rows[s].d;
+        }
+    return FH_OK;
+}
 
 } // namespace
 
@@ -5244,53 +5300,7 @@ int finch_search(const finch_sketches *queries, const finch_sketches *refs, doub
     });
     if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
 
-    // the candidates by query (chunks in reference order), each query's sorted by (containment descending, reference ascending)
-    // and cut to top_n; the doubles are distance_from_counts', as finch_distance has them
-    std::vector<uint64_t> at((size_t)nq + 1, 0);
-    for (const auto &f : found)
-        for (const SearchCand &x : f) {
-            if (x.q >= nq || x.r >= nr) return hfail(FH_ERR_STATE, "search: candidate (%u, %u) of %u x %u", x.q, x.r, nq, nr);
-            ++at[x.q + 1];
-        }
-    for (uint32_t q = 0; q < nq; ++q) at[q + 1] += at[q];
-    struct Row {
-        uint32_t r;
-        finch_distance_out d;
-    };
-    std::vector<Row> rows(at[nq]);
-    {
-        std::vector<uint64_t> fill(at.begin(), at.end() - 1);
-        for (auto &f : found) {
-            for (const SearchCand &x : f) {
-                Row &row = rows[fill[x.q]++];
-                row.r = x.r;
-                distance_from_counts(false, x.c, x.i, x.j, Qs[x.q].sketch_params.kmer_length, true, &row.d);
-            }
-            std::vector<SearchCand>().swap(f);
-        }
-    }
-    const unsigned T = (unsigned)std::min<uint64_t>(DIST_MAX_ENTRIES, std::max<uint64_t>(1, rows.size() >> 16));
-    const uint32_t per = (nq + T - 1) / T;
-    fork_join(T, [&](unsigned t) {
-        for (uint32_t q = std::min(nq, t * per); q < std::min<uint64_t>(nq, (uint64_t)(t + 1) * per); ++q)
-            std::sort(rows.begin() + at[q], rows.begin() + at[q + 1], [](const Row &a, const Row &b) {
-                return a.d.containment > b.d.containment || (a.d.containment == b.d.containment && a.r < b.r);
-            });
-    });
-    for (uint32_t q = 0; q < nq; ++q) {
-        const uint64_t have = at[q + 1] - at[q];
-        res->offsets[q + 1] = res->offsets[q] + (top_n ? std::min<uint64_t>(have, top_n) : have);
-    }
-    const uint64_t total = res->offsets[nq];
-    res->q.resize(total);
-    res->r.resize(total);
-    res->d.resize(total);
-    for (uint32_t q = 0; q < nq; ++q)
-        for (uint64_t o = res->offsets[q], s = at[q]; o < res->offsets[q + 1]; ++o, ++s) {
-            res->q[o] = q;
-            res->r[o] = rows[s].r;
-            res->d[o] = rows[s].d;
-        }
+    if (int rc = search_finish(found, Qs, nr, top_n, res.get())) return rc;
     *out = res.release();
     return FH_OK;
 } FINCH_CATCH
@@ -5321,6 +5331,173 @@ int finch_search_stats(const finch_search_result *r, double *kernel_ms, uint64_t
 } FINCH_CATCH
 
 void finch_search_free(finch_search_result *r) { delete r; }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// index: the same search through an inverted index of the library's hashes (fh_index.hip), built once per library.  The device
+// counts only the pairs that share a hash -- the only ones a threshold above 0 can keep --; their candidates come here and go
+// through finch_search's own finish, so the rows are finch_search's.  DESIGN.md §3.14.
+// ---------------------------------------------------------------------------------------------
+struct finch_index {
+    uint32_t nr = 0, chunk = 0;
+    uint64_t postings = 0, device_bytes = 0;
+    double build_ms = 0.;
+    std::vector<fh::IndexDevice *> entries; // one per device entry; none where the library has no hash
+    std::mutex mu;                          // one search at a time: the counters belong to the index
+    ~finch_index() {
+        if (entries.empty()) return;
+        const int prev = fh::matrix_current_device();
+        for (fh::IndexDevice *d : entries) fh::index_close(d);
+        fh::matrix_restore_device(prev);
+    }
+};
+
+namespace {
+
+constexpr uint64_t INDEX_STATE_BYTES = 256ull << 20; // counters plus touched lists of a launch by default, at most
+constexpr uint64_t INDEX_CHUNK_MAX = 4096;           // ... and its queries, at most
+
+} // namespace
+
+extern "C" {
+
+int finch_index_new(const finch_sketches *refs, const int *devices, uint32_t n_devices, finch_index **out) try {
+    if (!refs || !out || (n_devices && !devices)) return hfail(FH_ERR_INVALID, "null argument");
+    if (n_devices > DIST_MAX_ENTRIES) return hfail(FH_ERR_INVALID, "at most %u device entries (got %u)", DIST_MAX_ENTRIES, n_devices);
+    const std::vector<Sketch> &Rs = refs->v;
+    if (int rc = check_ascending(Rs, "reference")) return rc;
+    auto ix = std::make_unique<finch_index>();
+    ix->nr = (uint32_t)Rs.size();
+    for (const Sketch &s : Rs) ix->postings += s.hashes.size();
+    const uint64_t max_postings = std::min<uint64_t>(cfg_u64("index_max_postings", fh::INDEX_MAX_POSTINGS), fh::INDEX_MAX_POSTINGS);
+    if (ix->postings > max_postings)
+        return hfail(FH_ERR_UNSUPPORTED, "reference library: %llu postings (hashes of all %u sketches), an index holds at most %llu",
+                     (unsigned long long)ix->postings, ix->nr, (unsigned long long)max_postings);
+    if (ix->postings == 0) { // no reference has a hash: no pair shares one
+        *out = ix.release();
+        return FH_OK;
+    }
+    const int ndev = fh_device_count();
+    if (ndev <= 0) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
+    std::vector<int> devs = n_devices ? std::vector<int>(devices, devices + n_devices) : std::vector<int>{0};
+    for (int d : devs)
+        if (d < 0 || d >= ndev) return hfail(FH_ERR_NO_DEVICE, "no usable HIP device: device %d requested, %d visible", d, ndev);
+    struct RestoreDevice {
+        int prev = fh::matrix_current_device();
+        ~RestoreDevice() { fh::matrix_restore_device(prev); }
+    } restore_device;
+
+    DistCsr rc_;
+    rc_.build(Rs, false);
+    // queries per launch: 8 bytes per (query, reference) -- a counter and a place in the touched list
+    const uint64_t by_memory = std::min<uint64_t>(std::max<uint64_t>(1, INDEX_STATE_BYTES / (8ull * ix->nr)), INDEX_CHUNK_MAX);
+    ix->chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, cfg_u64("index_chunk_queries", by_memory)),
+                                             std::max<uint64_t>(1, (1ull << 31) / ix->nr)); // (a launch's list has a u32 cursor)
+    for (int d : devs) {
+        fh::IndexDevice *dev = nullptr;
+        uint64_t bytes = 0;
+        double ms = 0.;
+        if (int rc = fh::index_open(d, rc_.view(), ix->chunk, &dev, &bytes, &ms)) return hfail(rc, "%s", fh_last_error());
+        ix->entries.push_back(dev);
+        ix->device_bytes += bytes;
+        ix->build_ms += ms;
+    }
+    *out = ix.release();
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_index_search(const finch_index *cix, const finch_sketches *queries, double min_containment, uint32_t top_n,
+                       finch_search_result **out) try {
+    if (!cix || !queries || !out) return hfail(FH_ERR_INVALID, "null argument");
+    finch_index *ix = const_cast<finch_index *>(cix); // (the launch state is the index's; `mu` serialises its use)
+    if (min_containment <= 0.)
+        return hfail(FH_ERR_INVALID, "finch_index_search: min_containment %g: an index finds only the pairs that share a hash, and a threshold "
+                                     "<= 0 keeps every pair -- use finch_search", min_containment);
+    const std::vector<Sketch> &Qs = queries->v;
+    if (int rc = check_ascending(Qs, "query")) return rc;
+    const uint32_t nq = (uint32_t)Qs.size();
+    auto res = std::make_unique<finch_search_result>();
+    res->from_index = true;
+    res->offsets.assign((size_t)nq + 1, 0);
+    if (nq == 0 || ix->entries.empty()) {
+        *out = res.release();
+        return FH_OK;
+    }
+    std::lock_guard<std::mutex> one_search(ix->mu);
+    struct RestoreDevice { // (this thread runs the first device entry)
+        int prev = fh::matrix_current_device();
+        ~RestoreDevice() { fh::matrix_restore_device(prev); }
+    } restore_device;
+
+    DistCsr qc;
+    qc.build(Qs, false);
+    const uint32_t n_chunks = (nq + ix->chunk - 1) / ix->chunk;
+    const uint32_t n_entries = (uint32_t)std::min<size_t>(ix->entries.size(), n_chunks);
+    std::vector<std::vector<SearchCand>> found(n_chunks);
+
+    std::mutex err_mu;
+    int err_rc = FH_OK;
+    std::string err_msg;
+    std::atomic<bool> failed{false};
+    auto fail_with = [&](int rc, const std::string &msg) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (err_rc == FH_OK) err_rc = rc, err_msg = msg;
+        failed = true;
+    };
+    std::mutex stat_mu;
+
+    // one thread per device entry: chunks of queries e, e + n_entries, ...
+    fork_join(n_entries, [&](unsigned e) {
+        try {
+            std::vector<uint32_t> ent;
+            double ms_sum = 0.;
+            uint64_t touched = 0, copied = 0, launches = 0;
+            for (uint32_t k = e; k < n_chunks && !failed; k += n_entries) {
+                const uint32_t q0 = k * ix->chunk, q1 = (uint32_t)std::min<uint64_t>(nq, (uint64_t)q0 + ix->chunk);
+                ent.clear();
+                if (int rc = fh::index_search_chunk(ix->entries[e], qc.view(), q0, q1, min_containment, &ent, &touched, &ms_sum)) {
+                    fail_with(rc, fh_last_error());
+                    break;
+                }
+                static_assert(sizeof(SearchCand) == 5 * sizeof(uint32_t), "the device's entry");
+                found[k].resize(ent.size() / 5);
+                if (!ent.empty()) memcpy(found[k].data(), ent.data(), ent.size() * sizeof(uint32_t));
+                copied += found[k].size();
+                ++launches;
+            }
+            std::lock_guard<std::mutex> g(stat_mu);
+            res->kernel_ms += ms_sum;
+            res->launches += launches;
+            res->copied += copied;
+            res->touched += touched;
+        } catch (const std::bad_alloc &) {
+            fail_with(FH_ERR_CAPACITY, "out of host memory");
+        }
+    });
+    if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
+    if (int rc = search_finish(found, Qs, ix->nr, top_n, res.get())) return rc;
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_index_stats(const finch_index *ix, uint64_t *n_refs, uint64_t *postings, uint64_t *device_bytes, double *build_kernel_ms) try {
+    if (!ix) return hfail(FH_ERR_INVALID, "null argument");
+    if (n_refs) *n_refs = ix->nr;
+    if (postings) *postings = ix->postings;
+    if (device_bytes) *device_bytes = ix->device_bytes;
+    if (build_kernel_ms) *build_kernel_ms = ix->build_ms;
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_index_search_stats(const finch_search_result *r, uint64_t *pairs_touched) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    if (!r->from_index) return hfail(FH_ERR_INVALID, "finch_index_search_stats: the result was not made by finch_index_search");
+    if (pairs_touched) *pairs_touched = r->touched;
+    return FH_OK;
+} FINCH_CATCH
+
+void finch_index_free(finch_index *ix) { delete ix; }
 
 } // extern "C"
 

@@ -1,0 +1,29 @@
+// fh_index.h -- what fh_host.cpp's finch_index_new / finch_index_search (include/finch_host.h) ask of the device: an inverted index
+// over a library's hashes, and a search through it that counts only the (query, reference) pairs that share a hash (DESIGN.md
+// §3.14).  Defined in fh_index.hip; no HIP types here, fh_host.cpp is plain C++.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "fh_dist.h"
+
+namespace fh {
+
+// postings an index holds at most: the sort's tiles of 2048 pairs are counted in a u32 (fh_kernels.h: big_sort_pairs)
+constexpr uint64_t INDEX_MAX_POSTINGS = 0xffffffffull - 2047;
+
+struct IndexDevice;
+// uploads the library to `device`, forms and sorts its postings and allocates, zeroed, the counters of chunk_queries queries.
+// refs: at least one hash in all, no more than INDEX_MAX_POSTINGS.  *device_bytes = what the handle keeps allocated; *build_ms =
+// the build kernels' time (HIP events).  Synchronous.
+int index_open(int device, const DistSide &refs, uint32_t chunk_queries, IndexDevice **out, uint64_t *device_bytes, double *build_ms);
+// the queries [q0, q1) of `queries`, q1 - q0 <= chunk_queries: every pair (q, r) with c = |Q n R| > 0 is counted, given its
+// (c, i, j) and appended to *entries as 5 u32 (q, r, c, i, j) where c / j >= min_containment, in no order.
+// *touched is added the pairs with c > 0, *kernel_ms the kernels' time.  Synchronous; one call at a time per handle.
+int index_search_chunk(IndexDevice *d, const DistSide &queries, uint32_t q0, uint32_t q1, double min_containment,
+                       std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms);
+void index_close(IndexDevice *d);
+
+} // namespace fh

@@ -146,6 +146,10 @@ hipError_t launch_fill_tile_runs(uint32_t *list, uint32_t n_runs, uint32_t strid
 hipError_t launch_live_count_hist(const Entry *table, const uint32_t *live, const Ctl *ctl, uint32_t *hist, hipStream_t st);
 // fh_big.hip
 hipError_t big_sort_tmp_bytes(uint32_t M, size_t *bytes);
+// M (key, value) pairs ascending by key, in place, by eight stable 8-bit passes: equal keys keep their order.  keys_tmp / vals_tmp:
+// scratch of M entries each; tmp: big_sort_tmp_bytes(M) bytes.  M + 2047 must not wrap (the passes' tiles of 2048 pairs).
+hipError_t big_sort_pairs(void *tmp, size_t tmp_bytes, uint64_t *keys, uint64_t *keys_tmp, uint32_t *vals, uint32_t *vals_tmp,
+                          uint32_t M, hipStream_t st);
 hipError_t launch_big_prune(Entry *table, uint32_t *live, uint32_t *dead, uint32_t dead_cap, Ctl *ctl, uint32_t M,
                             uint32_t n_dead_now, uint32_t kind, uint64_t size, uint64_t max_hash, uint64_t *keys_a,
                             uint64_t *keys_b, uint32_t *slots_a, uint32_t *slots_b, void *tmp, size_t tmp_bytes,

@@ -142,6 +142,11 @@ _SYMS["finch_search_offsets"] = (C.c_int, [_P, _P])
 _SYMS["finch_search_copy"] = (C.c_int, [_P, _P, _P, _P])
 _SYMS["finch_search_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _SYMS["finch_search_free"] = (None, [_P])
+_SYMS["finch_index_new"] = (C.c_int, [_P, C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P)])
+_SYMS["finch_index_search"] = (C.c_int, [_P, _P, C.c_double, C.c_uint32, C.POINTER(_P)])
+_SYMS["finch_index_stats"] = (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)])
+_SYMS["finch_index_search_stats"] = (C.c_int, [_P, C.POINTER(C.c_uint64)])
+_SYMS["finch_index_free"] = (None, [_P])
 _SYMS["finch_gather_query"] = (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)])
 _SYMS["finch_gather"] = (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P)])
 _SYMS["finch_gather_len"] = (C.c_uint64, [_P])
@@ -627,6 +632,32 @@ def minmer_matrix(refs: Sketches, ir: int, sketches: Sketches, devices: Sequence
     return out
 
 
+def _search_rows(p, n_queries: int, stats: Optional[dict], from_index: bool = False):
+    """(offsets, rows) of a finch_search_result, which is freed here"""
+    L = lib()
+    try:
+        n = L.finch_search_len(p)
+        offsets = np.zeros(n_queries + 1, np.uint64)
+        _check(L.finch_search_offsets(p, offsets.ctypes.data))
+        qi, ri, d = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, _CDIST_DTYPE)
+        _check(L.finch_search_copy(p, qi.ctypes.data, ri.ctypes.data, d.ctypes.data))
+        if stats is not None:
+            ms, nl, nc = C.c_double(), C.c_uint64(), C.c_uint64()
+            _check(L.finch_search_stats(p, C.byref(ms), C.byref(nl), C.byref(nc)))
+            stats.update(kernel_ms=ms.value, launches=nl.value, candidates_copied=nc.value)
+            if from_index:
+                nt = C.c_uint64()
+                _check(L.finch_index_search_stats(p, C.byref(nt)))
+                stats.update(pairs_touched=nt.value)
+    finally:
+        L.finch_search_free(p)
+    rows = np.empty(n, DIST_DTYPE)
+    rows["query"], rows["reference"] = qi, ri
+    for f in _CDIST_DTYPE.names:
+        rows[f] = d[f]
+    return offsets, rows
+
+
 def search(queries: Sketches, refs: Sketches, min_containment: float = 0.0, top_n: int = 0, devices: Sequence[int] = (0,),
            stats: Optional[dict] = None):
     """per query the references with containment >= min_containment, best first (containment descending, then reference index
@@ -638,23 +669,7 @@ def search(queries: Sketches, refs: Sketches, min_containment: float = 0.0, top_
     darr = (C.c_int * len(devs))(*devs)
     p = _P()
     _check(L.finch_search(queries._p, refs._p, float(min_containment), int(top_n), darr, len(devs), C.byref(p)))
-    try:
-        n = L.finch_search_len(p)
-        offsets = np.zeros(len(queries) + 1, np.uint64)
-        _check(L.finch_search_offsets(p, offsets.ctypes.data))
-        qi, ri, d = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, _CDIST_DTYPE)
-        _check(L.finch_search_copy(p, qi.ctypes.data, ri.ctypes.data, d.ctypes.data))
-        if stats is not None:
-            ms, nl, nc = C.c_double(), C.c_uint64(), C.c_uint64()
-            _check(L.finch_search_stats(p, C.byref(ms), C.byref(nl), C.byref(nc)))
-            stats.update(kernel_ms=ms.value, launches=nl.value, candidates_copied=nc.value)
-    finally:
-        L.finch_search_free(p)
-    rows = np.empty(n, DIST_DTYPE)
-    rows["query"], rows["reference"] = qi, ri
-    for f in _CDIST_DTYPE.names:
-        rows[f] = d[f]
-    return offsets, rows
+    return _search_rows(p, len(queries), stats)
 
 
 def best_match(refs: Sketches, queries: Sketches, iq: int = 0, devices: Sequence[int] = (0,)) -> int:
@@ -672,6 +687,68 @@ def filter_to_matches(refs: Sketches, queries: Sketches, iq: int, threshold: flo
     >= threshold, in library order, as a collection of their own"""
     _, rows = search(select(queries, [iq]), refs, threshold, 0, devices)
     return select(refs, np.sort(rows["reference"]))
+
+
+SMALLEST_POSITIVE = 5e-324  # the smallest positive double: the threshold "any shared hash that counts"
+
+
+class LibraryIndex:
+    """an inverted index of the library `refs` on the GPU (finch_index_new): built once, searched many times.  For
+    min_containment > 0, .search(queries, min_containment, top_n) == search(queries, refs, min_containment, top_n), byte for
+    byte, at a cost that follows the pairs that share a hash instead of len(queries) x len(refs).  The index keeps its own copy
+    of what it needs on the device (`refs` itself only for filter_to_matches' result); a context manager, or .close()"""
+
+    def __init__(self, refs: Sketches, devices: Sequence[int] = (0,)):
+        devs = list(devices) if devices else [0]
+        darr = (C.c_int * len(devs))(*devs)
+        self._p, self.refs = _P(), refs
+        _check(lib().finch_index_new(refs._p, darr, len(devs), C.byref(self._p)))
+
+    def close(self) -> None:
+        if getattr(self, "_p", None) and lib is not None:  # module globals are gone at interpreter shutdown
+            lib().finch_index_free(self._p)
+        self._p = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _handle(self):
+        if not self._p:
+            raise FinchError("the index is closed")
+        return self._p
+
+    def stats(self) -> dict:
+        nr, np_, nb, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+        _check(lib().finch_index_stats(self._handle(), C.byref(nr), C.byref(np_), C.byref(nb), C.byref(ms)))
+        return dict(n_refs=nr.value, postings=np_.value, device_bytes=nb.value, build_kernel_ms=ms.value)
+
+    def search(self, queries: Sketches, min_containment: float, top_n: int = 0, stats: Optional[dict] = None):
+        """search()'s (offsets, rows) for a threshold above 0 (FinchError for one <= 0: the index cannot see the pairs that share
+        nothing); `stats` receives search()'s figures and pairs_touched, the pairs the device counted"""
+        p = _P()
+        _check(lib().finch_index_search(self._handle(), queries._p, float(min_containment), int(top_n), C.byref(p)))
+        return _search_rows(p, len(queries), stats, from_index=True)
+
+    def best_match(self, queries: Sketches, iq: int = 0) -> int:
+        """best_match(refs, queries, iq): a top-1 search at the smallest positive threshold; a query that shares nothing with
+        the library has no row and gets index 0, as the tie rule gives it there"""
+        if len(self.refs) == 0:
+            raise FinchError("best_match: the library has no sketches")
+        _, rows = self.search(select(queries, [iq]), SMALLEST_POSITIVE, 1)
+        return int(rows["reference"][0]) if len(rows) else 0
+
+    def filter_to_matches(self, queries: Sketches, iq: int, threshold: float) -> Sketches:
+        """filter_to_matches(refs, queries, iq, threshold); a threshold <= 0 keeps every reference and needs no device"""
+        if threshold <= 0:
+            self._handle()
+            return select(self.refs, np.arange(len(self.refs)))
+        _, rows = self.search(select(queries, [iq]), threshold, 0)
+        return select(self.refs, np.sort(rows["reference"]))
 
 
 # one row of finch_gather / finch_gather_query: finch_gather_row's nine integers and five doubles

@@ -89,8 +89,10 @@ const char *fh_last_error(void);
  * 13: fh_batch_new_wide and the rest of 12 unchanged, plus fh_batch_new_large (batches of Mash sketches of 3001..16384 hashes),
  * fh_batch_parked and the options batch_large_want, batch_large_files;
  * 14: fh_batch_new_wide and the rest of 13 unchanged, plus finch_gather, finch_gather_query and their accessors in finch_host.h
- * and the options gather_slice, gather_pos_bytes) */
-#define FH_ABI_VERSION 14
+ * and the options gather_slice, gather_pos_bytes;
+ * 15: fh_batch_new_wide and the rest of 14 unchanged, plus finch_index_new, finch_index_search, finch_index_stats,
+ * finch_index_search_stats and finch_index_free in finch_host.h and the options index_chunk_queries, index_max_postings) */
+#define FH_ABI_VERSION 15
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---

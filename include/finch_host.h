@@ -210,6 +210,43 @@ int finch_search_copy(const finch_search_result *r, uint32_t *query_idx, uint32_
 int finch_search_stats(const finch_search_result *r, double *kernel_ms, uint64_t *launches, uint64_t *candidates_copied);
 void finch_search_free(finch_search_result *r);
 
+/* index: finch_search through an inverted index of the library's hashes, built once per library.  finch_search counts every
+ * (query, reference) pair; a row with containment > 0 needs a shared hash, and an index enumerates exactly the pairs that have
+ * one.  THE CONTRACT: for min_containment > 0, finch_index_search(ix, queries, min_containment, top_n) returns byte for byte
+ * what finch_search(queries, refs, min_containment, top_n, ...) returns for the library the index was built from -- offsets,
+ * indices, rows, their order, the top_n cut.  The result is a finch_search_result: finch_search_len / _offsets / _copy / _stats /
+ * _free work on it unchanged (launches = the launches of chunks of queries; candidates_copied = exactly the pairs that passed the
+ * threshold, whatever top_n is: there is no device-side top-n here).
+ * finch_index_new: the index of `refs` on every entry of `devices` (NULL/0 = device 0, an entry may repeat, at most 16); each
+ *   entry holds the library's hashes as finch_search uploads them, per reference its length, last hash, scale and max hash, the
+ *   postings (hash, reference) sorted by hash -- equal hashes in ascending reference order, duplicates kept --, and the launch
+ *   state: per query of a launch one u32 counter and one u32 of touched list per reference (option index_chunk_queries: queries
+ *   per launch, read here; default: as many as keep that state within 256 MiB, at most 4096, at least 1).  The index is
+ *   self-contained: `refs` may be freed.  Decided before any device is touched: FH_ERR_INVALID for a null argument, more than
+ *   16 device entries, a reference whose hashes are not strictly ascending (named in finch_last_error, as finch_search names
+ *   it); FH_ERR_UNSUPPORTED for a library of more than 2^32 - 2048 postings (hashes of all its sketches; the message has both
+ *   numbers; option index_max_postings lowers the bound); a library without a single hash: FH_OK, no device needed.  Otherwise
+ *   FH_ERR_NO_DEVICE without a usable device.
+ * finch_index_search: queries are dealt over the index's device entries in chunks of index_chunk_queries.  Per launch the device
+ *   counts c = |Q n R| for the pairs that share a hash, completes (c, i, j) as finch_dist defines them and appends the pairs with
+ *   c / j >= min_containment to a list; the host finishes as finch_search does.  Decided before any device is touched:
+ *   FH_ERR_INVALID for a null argument, min_containment <= 0 (an index cannot enumerate pairs that share nothing: use
+ *   finch_search), a query whose hashes are not strictly ascending (named); zero queries, or an index of a library without a
+ *   hash: FH_OK, no rows, no device needed.  A NaN threshold selects nothing.  One search at a time runs on an index (others
+ *   wait).  FH_ERR_STATE for every search after one that failed between its two kernels: the index must be built again.
+ * finch_index_stats: references, postings, the device memory one build left allocated summed over the entries, the build
+ *   kernels' time (HIP events, summed); any pointer may be NULL.
+ * finch_index_search_stats: pairs_touched = the (query, reference) pairs the device counted, i.e. those with c > 0.
+ *   FH_ERR_INVALID, *pairs_touched untouched, for a result that finch_index_search did not make.
+ * The caller's current device is the same after each of these calls. */
+typedef struct finch_index finch_index;
+int finch_index_new(const finch_sketches *refs, const int *devices, uint32_t n_devices, finch_index **out);
+int finch_index_search(const finch_index *ix, const finch_sketches *queries, double min_containment, uint32_t top_n,
+                       finch_search_result **out);
+int finch_index_stats(const finch_index *ix, uint64_t *n_refs, uint64_t *postings, uint64_t *device_bytes, double *build_kernel_ms);
+int finch_index_search_stats(const finch_search_result *r, uint64_t *pairs_touched);
+void finch_index_free(finch_index *ix);
+
 /* gather: the greedy decomposition of a query sketch over a library -- what follows a search whose best-first list is full of
  * near-duplicates.  Not in the reference; the contract is this comment (tests/gather_model.py states it twice in Python).
  *   gather(Q, refs, min_overlap, max_rounds) for one query sketch Q and the library refs[0 .. R):
