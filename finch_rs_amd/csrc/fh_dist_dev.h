@@ -1,6 +1,7 @@
 // fh_dist_dev.h -- the device functions the pair kernels share (fh_dist.hip: k_dist_counts and the search's selection;
-// fh_index.hip: the index search): the pair's scale step, the branchless bound search and the containment's division.  One
-// statement of each, so that two kernels that must agree on a pair's (c, i, j) and on its containment cannot drift apart.
+// fh_index.hip: the index search and dist): the pair's scale step, the branchless bound search and the containment's and the
+// jaccard's divisions.  One statement of each, so that two kernels that must agree on a pair's (c, i, j) and on its containment
+// cannot drift apart.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,5 +41,13 @@ __device__ inline uint32_t count_below(const uint64_t *s, uint32_t n, uint32_t t
 // distance.rs:109-113 on the device.  No fast-math flag in this build: the division is IEEE's, the double finch_distance gets on
 // the host; c <= j, so it is never negative and two of them order as their bit patterns do.
 __device__ inline double containment_of(uint32_t c, uint32_t j) { return j ? (double)c / (double)j : 0.0; }
+
+// distance_from_counts' jaccard (distance.rs:120-125; old mode distance.rs:150-151 with i = total = |R|, c <= total) on the
+// device: the same u64 sums and the same IEEE division of the same two doubles, so the host's jaccard bit for bit.
+__device__ inline double jaccard_of(bool old_mode, uint32_t c, uint32_t i, uint32_t j) {
+    if (old_mode) return (double)c / (double)(c + 2 * ((uint64_t)i - c));
+    const uint64_t total = (uint64_t)i - c + j;
+    return total ? (double)c / (double)total : 1.0;
+}
 
 } // namespace fh

@@ -4721,6 +4721,8 @@ struct finch_dist_result {
     std::vector<std::string> qnames, rnames;
     double kernel_ms = 0.;
     uint64_t launches = 0;
+    bool from_index = false;          // finch_index_dist made it ...
+    uint64_t touched = 0, copied = 0; // ... from this many pairs with c > 0, of which this many crossed to the host
 };
 
 namespace {
@@ -5498,6 +5500,201 @@ int finch_index_search_stats(const finch_search_result *r, uint64_t *pairs_touch
 } FINCH_CATCH
 
 void finch_index_free(finch_index *ix) { delete ix; }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// finch dist through the index.  A bound below 1 keeps no pair with jaccard 0, and a pair of two non-empty sketches that shares
+// no hash has jaccard 0: what is left are the pairs the index enumerates, and the pairs with an empty side, which the host
+// makes itself.  The device's finish drops what a conservative jaccard bound drops; every entry that crosses goes through
+// finch_dist's own self-skip, distance_from_counts and `<= max_distance`, so the rows are finch_dist's.  DESIGN.md §3.15.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t INDEX_DIST_BUCKETS = 64; // the result's parts: ranges of references, each sorted on a thread of its own
+
+// the device's pre-filter for a query of this k: the jaccard at which the distance is max_distance, in real numbers
+// x / (2 - x) with x = exp(-k d), lowered by 2^-20 of itself -- some 2^30 ulps, against the few ulps of exp, log and the
+// divisions between this figure and distance_from_counts' test
+double index_dist_jmin(uint32_t kmer_length, double max_distance) {
+    const double x = std::exp(-(double)kmer_length * std::max(max_distance, 0.));
+    return x / (2. - x) * (1. - 0x1p-20);
+}
+
+// (c, i, j) of raw_counts for a pair with an empty side: nothing is walked, c = 0, and the scale step alone moves the cursor
+// of the other side to its first hash not below M
+void empty_side_counts(const Sketch &qs, const Sketch &rs, uint64_t &i, uint64_t &j) {
+    i = j = 0;
+    const double scale = pair_min_scale(qs, rs);
+    if (!(scale > 0.)) return;
+    const uint64_t m = scale_max_hash(scale);
+    auto below = [m](const std::vector<KmerCount> &h) {
+        return (uint64_t)(std::lower_bound(h.begin(), h.end(), m, [](const KmerCount &a, uint64_t x) { return a.hash < x; }) - h.begin());
+    };
+    i = below(qs.hashes), j = below(rs.hashes);
+}
+
+} // namespace
+
+extern "C" {
+
+int finch_index_dist(const finch_index *cix, const finch_sketches *refs, const finch_sketches *queries, int old_mode, double max_distance,
+                     finch_dist_result **out) try {
+    if (!cix || !refs || !out) return hfail(FH_ERR_INVALID, "null argument");
+    finch_index *ix = const_cast<finch_index *>(cix); // (the launch state is the index's; `mu` serialises its use)
+    if (max_distance >= 1.)
+        return hfail(FH_ERR_INVALID, "finch_index_dist: max_distance %g: an index finds only the pairs that share a hash, and a bound "
+                                     ">= 1 keeps every pair -- use finch_dist", max_distance);
+    const bool pairwise = queries == nullptr;
+    const std::vector<Sketch> &Rs = refs->v, &Qs = pairwise ? refs->v : queries->v;
+    uint64_t postings = 0;
+    for (const Sketch &s : Rs) postings += s.hashes.size();
+    if (Rs.size() != ix->nr || postings != ix->postings)
+        return hfail(FH_ERR_INVALID, "finch_index_dist: refs has %zu sketches and %llu hashes, the index was built from %u and %llu: "
+                                     "refs must be the library of the index", Rs.size(), (unsigned long long)postings, ix->nr,
+                     (unsigned long long)ix->postings);
+    if (!pairwise)
+        if (int rc = check_ascending(Qs, "query")) return rc;
+    if (int rc = check_ascending(Rs, "reference")) return rc;
+    if (old_mode) { // as finch_dist: old_distance refuses an empty query against a non-empty reference
+        bool empty_q = false;
+        for (const Sketch &s : Qs) empty_q = empty_q || s.hashes.empty();
+        if (empty_q && postings) return hfail(FH_ERR_INVALID, "old_distance: empty query sketch");
+    }
+    auto res = std::make_unique<finch_dist_result>();
+    res->from_index = true;
+    for (const Sketch &s : Qs) res->qnames.push_back(s.name);
+    for (const Sketch &s : Rs) res->rnames.push_back(s.name);
+    const uint32_t nq = (uint32_t)Qs.size(), nr = (uint32_t)Rs.size();
+    if (nq == 0 || nr == 0 || !(max_distance >= 0.)) { // (a NaN or negative bound keeps nothing: every distance is in [0, 1])
+        *out = res.release();
+        return FH_OK;
+    }
+    std::unordered_map<std::string, uint32_t> ids;
+    std::vector<uint32_t> qid(nq), rid(nr);
+    for (uint32_t q = 0; q < nq; ++q) qid[q] = ids.emplace(Qs[q].name, (uint32_t)ids.size()).first->second;
+    for (uint32_t r = 0; r < nr; ++r) rid[r] = ids.emplace(Rs[r].name, (uint32_t)ids.size()).first->second;
+
+    const uint32_t n_buckets = std::min(nr, INDEX_DIST_BUCKETS), per_bucket = (nr + n_buckets - 1) / n_buckets;
+    res->parts.resize(n_buckets);
+    // the pair's row from its counts, where it is not skipped and the exact test keeps it
+    auto keep = [&](std::vector<std::vector<finch_dist_result::Row>> &parts, uint32_t q, uint32_t r, uint64_t c, uint64_t i, uint64_t j) {
+        if (qid[q] == rid[r] && sketch_equal(Qs[q], Rs[r])) return false; // main.rs:324
+        finch_dist_result::Row row{q, r, {}};
+        distance_from_counts(old_mode != 0, c, old_mode ? Rs[r].hashes.size() : i, j, Qs[q].sketch_params.kmer_length, true, &row.d);
+        if (!(row.d.mash_distance <= max_distance)) return false;
+        parts[r / per_bucket].push_back(row);
+        return true;
+    };
+
+    // the pairs with an empty side.  Old mode: jaccard is 0 / 0 exactly where the reference is empty (an empty query has only
+    // empty references beside it).  New mode: total = 0 needs c = 0 and both cursors at 0, which a walk over two non-empty
+    // sketches never leaves.
+    for (uint32_t r = 0; r < nr; ++r)
+        if (Rs[r].hashes.empty())
+            for (uint32_t q = 0; q < nq; ++q) {
+                uint64_t i = 0, j = 0;
+                if (!old_mode) empty_side_counts(Qs[q], Rs[r], i, j);
+                keep(res->parts, q, r, 0, i, j);
+            }
+    if (!old_mode)
+        for (uint32_t q = 0; q < nq; ++q)
+            if (Qs[q].hashes.empty())
+                for (uint32_t r = 0; r < nr; ++r)
+                    if (!Rs[r].hashes.empty()) {
+                        uint64_t i = 0, j = 0;
+                        empty_side_counts(Qs[q], Rs[r], i, j);
+                        keep(res->parts, q, r, 0, i, j);
+                    }
+
+    if (!ix->entries.empty()) { // (a library without a hash: every row is made above)
+        std::lock_guard<std::mutex> one_call(ix->mu);
+        struct RestoreDevice { // (this thread runs the first device entry)
+            int prev = fh::matrix_current_device();
+            ~RestoreDevice() { fh::matrix_restore_device(prev); }
+        } restore_device;
+
+        DistCsr qc;
+        if (!pairwise) qc.build(Qs, false); // (the flags of the new mode, as the index has the library's; old mode reads none)
+        const fh::DistSide qview = qc.view();
+        std::vector<double> jmin(nq);
+        for (uint32_t q = 0; q < nq; ++q) jmin[q] = index_dist_jmin(Qs[q].sketch_params.kmer_length, max_distance);
+        const uint32_t n_chunks = (nq + ix->chunk - 1) / ix->chunk;
+        const uint32_t n_entries = (uint32_t)std::min<size_t>(ix->entries.size(), n_chunks);
+
+        std::mutex err_mu;
+        int err_rc = FH_OK;
+        std::string err_msg;
+        std::atomic<bool> failed{false};
+        auto fail_with = [&](int rc, const std::string &msg) {
+            std::lock_guard<std::mutex> g(err_mu);
+            if (err_rc == FH_OK) err_rc = rc, err_msg = msg;
+            failed = true;
+        };
+        std::mutex stat_mu;
+
+        // one thread per device entry: chunks of queries e, e + n_entries, ...
+        fork_join(n_entries, [&](unsigned e) {
+            try {
+                std::vector<uint32_t> ent;
+                std::vector<std::vector<finch_dist_result::Row>> mine(n_buckets);
+                double ms_sum = 0.;
+                uint64_t touched = 0, copied = 0, launches = 0;
+                for (uint32_t k = e; k < n_chunks && !failed; k += n_entries) {
+                    const uint32_t q0 = k * ix->chunk, q1 = (uint32_t)std::min<uint64_t>(nq, (uint64_t)q0 + ix->chunk);
+                    ent.clear();
+                    if (int rc = fh::index_dist_chunk(ix->entries[e], pairwise ? nullptr : &qview, q0, q1, old_mode != 0, jmin.data() + q0, &ent,
+                                                      &touched, &ms_sum)) {
+                        fail_with(rc, fh_last_error());
+                        break;
+                    }
+                    ++launches;
+                    copied += ent.size() / 5;
+                    for (size_t t = 0; t + 5 <= ent.size(); t += 5) {
+                        const uint32_t *x = ent.data() + t;
+                        if (x[0] < q0 || x[0] >= q1 || x[1] >= nr) {
+                            fail_with(FH_ERR_STATE, "index dist: an entry names pair (" + std::to_string(x[0]) + ", " + std::to_string(x[1]) + ")");
+                            break;
+                        }
+                        keep(mine, x[0], x[1], x[2], x[3], x[4]);
+                    }
+                }
+                std::lock_guard<std::mutex> g(stat_mu);
+                res->kernel_ms += ms_sum;
+                res->launches += launches;
+                res->copied += copied;
+                res->touched += touched;
+                for (uint32_t b = 0; b < n_buckets; ++b) {
+                    std::vector<finch_dist_result::Row> &to = res->parts[b];
+                    if (to.empty()) to.swap(mine[b]);
+                    else to.insert(to.end(), mine[b].begin(), mine[b].end());
+                }
+            } catch (const std::bad_alloc &) {
+                fail_with(FH_ERR_CAPACITY, "out of host memory");
+            }
+        });
+        if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
+    }
+    // reference-major, queries ascending inside a reference: a pair has one row at most
+    const unsigned T = std::min(n_buckets, DIST_MAX_ENTRIES);
+    fork_join(T, [&](unsigned t) {
+        for (uint32_t b = t; b < n_buckets; b += T)
+            std::sort(res->parts[b].begin(), res->parts[b].end(), [](const finch_dist_result::Row &x, const finch_dist_result::Row &y) {
+                return x.r != y.r ? x.r < y.r : x.q < y.q;
+            });
+    });
+    for (const auto &p : res->parts) res->n += p.size();
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_index_dist_stats(const finch_dist_result *r, uint64_t *pairs_touched, uint64_t *pairs_copied) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    if (!r->from_index) return hfail(FH_ERR_INVALID, "finch_index_dist_stats: the result was not made by finch_index_dist");
+    if (pairs_touched) *pairs_touched = r->touched;
+    if (pairs_copied) *pairs_copied = r->copied;
+    return FH_OK;
+} FINCH_CATCH
 
 } // extern "C"
 

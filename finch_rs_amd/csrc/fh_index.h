@@ -24,6 +24,13 @@ int index_open(int device, const DistSide &refs, uint32_t chunk_queries, IndexDe
 // *touched is added the pairs with c > 0, *kernel_ms the kernels' time.  Synchronous; one call at a time per handle.
 int index_search_chunk(IndexDevice *d, const DistSide &queries, uint32_t q0, uint32_t q1, double min_containment,
                        std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms);
+// finch_index_dist's chunk: the queries [q0, q1) of `queries`, or -- queries == nullptr, pairwise -- the library's own sketches
+// q0 .. q1, read from the index's copy: no hashes cross.  Counted as above; a touched pair's jaccard is distance_from_counts'
+// (new mode from (c, i, j); old_mode: c / (c + 2 (|R| - c))), and the pair is appended as (q, r, c, i, j) -- old mode: i = |R|,
+// j = 0 -- where jaccard >= jmin[q - q0] (q1 - q0 doubles: a conservative bound; the caller decides).  The counters are zero
+// again afterwards, as after a search.
+int index_dist_chunk(IndexDevice *d, const DistSide *queries, uint32_t q0, uint32_t q1, bool old_mode, const double *jmin,
+                     std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms);
 void index_close(IndexDevice *d);
 
 } // namespace fh

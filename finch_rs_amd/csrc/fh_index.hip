@@ -12,6 +12,9 @@
 //   * k_index_finish: per touched pair c is read and 0 stored back -- the counters are clean for the next launch without a
 //     memset of the dense array --, i and j follow in closed form from each side's last hash and the pair's M (DESIGN.md §3.7:
 //     two to four bound searches), and the pair is appended to the chunk's list where c / j >= min_containment.
+//   * k_index_dist_finish: finch_index_dist's finish after the same count: c, and 0 back; (i, j) as above, or
+//     old mode's total = |R|; the pair is appended where its jaccard reaches the host's conservative bound for the query.  The
+//     queries may be the library's own sketches (pairwise), read from the CSR the index holds.
 // The order in which atomics land decides only where an entry sits in a list; the host sorts.
 #include <hip/hip_runtime.h>
 
@@ -170,6 +173,57 @@ __global__ void __launch_bounds__(THREADS) k_index_finish(IndexArgs a) {
     }
 }
 
+// grid: x = query of the chunk.  finch_index_dist's finish: per touched pair c, and 0 back, as above; new mode completes (i, j)
+// as k_index_finish does, old mode has total = |R| and no bound search (old_distance: c = |Q n R| for ascending hashes).  The
+// pair's jaccard is the division distance_from_counts makes on the host; the entry (q, r, c, i, j) -- old mode: i = |R|, j = 0 --
+// is appended where it reaches jmin[q], the host's conservative bound for the query's k and the call's max_distance: the host
+// makes the decision, with its own log.
+__global__ void __launch_bounds__(THREADS) k_index_dist_finish(IndexArgs a, const double *jmin, uint32_t old_mode) {
+    const uint32_t qi = blockIdx.x, n = a.tcount[qi];
+    const uint32_t nqh = (uint32_t)(a.qoff[qi + 1] - a.qoff[qi]);
+    const uint64_t *Q = a.qh + (a.qoff[qi] - a.qbase);
+    const uint32_t qtop = top_of(nqh);
+    const uint64_t max_q = nqh ? Q[nqh - 1] : 0;
+    const double jm = jmin[qi];
+    uint32_t *cnt = a.cnt + (uint64_t)qi * a.nr;
+    const uint32_t *touched = a.touched + (uint64_t)qi * a.nr;
+    for (uint32_t base = 0; base < n; base += THREADS) { // (whole waves go round: the ballot sees every lane)
+        const uint32_t t = base + threadIdx.x;
+        uint32_t r = 0, c = 0, i = 0, j = 0;
+        bool pass = false;
+        if (t < n) {
+            r = touched[t];
+            c = cnt[r];
+            cnt[r] = 0;
+            const uint32_t nrh = a.rlen[r];
+            if (old_mode) {
+                i = nrh;
+            } else if (nqh && nrh) {
+                const uint64_t *R = a.rh + a.roff[r];
+                const uint32_t rtop = top_of(nrh);
+                i = count_below<true>(Q, nqh, qtop, a.rlast[r]);
+                j = count_below<true>(R, nrh, rtop, max_q);
+                uint64_t m = 0;
+                if (pair_max_hash(a, qi, r, m)) {
+                    i = max(i, count_below<false>(Q, nqh, qtop, m));
+                    j = max(j, count_below<false>(R, nrh, rtop, m));
+                }
+            }
+            pass = jaccard_of(old_mode != 0, c, i, j) >= jm;
+        }
+        const uint64_t mask = __ballot(pass);
+        if (!mask) continue;
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        uint32_t first = 0;
+        if (pass && rank == 0) first = atomicAdd(a.cursor, (uint32_t)__popcll(mask));
+        first = __shfl(first, __ffsll((unsigned long long)mask) - 1, 64);
+        if (pass && first + rank < a.sel_cap) { // (the host sized the list to the chunk's touched pairs)
+            uint32_t *e = a.sel + (uint64_t)(first + rank) * 5;
+            e[0] = a.q0 + qi, e[1] = r, e[2] = c, e[3] = i, e[4] = j;
+        }
+    }
+}
+
 } // namespace
 
 namespace fh {
@@ -184,6 +238,7 @@ struct IndexDevice {
     uint32_t *cnt = nullptr, *touched = nullptr, *tcount = nullptr, *cursor = nullptr, *sel = nullptr;
     uint64_t sel_cap = 0;         // entries that sel holds
     uint32_t *back_h = nullptr;   // pinned: chunk touched-list lengths, then the cursor
+    double *jmin = nullptr;       // finch_index_dist: the chunk's jaccard bounds, one per query (allocated by its first chunk)
     hipEvent_t ev[4] = {};
     bool dirty = false;           // a launch failed between the count and the finish: the counters are not known to be zero
 };
@@ -198,6 +253,7 @@ void index_close(IndexDevice *d) {
             if (p) (void)hipFree(p);
         for (uint32_t *p : {d->cnt, d->touched, d->tcount, d->cursor, d->sel})
             if (p) (void)hipFree(p);
+        if (d->jmin) (void)hipFree(d->jmin);
         if (d->back_h) (void)hipHostFree(d->back_h);
         for (hipEvent_t e : d->ev)
             if (e) (void)hipEventDestroy(e);
@@ -303,31 +359,45 @@ static int grow(void **p, size_t *have, size_t bytes) {
     return FH_OK;
 }
 
-static int search_chunk(IndexDevice *d, const DistSide &q, uint32_t q0, uint32_t q1, double min_containment, std::vector<uint32_t> *entries,
-                        uint64_t *touched, double *kernel_ms) {
+// one chunk of either route.  q = nullptr: the queries are the library's own sketches q0 .. q1 (pairwise), read where the index
+// keeps them.  jmin = nullptr: the search's finish with min_containment; else finch_index_dist's with the chunk's bounds.
+static int run_chunk(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q1, double min_containment, const double *jmin, bool old_mode,
+                     std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms) {
     const uint32_t n = q1 - q0;
-    const uint64_t h0 = q.offsets[q0], nh = q.offsets[q1] - h0;
     IHIP_TRY(hipSetDevice(d->device));
-    if (int rc = grow(&d->qry[0], &d->qry_hashes, nh * sizeof(uint64_t))) return rc;
-    if (!d->qry[1]) { // the per-query arrays: a chunk never has more than d->chunk queries
-        IHIP_TRY(api_dev_malloc(&d->qry[1], ((size_t)d->chunk + 1) * sizeof(uint64_t)));
-        IHIP_TRY(api_dev_malloc(&d->qry[2], (size_t)d->chunk * sizeof(uint64_t)));
-        IHIP_TRY(api_dev_malloc(&d->qry[3], (size_t)d->chunk * sizeof(uint32_t)));
-        IHIP_TRY(api_dev_malloc(&d->qry[4], (size_t)d->chunk * sizeof(double)));
+    uint64_t h0 = 0;
+    if (q) {
+        h0 = q->offsets[q0];
+        const uint64_t nh = q->offsets[q1] - h0;
+        if (int rc = grow(&d->qry[0], &d->qry_hashes, nh * sizeof(uint64_t))) return rc;
+        if (!d->qry[1]) { // the per-query arrays: a chunk never has more than d->chunk queries
+            IHIP_TRY(api_dev_malloc(&d->qry[1], ((size_t)d->chunk + 1) * sizeof(uint64_t)));
+            IHIP_TRY(api_dev_malloc(&d->qry[2], (size_t)d->chunk * sizeof(uint64_t)));
+            IHIP_TRY(api_dev_malloc(&d->qry[3], (size_t)d->chunk * sizeof(uint32_t)));
+            IHIP_TRY(api_dev_malloc(&d->qry[4], (size_t)d->chunk * sizeof(double)));
+        }
+        if (nh) IHIP_TRY(hipMemcpy(d->qry[0], q->hashes + h0, nh * sizeof(uint64_t), hipMemcpyHostToDevice));
+        IHIP_TRY(hipMemcpy(d->qry[1], q->offsets + q0, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+        IHIP_TRY(hipMemcpy(d->qry[2], q->max_hash + q0, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
+        IHIP_TRY(hipMemcpy(d->qry[3], q->flags + q0, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        IHIP_TRY(hipMemcpy(d->qry[4], q->scale + q0, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (nh) IHIP_TRY(hipMemcpy(d->qry[0], q.hashes + h0, nh * sizeof(uint64_t), hipMemcpyHostToDevice));
-    IHIP_TRY(hipMemcpy(d->qry[1], q.offsets + q0, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    IHIP_TRY(hipMemcpy(d->qry[2], q.max_hash + q0, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
-    IHIP_TRY(hipMemcpy(d->qry[3], q.flags + q0, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    IHIP_TRY(hipMemcpy(d->qry[4], q.scale + q0, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    if (jmin) {
+        if (!d->jmin) IHIP_TRY(api_dev_malloc((void **)&d->jmin, (size_t)d->chunk * sizeof(double)));
+        IHIP_TRY(hipMemcpy(d->jmin, jmin, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    }
 
     IndexArgs a;
     a.rh = (const uint64_t *)d->lib[0], a.roff = (const uint64_t *)d->lib[1], a.rlast = (const uint64_t *)d->lib[2];
     a.rmax = (const uint64_t *)d->lib[3], a.rlen = (const uint32_t *)d->lib[4], a.rflag = (const uint32_t *)d->lib[5];
     a.rscale = (const double *)d->lib[6], a.keys = (const uint64_t *)d->lib[7], a.vals = (const uint32_t *)d->lib[8];
     a.n_post = d->n_post, a.post_top = 1u << (31 - __builtin_clz(d->n_post)), a.nr = d->nr;
-    a.qh = (const uint64_t *)d->qry[0], a.qoff = (const uint64_t *)d->qry[1], a.qmax = (const uint64_t *)d->qry[2];
-    a.qflag = (const uint32_t *)d->qry[3], a.qscale = (const double *)d->qry[4];
+    if (q) {
+        a.qh = (const uint64_t *)d->qry[0], a.qoff = (const uint64_t *)d->qry[1], a.qmax = (const uint64_t *)d->qry[2];
+        a.qflag = (const uint32_t *)d->qry[3], a.qscale = (const double *)d->qry[4];
+    } else { // the library's own CSR: hashes from 0 on, the per-sketch arrays from sketch q0 on (roff has nr + 1 entries)
+        a.qh = a.rh, a.qoff = a.roff + q0, a.qmax = a.rmax + q0, a.qflag = a.rflag + q0, a.qscale = a.rscale + q0;
+    }
     a.qbase = h0, a.q0 = q0;
     a.cnt = d->cnt, a.touched = d->touched, a.tcount = d->tcount;
     a.min_c = min_containment;
@@ -364,7 +434,8 @@ static int search_chunk(IndexDevice *d, const DistSide &q, uint32_t q0, uint32_t
 
     IHIP_TRY(hipMemsetAsync(d->cursor, 0, sizeof(uint32_t), d->stream));
     IHIP_TRY(hipEventRecord(d->ev[2], d->stream));
-    hipLaunchKernelGGL(k_index_finish, dim3(n), dim3(THREADS), 0, d->stream, a);
+    if (jmin) hipLaunchKernelGGL(k_index_dist_finish, dim3(n), dim3(THREADS), 0, d->stream, a, (const double *)d->jmin, old_mode ? 1u : 0u);
+    else hipLaunchKernelGGL(k_index_finish, dim3(n), dim3(THREADS), 0, d->stream, a);
     IHIP_TRY(hipGetLastError());
     IHIP_TRY(hipEventRecord(d->ev[3], d->stream));
     IHIP_TRY(hipMemcpyAsync(d->back_h + d->chunk, d->cursor, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
@@ -385,7 +456,15 @@ int index_search_chunk(IndexDevice *d, const DistSide &queries, uint32_t q0, uin
     if (q1 <= q0 || q1 > queries.n || q1 - q0 > d->chunk)
         return api_fail(FH_ERR_INVALID, "index_search_chunk: queries %u..%u of %u, %u per launch", q0, q1, queries.n, d->chunk);
     if (d->dirty) return api_fail(FH_ERR_STATE, "index search: an earlier search on this index failed between its two kernels; build the index again");
-    return search_chunk(d, queries, q0, q1, min_containment, entries, touched, kernel_ms);
+    return run_chunk(d, &queries, q0, q1, min_containment, nullptr, false, entries, touched, kernel_ms);
+}
+
+int index_dist_chunk(IndexDevice *d, const DistSide *queries, uint32_t q0, uint32_t q1, bool old_mode, const double *jmin,
+                     std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms) {
+    if (!jmin || q1 <= q0 || q1 > (queries ? queries->n : d->nr) || q1 - q0 > d->chunk)
+        return api_fail(FH_ERR_INVALID, "index_dist_chunk: queries %u..%u of %u, %u per launch", q0, q1, queries ? queries->n : d->nr, d->chunk);
+    if (d->dirty) return api_fail(FH_ERR_STATE, "index dist: an earlier call on this index failed between its two kernels; build the index again");
+    return run_chunk(d, queries, q0, q1, 0., jmin, old_mode, entries, touched, kernel_ms);
 }
 
 } // namespace fh

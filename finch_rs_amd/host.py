@@ -147,6 +147,8 @@ _SYMS["finch_index_search"] = (C.c_int, [_P, _P, C.c_double, C.c_uint32, C.POINT
 _SYMS["finch_index_stats"] = (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)])
 _SYMS["finch_index_search_stats"] = (C.c_int, [_P, C.POINTER(C.c_uint64)])
 _SYMS["finch_index_free"] = (None, [_P])
+_SYMS["finch_index_dist"] = (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.POINTER(_P)])
+_SYMS["finch_index_dist_stats"] = (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _SYMS["finch_gather_query"] = (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)])
 _SYMS["finch_gather"] = (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P)])
 _SYMS["finch_gather_len"] = (C.c_uint64, [_P])
@@ -569,12 +571,9 @@ def _dist_result(queries: Sketches, refs: Sketches, max_distance: float, old_mod
     return out
 
 
-def dist(queries: Sketches, refs: Sketches, max_distance: float = 1.0, old_mode: bool = False, devices: Sequence[int] = (0,),
-         stats: Optional[dict] = None) -> np.ndarray:
-    """calc_sketch_distances (cli/src/main.rs:315-333) on the GPU: one DIST_DTYPE row per (query, reference) pair kept, in the
-    reference's order (for each reference, for each query); `stats`, if given, receives the kernels' time and launches"""
+def _dist_rows(p, stats: Optional[dict], from_index: bool = False) -> np.ndarray:
+    """the rows of a finch_dist_result, which is freed"""
     L = lib()
-    p = _dist_result(queries, refs, max_distance, old_mode, devices)
     try:
         n = L.finch_dist_len(p)
         qi, ri, d = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, _CDIST_DTYPE)
@@ -583,6 +582,10 @@ def dist(queries: Sketches, refs: Sketches, max_distance: float = 1.0, old_mode:
             ms, nl = C.c_double(), C.c_uint64()
             _check(L.finch_dist_stats(p, C.byref(ms), C.byref(nl)))
             stats.update(kernel_ms=ms.value, launches=nl.value)
+            if from_index:
+                nt, nc = C.c_uint64(), C.c_uint64()
+                _check(L.finch_index_dist_stats(p, C.byref(nt), C.byref(nc)))
+                stats.update(pairs_touched=nt.value, pairs_copied=nc.value)
     finally:
         L.finch_dist_free(p)
     rows = np.empty(n, DIST_DTYPE)
@@ -592,11 +595,9 @@ def dist(queries: Sketches, refs: Sketches, max_distance: float = 1.0, old_mode:
     return rows
 
 
-def dist_json(queries: Sketches, refs: Sketches, max_distance: float = 1.0, old_mode: bool = False,
-              devices: Sequence[int] = (0,)) -> str:
-    """the same rows as serde_json::to_writer(&Vec<SketchDistance>) writes them (main.rs:117-121)"""
+def _dist_text(p) -> str:
+    """the JSON text of a finch_dist_result, which is freed"""
     L = lib()
-    p = _dist_result(queries, refs, max_distance, old_mode, devices)
     try:
         s, n = _P(), C.c_uint64()
         _check(L.finch_dist_to_json(p, C.byref(s), C.byref(n)))
@@ -606,6 +607,19 @@ def dist_json(queries: Sketches, refs: Sketches, max_distance: float = 1.0, old_
             L.finch_free_string(s)
     finally:
         L.finch_dist_free(p)
+
+
+def dist(queries: Sketches, refs: Sketches, max_distance: float = 1.0, old_mode: bool = False, devices: Sequence[int] = (0,),
+         stats: Optional[dict] = None) -> np.ndarray:
+    """calc_sketch_distances (cli/src/main.rs:315-333) on the GPU: one DIST_DTYPE row per (query, reference) pair kept, in the
+    reference's order (for each reference, for each query); `stats`, if given, receives the kernels' time and launches"""
+    return _dist_rows(_dist_result(queries, refs, max_distance, old_mode, devices), stats)
+
+
+def dist_json(queries: Sketches, refs: Sketches, max_distance: float = 1.0, old_mode: bool = False,
+              devices: Sequence[int] = (0,)) -> str:
+    """the same rows as serde_json::to_writer(&Vec<SketchDistance>) writes them (main.rs:117-121)"""
+    return _dist_text(_dist_result(queries, refs, max_distance, old_mode, devices))
 
 
 def select(sketches: Sketches, idx: Sequence[int]) -> Sketches:
@@ -696,7 +710,8 @@ class LibraryIndex:
     """an inverted index of the library `refs` on the GPU (finch_index_new): built once, searched many times.  For
     min_containment > 0, .search(queries, min_containment, top_n) == search(queries, refs, min_containment, top_n), byte for
     byte, at a cost that follows the pairs that share a hash instead of len(queries) x len(refs).  The index keeps its own copy
-    of what it needs on the device (`refs` itself only for filter_to_matches' result); a context manager, or .close()"""
+    of what it needs on the device (`refs` itself for filter_to_matches' result and for dist's rows); a context manager, or
+    .close()"""
 
     def __init__(self, refs: Sketches, devices: Sequence[int] = (0,)):
         devs = list(devices) if devices else [0]
@@ -733,6 +748,24 @@ class LibraryIndex:
         p = _P()
         _check(lib().finch_index_search(self._handle(), queries._p, float(min_containment), int(top_n), C.byref(p)))
         return _search_rows(p, len(queries), stats, from_index=True)
+
+    def _dist_result(self, queries: Optional[Sketches], max_distance: float, old_mode: bool):
+        p = _P()
+        _check(lib().finch_index_dist(self._handle(), self.refs._p, queries._p if queries is not None else None, int(old_mode),
+                                      float(max_distance), C.byref(p)))
+        return p
+
+    def dist(self, queries: Optional[Sketches] = None, max_distance: float = 0.1, old_mode: bool = False,
+             stats: Optional[dict] = None) -> np.ndarray:
+        """dist(queries, refs, max_distance, old_mode)'s rows, byte for byte, for a bound below 1 (FinchError for one >= 1: the
+        index cannot see the pairs that share nothing); queries=None is pairwise, dist(refs, refs, ...), read from the index's own
+        copy of the library.  `stats` receives dist()'s figures, pairs_touched (the pairs the device counted) and pairs_copied
+        (those that passed the device's pre-filter)"""
+        return _dist_rows(self._dist_result(queries, max_distance, old_mode), stats, from_index=True)
+
+    def dist_json(self, queries: Optional[Sketches] = None, max_distance: float = 0.1, old_mode: bool = False) -> str:
+        """dist_json(queries, refs, max_distance, old_mode)'s text for a bound below 1"""
+        return _dist_text(self._dist_result(queries, max_distance, old_mode))
 
     def best_match(self, queries: Sketches, iq: int = 0) -> int:
         """best_match(refs, queries, iq): a top-1 search at the smallest positive threshold; a query that shares nothing with

@@ -91,8 +91,9 @@ const char *fh_last_error(void);
  * 14: fh_batch_new_wide and the rest of 13 unchanged, plus finch_gather, finch_gather_query and their accessors in finch_host.h
  * and the options gather_slice, gather_pos_bytes;
  * 15: fh_batch_new_wide and the rest of 14 unchanged, plus finch_index_new, finch_index_search, finch_index_stats,
- * finch_index_search_stats and finch_index_free in finch_host.h and the options index_chunk_queries, index_max_postings) */
-#define FH_ABI_VERSION 15
+ * finch_index_search_stats and finch_index_free in finch_host.h and the options index_chunk_queries, index_max_postings;
+ * 16: fh_batch_new_wide and the rest of 15 unchanged, plus finch_index_dist and finch_index_dist_stats in finch_host.h) */
+#define FH_ABI_VERSION 16
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---

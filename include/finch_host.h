@@ -247,6 +247,39 @@ int finch_index_stats(const finch_index *ix, uint64_t *n_refs, uint64_t *posting
 int finch_index_search_stats(const finch_search_result *r, uint64_t *pairs_touched);
 void finch_index_free(finch_index *ix);
 
+/* finch dist through the index: `finch dist -d D` over a library, pairwise included, at a cost that follows the pairs that share
+ * a hash.  THE CONTRACT: for max_distance < 1, finch_index_dist(ix, refs, queries, old_mode, max_distance) returns byte for byte
+ * what finch_dist(queries, refs, old_mode, max_distance, ...) returns -- queries == NULL (pairwise): what finch_dist(refs, refs,
+ * ...) returns --: the rows, the query and reference indices, the reference-major order with queries ascending inside a
+ * reference, and the self-skip (equal names and Sketch::eq, decided by the function finch_dist uses).  The result is a
+ * finch_dist_result: finch_dist_len / _copy / _to_json / _stats / _free work on it unchanged (kernel_ms: the count and finish
+ * kernels; launches: the launches of chunks of queries).
+ *   Why max_distance < 1: two non-empty sketches that share no hash have jaccard 0 and mash_distance exactly 1, so a bound below
+ *   1 drops them, and the pairs that share a hash are what the index enumerates.  A bound >= 1 (+inf included) keeps every pair:
+ *   FH_ERR_INVALID, use finch_dist.  NaN or max_distance < 0: FH_OK, no rows (-0.0 is not < 0: it keeps the distance-0 rows).
+ *   Pairs that share no hash and are kept all the same have total_hashes 0, jaccard 1 (old mode: 0 / 0) and distance 0, and at
+ *   least one empty side.  New mode: both sides empty, or one side empty and the other with no hash below the pair's max hash (a
+ *   Mash sketch beside it: no max hash, so always).  Old mode: every pair whose reference is empty.  The host makes these pairs
+ *   itself -- every empty sketch of either side against all sketches of the other, c = 0 and the cursors by bound searches, then
+ *   the same distance function and the same `<= max_distance` --: O(empty x other side), nothing for a library without empty
+ *   sketches.  Every pair of two non-empty sketches goes through the index.
+ *   `refs` MUST be the library `ix` was built from: the index keeps no sketches, and names, kmer_length, the self-skip and the
+ *   rows come from `refs`.  The call refuses (FH_ERR_INVALID) a `refs` whose sketch count or total hash count differs from the
+ *   index's; the rest of that promise is the caller's.
+ *   The device completes each touched pair's counts (old mode: total = |R|) and its jaccard -- the host's division, bit for bit
+ *   -- and sends (q, r, c, i, j) where jaccard >= jmin[q] = x / (2 - x) * (1 - 2^-20), x = exp(-kmer_length(q) * max_distance):
+ *   a conservative pre-filter; the host decides each entry with distance_from_counts.  Pairwise, the queries are read from the
+ *   index's own copy of the library: 8 bytes per query cross to the device.
+ *   Decided before any device is touched: FH_ERR_INVALID for a null ix, refs or out, max_distance >= 1, the refs mismatch, a
+ *   sketch whose hashes are not strictly ascending (named, as finch_dist names it), old mode with an empty query next to a
+ *   non-empty reference (as finch_dist); zero queries: no rows; an index of a library without a hash: every row is host-made,
+ *   no device needed.  One call at a time runs on an index, searches included.  FH_ERR_STATE as for finch_index_search.
+ * finch_index_dist_stats: pairs_touched = the pairs the device counted (c > 0), pairs_copied = the entries that passed the
+ *   pre-filter and crossed; either pointer may be NULL.  FH_ERR_INVALID, outputs untouched, for a result finch_dist made. */
+int finch_index_dist(const finch_index *ix, const finch_sketches *refs, const finch_sketches *queries /* NULL = pairwise */,
+                     int old_mode, double max_distance, finch_dist_result **out);
+int finch_index_dist_stats(const finch_dist_result *r, uint64_t *pairs_touched, uint64_t *pairs_copied);
+
 /* gather: the greedy decomposition of a query sketch over a library -- what follows a search whose best-first list is full of
  * near-duplicates.  Not in the reference; the contract is this comment (tests/gather_model.py states it twice in Python).
  *   gather(Q, refs, min_overlap, max_rounds) for one query sketch Q and the library refs[0 .. R):
