@@ -5709,6 +5709,8 @@ struct finch_gather_result {
     std::vector<finch_gather_row> rows;
     double kernel_ms = 0.;
     uint64_t launches = 0, candidates = 0, copied = 0;
+    bool from_index = false; // made by finch_index_gather: `touched` = the pairs its device counted
+    uint64_t touched = 0;
 };
 
 namespace {
@@ -5782,6 +5784,53 @@ void gather_on_host(const std::vector<Sketch> &Rs, const Sketch &Q, uint32_t iq,
 
 constexpr uint64_t GATHER_POS_BYTES = 1ull << 30; // a chunk's position arrays: a design choice, not a measurement
 
+// what finch_gather and finch_index_gather do with the records a launch left for the queries [q0, q1) (the device's numbering):
+// each is checked against the candidates -- query q's are cands[first[q - first_q] .. first[q - first_q + 1]), by reference -- and
+// becomes the row of its round in rows_of[caller's index] (mine: the device's numbering -> the caller's; nullptr: the same).
+// A message where a record is not what the candidates allow.
+std::string gather_place_records(const std::vector<fh::GatherRecord> &recs, uint32_t q0, uint32_t q1, const fh::GatherCand *cands,
+                                 const uint64_t *first, uint32_t first_q, const uint32_t *mine,
+                                 std::vector<std::vector<finch_gather_row>> &rows_of) {
+    for (const fh::GatherRecord &x : recs) {
+        const bool in = x.q >= q0 && x.q < q1;
+        const uint64_t nc = in ? first[x.q - first_q + 1] - first[x.q - first_q] : 0;
+        if (x.round >= nc || x.cand >= nc || cands[first[x.q - first_q] + x.cand].r != x.r)
+            return "gather: a record of query " + std::to_string(x.q) + ", round " + std::to_string(x.round);
+        std::vector<finch_gather_row> &to = rows_of[mine ? mine[x.q] : x.q];
+        if (to.size() <= x.round) to.resize((size_t)x.round + 1, finch_gather_row{0, 0, UINT64_MAX, 0, 0, 0, 0, 0, 0, 0., 0., 0., 0., 0.});
+        finch_gather_row &row = to[x.round];
+        if (row.round != UINT64_MAX) return "gather: two records of query " + std::to_string(x.q) + ", round " + std::to_string(x.round);
+        row.query = mine ? mine[x.q] : x.q, row.reference = x.r, row.round = x.round, row.overlap = x.overlap, row.common = x.common;
+        row.ref_len = x.ref_len, row.query_len = x.query_len, row.abund = x.abund, row.remaining = x.remaining;
+    }
+    return std::string();
+}
+
+// ... and with every query's rows once all records are placed: the offsets, the doubles, the rows in query order
+int gather_finish(std::vector<std::vector<finch_gather_row>> &rows_of, const std::vector<Sketch> &Qs, finch_gather_result *res) {
+    const uint32_t nq = (uint32_t)Qs.size();
+    for (uint32_t q = 0; q < nq; ++q) res->offsets[q + 1] = res->offsets[q] + rows_of[q].size();
+    res->rows.reserve(res->offsets[nq]);
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint64_t count_sum = gather_count_sum(Qs[q]);
+        for (finch_gather_row &row : rows_of[q]) {
+            if (row.round == UINT64_MAX) return hfail(FH_ERR_STATE, "gather: query %u has a round without a record", q);
+            gather_row_doubles(&row, count_sum);
+            res->rows.push_back(row);
+        }
+    }
+    return FH_OK;
+}
+
+// finch_gather's refusal of a query the rounds kernels' LDS mask cannot hold, finch_index_gather's too
+int gather_check_query_lengths(const std::vector<Sketch> &Qs) {
+    for (size_t q = 0; q < Qs.size(); ++q)
+        if (Qs[q].hashes.size() > fh::GATHER_MAX_QUERY)
+            return hfail(FH_ERR_UNSUPPORTED, "query sketch %zu (%s) has %zu hashes (a gather takes at most %u: one bit each in the rounds kernel's LDS)",
+                         q, Qs[q].name.c_str(), Qs[q].hashes.size(), fh::GATHER_MAX_QUERY);
+    return FH_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -5807,10 +5856,7 @@ int finch_gather(const finch_sketches *queries, const finch_sketches *refs, uint
     const std::vector<Sketch> &Qs = queries->v, &Rs = refs->v;
     if (int rc = check_ascending(Qs, "query")) return rc;
     if (int rc = check_ascending(Rs, "reference")) return rc;
-    for (size_t q = 0; q < Qs.size(); ++q)
-        if (Qs[q].hashes.size() > fh::GATHER_MAX_QUERY)
-            return hfail(FH_ERR_UNSUPPORTED, "query sketch %zu (%s) has %zu hashes (a gather takes at most %u: one bit each in the rounds kernel's LDS)",
-                         q, Qs[q].name.c_str(), Qs[q].hashes.size(), fh::GATHER_MAX_QUERY);
+    if (int rc = gather_check_query_lengths(Qs)) return rc;
     const uint32_t nq = (uint32_t)Qs.size(), nr = (uint32_t)Rs.size();
     auto res = std::make_unique<finch_gather_result>();
     res->offsets.assign((size_t)nq + 1, 0);
@@ -5931,23 +5977,10 @@ int finch_gather(const finch_sketches *queries, const finch_sketches *refs, uint
                 if (rc != FH_OK) break;
                 copied += recs.size();
                 // the records of the chunk, each at its round
-                for (const fh::GatherRecord &x : recs) {
-                    const uint64_t nc = x.q >= q0 && x.q < q1 ? first[x.q + 1] - first[x.q] : 0;
-                    if (x.round >= nc || x.cand >= nc || cands[first[x.q] + x.cand].r != x.r) {
-                        fail_with(FH_ERR_STATE, "gather: a record of query " + std::to_string(x.q) + ", round " + std::to_string(x.round));
-                        bad_record = true;
-                        break;
-                    }
-                    std::vector<finch_gather_row> &to = rows_of[mine[x.q]];
-                    if (to.size() <= x.round) to.resize((size_t)x.round + 1, finch_gather_row{0, 0, UINT64_MAX, 0, 0, 0, 0, 0, 0, 0., 0., 0., 0., 0.});
-                    finch_gather_row &row = to[x.round];
-                    if (row.round != UINT64_MAX) {
-                        fail_with(FH_ERR_STATE, "gather: two records of query " + std::to_string(x.q) + ", round " + std::to_string(x.round));
-                        bad_record = true;
-                        break;
-                    }
-                    row.query = mine[x.q], row.reference = x.r, row.round = x.round, row.overlap = x.overlap, row.common = x.common;
-                    row.ref_len = x.ref_len, row.query_len = x.query_len, row.abund = x.abund, row.remaining = x.remaining;
+                const std::string bad = gather_place_records(recs, q0, q1, cands.data(), first.data(), 0, mine.data(), rows_of);
+                if (!bad.empty()) {
+                    fail_with(FH_ERR_STATE, bad);
+                    bad_record = true;
                 }
                 q0 = q1;
             }
@@ -5963,18 +5996,102 @@ int finch_gather(const finch_sketches *queries, const finch_sketches *refs, uint
         fh::gather_close(gd);
     });
     if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
-
-    for (uint32_t q = 0; q < nq; ++q) res->offsets[q + 1] = res->offsets[q] + rows_of[q].size();
-    res->rows.reserve(res->offsets[nq]);
-    for (uint32_t q = 0; q < nq; ++q) {
-        const uint64_t count_sum = gather_count_sum(Qs[q]);
-        for (finch_gather_row &row : rows_of[q]) {
-            if (row.round == UINT64_MAX) return hfail(FH_ERR_STATE, "gather: query %u has a round without a record", q);
-            gather_row_doubles(&row, count_sum);
-            res->rows.push_back(row);
-        }
-    }
+    if (int rc = gather_finish(rows_of, Qs, res.get())) return rc;
     *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+// the same decomposition through the library index (fh_index.hip): the index's count leaves |Q n H_r| of every
+// pair that shares a hash, the rounds keep those counters live, and the records come through finch_gather's own finish.
+int finch_index_gather(const finch_index *cix, const finch_sketches *queries, uint64_t min_overlap, uint64_t max_rounds,
+                       finch_gather_result **out) try {
+    if (!cix || !queries || !out) return hfail(FH_ERR_INVALID, "null argument");
+    finch_index *ix = const_cast<finch_index *>(cix); // (the launch state is the index's; `mu` serialises its use)
+    const std::vector<Sketch> &Qs = queries->v;
+    if (int rc = check_ascending(Qs, "query")) return rc;
+    if (int rc = gather_check_query_lengths(Qs)) return rc;
+    const uint32_t nq = (uint32_t)Qs.size();
+    auto res = std::make_unique<finch_gather_result>();
+    res->from_index = true;
+    res->offsets.assign((size_t)nq + 1, 0);
+    if (nq == 0 || ix->entries.empty()) {
+        *out = res.release();
+        return FH_OK;
+    }
+    std::lock_guard<std::mutex> one_call(ix->mu);
+    struct RestoreDevice { // (this thread runs the first device entry)
+        int prev = fh::matrix_current_device();
+        ~RestoreDevice() { fh::matrix_restore_device(prev); }
+    } restore_device;
+
+    const uint32_t min_ov = gather_clamp(min_overlap, 1), max_r = gather_clamp(max_rounds, 0);
+    DistCsr qc;
+    qc.build(Qs, false);
+    std::vector<uint32_t> counts;
+    counts.reserve(qc.hashes.size());
+    for (const Sketch &s : Qs)
+        for (const KmerCount &h : s.hashes) counts.push_back(h.count);
+    const uint32_t n_chunks = (nq + ix->chunk - 1) / ix->chunk;
+    const uint32_t n_entries = (uint32_t)std::min<size_t>(ix->entries.size(), n_chunks);
+    std::vector<std::vector<finch_gather_row>> rows_of(nq); // (a chunk's queries are its own: no two threads share a row list)
+
+    std::mutex err_mu;
+    int err_rc = FH_OK;
+    std::string err_msg;
+    std::atomic<bool> failed{false};
+    auto fail_with = [&](int rc, const std::string &msg) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (err_rc == FH_OK) err_rc = rc, err_msg = msg;
+        failed = true;
+    };
+    std::mutex stat_mu;
+
+    // one thread per device entry: chunks of queries e, e + n_entries, ...
+    fork_join(n_entries, [&](unsigned e) {
+        try {
+            std::vector<fh::GatherCand> cands;
+            std::vector<fh::GatherRecord> recs;
+            std::vector<uint64_t> first;
+            double ms_sum = 0.;
+            uint64_t touched = 0, n_cands = 0, copied = 0, launches = 0;
+            for (uint32_t k = e; k < n_chunks && !failed; k += n_entries) {
+                const uint32_t q0 = k * ix->chunk, q1 = (uint32_t)std::min<uint64_t>(nq, (uint64_t)q0 + ix->chunk);
+                if (int rc = fh::index_gather_chunk(ix->entries[e], qc.view(), counts.data(), q0, q1, min_ov, max_r, &cands, &recs, &touched,
+                                                    &ms_sum, &launches)) {
+                    fail_with(rc, fh_last_error());
+                    break;
+                }
+                n_cands += cands.size();
+                copied += recs.size();
+                first.assign((size_t)(q1 - q0) + 1, 0); // each query's candidates: the list is sorted by (q, r), q in [q0, q1)
+                for (const fh::GatherCand &c : cands) ++first[c.q - q0 + 1];
+                for (uint32_t b = 0; b < q1 - q0; ++b) first[b + 1] += first[b];
+                const std::string bad = gather_place_records(recs, q0, q1, cands.data(), first.data(), q0, nullptr, rows_of);
+                if (!bad.empty()) {
+                    fail_with(FH_ERR_STATE, bad);
+                    break;
+                }
+            }
+            std::lock_guard<std::mutex> g(stat_mu);
+            res->kernel_ms += ms_sum;
+            res->launches += launches;
+            res->candidates += n_cands;
+            res->copied += copied;
+            res->touched += touched;
+        } catch (const std::bad_alloc &) {
+            fail_with(FH_ERR_CAPACITY, "out of host memory");
+        }
+    });
+    if (err_rc != FH_OK) return hfail(err_rc, "%s", err_msg.c_str());
+    if (int rc = gather_finish(rows_of, Qs, res.get())) return rc;
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_index_gather_stats(const finch_gather_result *r, uint64_t *pairs_touched) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    if (!r->from_index) return hfail(FH_ERR_INVALID, "finch_index_gather_stats: the result was not made by finch_index_gather");
+    if (pairs_touched) *pairs_touched = r->touched;
     return FH_OK;
 } FINCH_CATCH
 

@@ -31,6 +31,16 @@ int index_search_chunk(IndexDevice *d, const DistSide &queries, uint32_t q0, uin
 // again afterwards, as after a search.
 int index_dist_chunk(IndexDevice *d, const DistSide *queries, uint32_t q0, uint32_t q1, bool old_mode, const double *jmin,
                      std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms);
+// finch_index_gather's chunk: the queries [q0, q1) of `queries`, q1 - q0 <= chunk_queries, `counts` parallel to
+// queries.hashes.  Counted as above; *cands = the pairs with c >= min_overlap as (q, r, common), sorted by (q, r), q the caller's
+// index; then every round of every query in one launch over the live counters: *recs = one record per round, in no order, q the
+// caller's index, cand the winner's place among its query's candidates.  Both vectors are overwritten.  The counters are zero
+// again afterwards.  *touched is added the pairs with c > 0, *kernel_ms the three kernels' time, *launches 3.  No position
+// arrays are built: option gather_pos_bytes does not apply.  FH_ERR_STATE if the rounds kernel's own checks fail (its tail has
+// run all the same: the handle stays clean); a failure between the count and the end of the rounds leaves the handle dirty.
+int index_gather_chunk(IndexDevice *d, const DistSide &queries, const uint32_t *counts, uint32_t q0, uint32_t q1, uint32_t min_overlap,
+                       uint32_t max_rounds, std::vector<GatherCand> *cands, std::vector<GatherRecord> *recs, uint64_t *touched,
+                       double *kernel_ms, uint64_t *launches);
 void index_close(IndexDevice *d);
 
 } // namespace fh

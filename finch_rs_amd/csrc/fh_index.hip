@@ -15,6 +15,13 @@
 //   * k_index_dist_finish: finch_index_dist's finish after the same count: c, and 0 back; (i, j) as above, or
 //     old mode's total = |R|; the pair is appended where its jaccard reaches the host's conservative bound for the query.  The
 //     queries may be the library's own sketches (pairwise), read from the CSR the index holds.
+// finch_index_gather keeps the counters of the same count live through the rounds of finch_gather's loop:
+//   * k_index_gather_candidates: per touched pair c is read and LEFT; (q, r, c) is appended where c >= min_overlap;
+//   * k_index_gather_rounds: one workgroup of 1024 per query, the whole loop inside.  cnt[r] == |S_t n H_r| for every touched r:
+//     a round's winner is an arg-max over the candidates' counters, and removing S_t n H_w lowers by one the counter of every
+//     reference in the posting run of every removed hash, the runs dealt flat over the workgroup as the count deals them.  The
+//     remaining set is a bitmask over query positions in LDS, as in fh_gather.hip; no position arrays are built.  The tail
+//     stores 0 to every touched counter, so the index is clean for the next launch.
 // The order in which atomics land decides only where an entry sits in a list; the host sorts.
 #include <hip/hip_runtime.h>
 
@@ -224,6 +231,195 @@ __global__ void __launch_bounds__(THREADS) k_index_dist_finish(IndexArgs a, cons
     }
 }
 
+// ---- finch_index_gather ------------------------------------------------------------------------------------------------
+
+constexpr uint32_t ROUND_THREADS = 1024, ROUND_WAVES = ROUND_THREADS / 64;
+constexpr uint32_t NONE = 0xffffffffu;
+// bits of the error word: a counter decremented at 0; a round that cleared another number of bits than its winner's counter
+// said; a winner whose counter is not 0 after its round; a query with candidates that is longer than the launch's mask
+constexpr uint32_t GERR_UNDERFLOW = 1, GERR_CLEARED = 2, GERR_WINNER = 4, GERR_MASK = 8;
+
+struct IndexGatherArgs {
+    uint32_t min_overlap, max_rounds;
+    const uint32_t *qcnt;     // the chunk's counts, parallel to qh
+    GatherCand *list;         // k_index_gather_candidates: the chunk's list, list_cap entries, and its cursor (zero before)
+    uint32_t list_cap;
+    uint32_t *cursor;
+    const uint2 *cand;        // k_index_gather_rounds: the chunk's candidates (r, common) by (q, r) ...
+    const uint32_t *cand_off; // ... query q0 + b's are cand[cand_off[b] .. cand_off[b + 1])
+    GatherRecord *rec;
+    uint32_t rec_cap;
+    uint32_t *rec_cursor;     // zero before the launch
+    uint32_t *err;            // zero before the launch
+    uint32_t mask_words;      // the launch's dynamic LDS, in u32
+};
+
+// grid: x = query of the chunk.  Per touched pair c is read and the counter LEFT AS IT IS: the rounds go on from it.  The entry
+// (q, r, c) where c >= min_overlap, appended as k_index_finish appends.
+__global__ void __launch_bounds__(THREADS) k_index_gather_candidates(IndexArgs a, IndexGatherArgs g) {
+    const uint32_t qi = blockIdx.x, n = a.tcount[qi];
+    const uint32_t *cnt = a.cnt + (uint64_t)qi * a.nr;
+    const uint32_t *touched = a.touched + (uint64_t)qi * a.nr;
+    for (uint32_t base = 0; base < n; base += THREADS) { // (whole waves go round: the ballot sees every lane)
+        const uint32_t t = base + threadIdx.x;
+        uint32_t r = 0, c = 0;
+        if (t < n) {
+            r = touched[t];
+            c = r < a.nr ? cnt[r] : 0;
+        }
+        const bool pass = t < n && c >= g.min_overlap;
+        const uint64_t mask = __ballot(pass);
+        if (!mask) continue;
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        uint32_t first = 0;
+        if (pass && rank == 0) first = atomicAdd(g.cursor, (uint32_t)__popcll(mask));
+        first = __shfl(first, __ffsll((unsigned long long)mask) - 1, 64);
+        if (pass && first + rank < g.list_cap) { // (the host sized the list to the chunk's touched pairs)
+            GatherCand e;
+            e.q = a.q0 + qi, e.r = r, e.common = c;
+            g.list[first + rank] = e;
+        }
+    }
+}
+
+enum { W_BOUND = 0, W_WIN = 1, W_COUNT = 2, W_REF = 3, W_LEN = 4, W_N = 5 };
+
+// (count descending, candidate ascending): does (c2, i2) come before (c1, i1)?  NONE is no candidate
+__device__ inline bool gather_better(uint32_t c2, uint32_t i2, uint32_t c1, uint32_t i1) {
+    return i2 != NONE && (i1 == NONE || c2 > c1 || (c2 == c1 && i2 < i1));
+}
+
+// grid: x = query of the chunk; dynamic LDS: g.mask_words u32, one bit per hash of the longest of the chunk's queries that have
+// candidates.  A query without candidates runs no round and touches no mask: it may be longer than the mask.  Every branch
+// that holds a barrier is taken on an LDS word every thread reads (s_word; fh_batch_large.hip's rule).
+__global__ void __launch_bounds__(ROUND_THREADS) k_index_gather_rounds(IndexArgs a, IndexGatherArgs g) {
+    extern __shared__ uint32_t s_mask[];
+    __shared__ uint32_t s_lo[ROUND_THREADS], s_start[ROUND_THREADS], s_wsum[ROUND_WAVES];
+    __shared__ uint32_t s_cnt[ROUND_WAVES], s_idx[ROUND_WAVES], s_clr[ROUND_WAVES];
+    __shared__ uint64_t s_ab[ROUND_WAVES];
+    __shared__ uint32_t s_word[W_N];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t qi = blockIdx.x;
+    const uint32_t nqh = (uint32_t)(a.qoff[qi + 1] - a.qoff[qi]);
+    const uint64_t *Q = a.qh + (a.qoff[qi] - a.qbase);
+    const uint32_t *QC = g.qcnt + (a.qoff[qi] - a.qbase);
+    const uint32_t qtop = top_of(nqh);
+    const uint32_t c0 = g.cand_off[qi], ncand = g.cand_off[qi + 1] - c0;
+    const uint2 *cand = g.cand + c0;
+    uint32_t *cnt = a.cnt + (uint64_t)qi * a.nr;
+    const bool fits = (nqh + 31) / 32 <= g.mask_words;
+    uint32_t bad = 0;
+    if (ncand && fits) // (no barrier inside; the host sized the mask for every query that gets here)
+        for (uint32_t w = tid; w < (nqh + 31) / 32; w += ROUND_THREADS) s_mask[w] = w * 32 + 32 <= nqh ? ~0u : (1u << (nqh & 31)) - 1;
+    if (tid == 0) {
+        if (ncand && !fits) bad |= GERR_MASK;
+        s_word[W_BOUND] = !fits ? 0 : g.max_rounds ? min(g.max_rounds, ncand) : ncand;
+    }
+    __syncthreads();
+    const uint32_t bound = s_word[W_BOUND];
+    uint32_t remaining = nqh;
+    for (uint32_t t = 0; t < bound; ++t) {
+        // the arg-max over the live counters.  Other waves' atomics have changed them at L2 since this thread last read them:
+        // an agent-scope atomic load, so that nothing rests on what the CU's vector cache holds of such a line
+        uint32_t best_c = 0, best_i = NONE;
+        for (uint32_t i = tid; i < ncand; i += ROUND_THREADS) { // (i ascends: among equal counts the first stays)
+            const uint32_t r = cand[i].x;
+            const uint32_t c = r < a.nr ? __hip_atomic_load(&cnt[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+            if (c >= g.min_overlap && c > best_c) best_c = c, best_i = i;
+        }
+        for (int o = 32; o; o >>= 1) {
+            const uint32_t c2 = __shfl_xor(best_c, o, 64), i2 = __shfl_xor(best_i, o, 64);
+            if (gather_better(c2, i2, best_c, best_i)) best_c = c2, best_i = i2;
+        }
+        if (lane == 0) s_cnt[wave] = best_c, s_idx[wave] = best_i;
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t wc = 0, wi = NONE;
+            for (uint32_t w = 0; w < ROUND_WAVES; ++w)
+                if (gather_better(s_cnt[w], s_idx[w], wc, wi)) wc = s_cnt[w], wi = s_idx[w];
+            const uint32_t r = wi != NONE ? cand[wi].x : 0;
+            s_word[W_WIN] = wi; // NONE: no candidate reaches min_overlap
+            s_word[W_COUNT] = wc;
+            s_word[W_REF] = r;
+            s_word[W_LEN] = wi != NONE ? a.rlen[r] : 0;
+        }
+        __syncthreads();
+        const uint32_t wi = s_word[W_WIN], wc = s_word[W_COUNT], wr = s_word[W_REF], nrh = s_word[W_LEN];
+        if (wi == NONE) break; // the same LDS word in every thread
+        // S_{t+1} = S_t \ H_w.  1024 of the winner's hashes at a time: thread t looks hash t up in the query; a hit whose bit is
+        // set clears it, adds the query's count of it and finds the hash's posting run; the runs are scanned and dealt flat over
+        // the workgroup as k_index_count deals them, one decrement per posting
+        const uint64_t *R = a.rh + a.roff[wr];
+        uint64_t ab = 0;
+        uint32_t clr = 0;
+        for (uint32_t base = 0; base < nrh; base += ROUND_THREADS) { // (nrh: an LDS word; whole workgroups go round)
+            const uint32_t k0 = base + tid;
+            uint32_t lo = 0, len = 0;
+            if (k0 < nrh) {
+                const uint64_t x = R[k0];
+                const uint32_t p = count_below<true>(Q, nqh, qtop, x);
+                if (p && Q[p - 1] == x) {
+                    const uint32_t bit = 1u << ((p - 1) & 31);
+                    if (atomicAnd(&s_mask[(p - 1) >> 5], ~bit) & bit) {
+                        ab += QC[p - 1], ++clr;
+                        lo = count_below<false>(a.keys, a.n_post, a.post_top, x);
+                        len = count_below<true>(a.keys, a.n_post, a.post_top, x) - lo;
+                    }
+                }
+            }
+            uint32_t inc = len; // inclusive scan over the wave, then over the sixteen waves
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t v = __shfl_up(inc, o, 64);
+                if ((int)lane >= o) inc += v;
+            }
+            if (lane == 63) s_wsum[wave] = inc;
+            __syncthreads();
+            uint32_t before = 0, total = 0;
+            for (uint32_t w = 0; w < ROUND_WAVES; ++w) {
+                before += w < wave ? s_wsum[w] : 0;
+                total += s_wsum[w];
+            }
+            s_lo[tid] = lo;
+            s_start[tid] = before + inc - len;
+            __syncthreads();
+            for (uint32_t k = tid; k < total; k += ROUND_THREADS) {
+                // posting k of the batch is in the last run that starts at or before k (k_index_count's search)
+                uint32_t run = 0;
+                for (uint32_t step = ROUND_THREADS / 2; step; step >>= 1) run = s_start[run + step] <= k ? run + step : run;
+                const uint32_t r = a.vals[s_lo[run] + (k - s_start[run])];
+                if (r < a.nr && atomicSub(&cnt[r], 1u) == 0) bad |= GERR_UNDERFLOW;
+            }
+            __syncthreads(); // the next batch writes s_lo, s_start and s_wsum again; every decrement of this one has landed
+        }
+        for (int o = 32; o; o >>= 1) ab += __shfl_xor(ab, o, 64), clr += __shfl_xor(clr, o, 64);
+        if (lane == 0) s_ab[wave] = ab, s_clr[wave] = clr;
+        __syncthreads();
+        remaining -= wc;
+        if (tid == 0) {
+            uint64_t abund = 0;
+            uint32_t cleared = 0;
+            for (uint32_t w = 0; w < ROUND_WAVES; ++w) abund += s_ab[w], cleared += s_clr[w];
+            if (cleared != wc) bad |= GERR_CLEARED;
+            if (__hip_atomic_load(&cnt[wr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) bad |= GERR_WINNER;
+            GatherRecord rec;
+            rec.q = a.q0 + qi, rec.r = wr, rec.round = t, rec.overlap = wc, rec.common = cand[wi].y;
+            rec.ref_len = nrh, rec.query_len = nqh, rec.remaining = remaining, rec.abund = abund, rec.cand = wi, rec.pad = 0;
+            const uint32_t at = atomicAdd(g.rec_cursor, 1u);
+            if (at < g.rec_cap) g.rec[at] = rec;
+        }
+    }
+    if (bad) atomicOr(g.err, bad);
+    // the tail, for every query, with or without candidates, whatever the error word says: 0 to the counter of every touched
+    // reference -- non-candidates were touched and decremented too --, so the index is clean for the next launch
+    __syncthreads();
+    const uint32_t n = a.tcount[qi];
+    const uint32_t *touched = a.touched + (uint64_t)qi * a.nr;
+    for (uint32_t i = tid; i < n; i += ROUND_THREADS) {
+        const uint32_t r = touched[i];
+        if (r < a.nr) cnt[r] = 0;
+    }
+}
+
 } // namespace
 
 namespace fh {
@@ -239,7 +435,14 @@ struct IndexDevice {
     uint64_t sel_cap = 0;         // entries that sel holds
     uint32_t *back_h = nullptr;   // pinned: chunk touched-list lengths, then the cursor
     double *jmin = nullptr;       // finch_index_dist: the chunk's jaccard bounds, one per query (allocated by its first chunk)
-    hipEvent_t ev[4] = {};
+    // finch_index_gather, grown as needed: the chunk's counts, its list of (q, r, common), the candidates (r, common) by (q, r),
+    // each query's range of them, the records; two words -- the records' cursor, the error word -- and their pinned copy
+    void *gat[5] = {};
+    size_t gat_cap[5] = {};
+    uint32_t *gwords = nullptr, *gwords_h = nullptr;
+    bool rounds_lds_set = false;  // k_index_gather_rounds may ask for more dynamic LDS than a launch gets unasked
+    std::vector<uint32_t> rlen_h; // the library's lengths: what a candidate's `common` is checked against
+    hipEvent_t ev[6] = {};
     bool dirty = false;           // a launch failed between the count and the finish: the counters are not known to be zero
 };
 
@@ -254,6 +457,10 @@ void index_close(IndexDevice *d) {
         for (uint32_t *p : {d->cnt, d->touched, d->tcount, d->cursor, d->sel})
             if (p) (void)hipFree(p);
         if (d->jmin) (void)hipFree(d->jmin);
+        for (void *p : d->gat)
+            if (p) (void)hipFree(p);
+        if (d->gwords) (void)hipFree(d->gwords);
+        if (d->gwords_h) (void)hipHostFree(d->gwords_h);
         if (d->back_h) (void)hipHostFree(d->back_h);
         for (hipEvent_t e : d->ev)
             if (e) (void)hipEventDestroy(e);
@@ -282,6 +489,7 @@ static int open_into(IndexDevice *d, const DistSide &r, uint64_t *device_bytes, 
         rlen[s] = (uint32_t)(r.offsets[s + 1] - r.offsets[s]);
         rlast[s] = rlen[s] ? r.hashes[r.offsets[s + 1] - 1] : 0;
     }
+    d->rlen_h = rlen;
     uint64_t total = 0;
     if (int rc = upload(&d->lib[0], r.hashes, P * sizeof(uint64_t), &total)) return rc;
     if (int rc = upload(&d->lib[1], r.offsets, ((size_t)r.n + 1) * sizeof(uint64_t), &total)) return rc;
@@ -359,12 +567,10 @@ static int grow(void **p, size_t *have, size_t bytes) {
     return FH_OK;
 }
 
-// one chunk of either route.  q = nullptr: the queries are the library's own sketches q0 .. q1 (pairwise), read where the index
-// keeps them.  jmin = nullptr: the search's finish with min_containment; else finch_index_dist's with the chunk's bounds.
-static int run_chunk(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q1, double min_containment, const double *jmin, bool old_mode,
-                     std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms) {
+// the queries [q0, q1) of `q` to the device (q = nullptr: the library's own sketches, which are there) and the argument block of
+// the chunk's kernels
+static int chunk_args(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q1, IndexArgs *out) {
     const uint32_t n = q1 - q0;
-    IHIP_TRY(hipSetDevice(d->device));
     uint64_t h0 = 0;
     if (q) {
         h0 = q->offsets[q0];
@@ -382,11 +588,6 @@ static int run_chunk(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q1
         IHIP_TRY(hipMemcpy(d->qry[3], q->flags + q0, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
         IHIP_TRY(hipMemcpy(d->qry[4], q->scale + q0, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (jmin) {
-        if (!d->jmin) IHIP_TRY(api_dev_malloc((void **)&d->jmin, (size_t)d->chunk * sizeof(double)));
-        IHIP_TRY(hipMemcpy(d->jmin, jmin, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    }
-
     IndexArgs a;
     a.rh = (const uint64_t *)d->lib[0], a.roff = (const uint64_t *)d->lib[1], a.rlast = (const uint64_t *)d->lib[2];
     a.rmax = (const uint64_t *)d->lib[3], a.rlen = (const uint32_t *)d->lib[4], a.rflag = (const uint32_t *)d->lib[5];
@@ -400,8 +601,25 @@ static int run_chunk(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q1
     }
     a.qbase = h0, a.q0 = q0;
     a.cnt = d->cnt, a.touched = d->touched, a.tcount = d->tcount;
-    a.min_c = min_containment;
+    a.min_c = 0.;
     a.sel = d->sel, a.cursor = d->cursor, a.sel_cap = 0;
+    *out = a;
+    return FH_OK;
+}
+
+// one chunk of either route.  q = nullptr: the queries are the library's own sketches q0 .. q1 (pairwise), read where the index
+// keeps them.  jmin = nullptr: the search's finish with min_containment; else finch_index_dist's with the chunk's bounds.
+static int run_chunk(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q1, double min_containment, const double *jmin, bool old_mode,
+                     std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms) {
+    const uint32_t n = q1 - q0;
+    IHIP_TRY(hipSetDevice(d->device));
+    IndexArgs a;
+    if (int rc = chunk_args(d, q, q0, q1, &a)) return rc;
+    a.min_c = min_containment;
+    if (jmin) {
+        if (!d->jmin) IHIP_TRY(api_dev_malloc((void **)&d->jmin, (size_t)d->chunk * sizeof(double)));
+        IHIP_TRY(hipMemcpy(d->jmin, jmin, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    }
 
     // the count; the touched lists' lengths cross, so that the chunk's list can be sized to what may pass
     d->dirty = true; // until the finish has stored the zeros back
@@ -465,6 +683,125 @@ int index_dist_chunk(IndexDevice *d, const DistSide *queries, uint32_t q0, uint3
         return api_fail(FH_ERR_INVALID, "index_dist_chunk: queries %u..%u of %u, %u per launch", q0, q1, queries ? queries->n : d->nr, d->chunk);
     if (d->dirty) return api_fail(FH_ERR_STATE, "index dist: an earlier call on this index failed between its two kernels; build the index again");
     return run_chunk(d, queries, q0, q1, 0., jmin, old_mode, entries, touched, kernel_ms);
+}
+
+// finch_index_gather's chunk: the count as above, the candidates, then every round of every query in one launch.
+static int gather_chunk(IndexDevice *d, const DistSide &q, const uint32_t *counts, uint32_t q0, uint32_t q1, uint32_t min_overlap,
+                        uint32_t max_rounds, std::vector<GatherCand> *cands, std::vector<GatherRecord> *recs, uint64_t *touched,
+                        double *kernel_ms, uint64_t *launches) {
+    const uint32_t n = q1 - q0;
+    IHIP_TRY(hipSetDevice(d->device));
+    IndexArgs a;
+    if (int rc = chunk_args(d, &q, q0, q1, &a)) return rc;
+    const uint64_t nh = q.offsets[q1] - a.qbase;
+    if (int rc = grow(&d->gat[0], &d->gat_cap[0], nh * sizeof(uint32_t))) return rc;
+    if (nh) IHIP_TRY(hipMemcpy(d->gat[0], counts + a.qbase, nh * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = grow(&d->gat[3], &d->gat_cap[3], ((size_t)n + 1) * sizeof(uint32_t))) return rc;
+    if (!d->gwords) {
+        IHIP_TRY(api_dev_malloc((void **)&d->gwords, 2 * sizeof(uint32_t)));
+        IHIP_TRY(api_host_malloc((void **)&d->gwords_h, 2 * sizeof(uint32_t)));
+    }
+    if (!d->rounds_lds_set) { // the mask may take all of GATHER_MAX_QUERY bits: above the 64 KiB a launch gets unasked
+        IHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_index_gather_rounds), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(GATHER_MAX_QUERY / 8)));
+        d->rounds_lds_set = true;
+    }
+    IndexGatherArgs g{};
+    g.min_overlap = std::max(min_overlap, 1u), g.max_rounds = max_rounds;
+    g.qcnt = (const uint32_t *)d->gat[0];
+    g.cursor = d->cursor;
+    g.rec_cursor = d->gwords, g.err = d->gwords + 1;
+
+    // 1. the count; the touched lists' lengths cross, so that the chunk's list can be sized to what may pass
+    d->dirty = true; // until the rounds kernel's tail has stored the zeros back
+    IHIP_TRY(hipEventRecord(d->ev[0], d->stream));
+    hipLaunchKernelGGL(k_index_count, dim3(n), dim3(THREADS), 0, d->stream, a);
+    IHIP_TRY(hipGetLastError());
+    IHIP_TRY(hipEventRecord(d->ev[1], d->stream));
+    IHIP_TRY(hipMemcpyAsync(d->back_h, d->tcount, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    IHIP_TRY(hipStreamSynchronize(d->stream));
+    uint64_t pairs = 0;
+    for (uint32_t i = 0; i < n; ++i) pairs += d->back_h[i];
+    *touched += pairs;
+
+    // 2. the candidates: the cursor crosses, then that many entries (pairs <= chunk x nr <= 2^31: index_open)
+    if (int rc = grow(&d->gat[1], &d->gat_cap[1], pairs * sizeof(GatherCand))) return rc;
+    g.list = (GatherCand *)d->gat[1], g.list_cap = (uint32_t)pairs;
+    IHIP_TRY(hipMemsetAsync(d->cursor, 0, sizeof(uint32_t), d->stream));
+    IHIP_TRY(hipEventRecord(d->ev[2], d->stream));
+    hipLaunchKernelGGL(k_index_gather_candidates, dim3(n), dim3(THREADS), 0, d->stream, a, g);
+    IHIP_TRY(hipGetLastError());
+    IHIP_TRY(hipEventRecord(d->ev[3], d->stream));
+    IHIP_TRY(hipMemcpyAsync(d->back_h + d->chunk, d->cursor, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    IHIP_TRY(hipStreamSynchronize(d->stream));
+    const uint32_t nc = d->back_h[d->chunk];
+    if (nc > pairs) return api_fail(FH_ERR_STATE, "index gather: %u candidates from %llu pairs", nc, (unsigned long long)pairs);
+    cands->resize(nc);
+    if (nc) IHIP_TRY(hipMemcpy(cands->data(), d->gat[1], (size_t)nc * sizeof(GatherCand), hipMemcpyDeviceToHost));
+    for (const GatherCand &c : *cands)
+        if (c.q < q0 || c.q >= q1 || c.r >= d->nr || c.common == 0 || c.common > q.offsets[c.q + 1] - q.offsets[c.q] || c.common > d->rlen_h[c.r])
+            return api_fail(FH_ERR_STATE, "index gather: candidate (%u, %u) with %u common hashes", c.q, c.r, c.common);
+    std::sort(cands->begin(), cands->end(), [](const GatherCand &x, const GatherCand &y) { return x.q < y.q || (x.q == y.q && x.r < y.r); });
+    // each query's range, (r, common) per candidate, the records the chunk can give at most -- a round removes at least one
+    // hash --, the longest query that has candidates
+    std::vector<uint32_t> off((size_t)n + 1, 0);
+    std::vector<uint32_t> rc2((size_t)nc * 2);
+    for (uint32_t i = 0; i < nc; ++i) {
+        const GatherCand &c = (*cands)[i];
+        if (i && (*cands)[i - 1].q == c.q && (*cands)[i - 1].r == c.r)
+            return api_fail(FH_ERR_STATE, "index gather: candidate (%u, %u) twice", c.q, c.r);
+        rc2[2 * (size_t)i] = c.r, rc2[2 * (size_t)i + 1] = c.common;
+        ++off[c.q - q0 + 1];
+    }
+    uint64_t n_rec = 0, longest = 1;
+    for (uint32_t b = 0; b < n; ++b) {
+        const uint64_t len = q.offsets[q0 + b + 1] - q.offsets[q0 + b];
+        n_rec += std::min<uint64_t>(max_rounds ? std::min<uint64_t>(max_rounds, off[b + 1]) : off[b + 1], len);
+        if (off[b + 1]) longest = std::max(longest, len);
+        off[b + 1] += off[b];
+    }
+    if (longest > GATHER_MAX_QUERY) return api_fail(FH_ERR_STATE, "index gather: a query of %llu hashes", (unsigned long long)longest);
+    if (int rc = grow(&d->gat[2], &d->gat_cap[2], (size_t)nc * 2 * sizeof(uint32_t))) return rc;
+    if (int rc = grow(&d->gat[4], &d->gat_cap[4], n_rec * sizeof(GatherRecord))) return rc;
+    if (nc) IHIP_TRY(hipMemcpyAsync(d->gat[2], rc2.data(), (size_t)nc * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+    IHIP_TRY(hipMemcpyAsync(d->gat[3], off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+    IHIP_TRY(hipMemsetAsync(d->gwords, 0, 2 * sizeof(uint32_t), d->stream));
+    g.cand = (const uint2 *)d->gat[2], g.cand_off = (const uint32_t *)d->gat[3];
+    g.rec = (GatherRecord *)d->gat[4], g.rec_cap = (uint32_t)n_rec;
+    g.mask_words = (uint32_t)((longest + 31) / 32);
+
+    // 3. the rounds, and the tail that leaves the counters zero
+    IHIP_TRY(hipEventRecord(d->ev[4], d->stream));
+    hipLaunchKernelGGL(k_index_gather_rounds, dim3(n), dim3(ROUND_THREADS), (size_t)g.mask_words * sizeof(uint32_t), d->stream, a, g);
+    IHIP_TRY(hipGetLastError());
+    IHIP_TRY(hipEventRecord(d->ev[5], d->stream));
+    IHIP_TRY(hipMemcpyAsync(d->gwords_h, d->gwords, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    IHIP_TRY(hipStreamSynchronize(d->stream)); // (rc2 and off are this frame's)
+    d->dirty = false;
+    *launches += 3;
+    for (int e = 0; e < 6; e += 2) {
+        float ms = 0.f;
+        IHIP_TRY(hipEventElapsedTime(&ms, d->ev[e], d->ev[e + 1]));
+        *kernel_ms += ms;
+    }
+    const uint32_t rows = d->gwords_h[0], err = d->gwords_h[1];
+    if (err)
+        return api_fail(FH_ERR_STATE, "index gather: the rounds kernel's counters do not match its mask (error word %u: %s)", err,
+                        err & GERR_UNDERFLOW ? "a counter decremented at 0" : err & GERR_CLEARED ? "a round cleared another number of bits than its count"
+                        : err & GERR_WINNER ? "a winner's counter is not 0 after its round" : "a query longer than the mask");
+    if (rows > n_rec) return api_fail(FH_ERR_STATE, "index gather: %u records where at most %llu can be", rows, (unsigned long long)n_rec);
+    recs->resize(rows);
+    if (rows) IHIP_TRY(hipMemcpy(recs->data(), d->gat[4], (size_t)rows * sizeof(GatherRecord), hipMemcpyDeviceToHost));
+    return FH_OK;
+}
+
+int index_gather_chunk(IndexDevice *d, const DistSide &queries, const uint32_t *counts, uint32_t q0, uint32_t q1, uint32_t min_overlap,
+                       uint32_t max_rounds, std::vector<GatherCand> *cands, std::vector<GatherRecord> *recs, uint64_t *touched,
+                       double *kernel_ms, uint64_t *launches) {
+    if (!counts || q1 <= q0 || q1 > queries.n || q1 - q0 > d->chunk)
+        return api_fail(FH_ERR_INVALID, "index_gather_chunk: queries %u..%u of %u, %u per launch", q0, q1, queries.n, d->chunk);
+    if (d->dirty) return api_fail(FH_ERR_STATE, "index gather: an earlier call on this index failed between its kernels; build the index again");
+    return gather_chunk(d, queries, counts, q0, q1, min_overlap, max_rounds, cands, recs, touched, kernel_ms, launches);
 }
 
 } // namespace fh

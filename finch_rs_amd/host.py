@@ -156,6 +156,8 @@ _SYMS["finch_gather_offsets"] = (C.c_int, [_P, _P])
 _SYMS["finch_gather_copy"] = (C.c_int, [_P, _P, _P, _P])
 _SYMS["finch_gather_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _SYMS["finch_gather_free"] = (None, [_P])
+_SYMS["finch_index_gather"] = (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(_P)])
+_SYMS["finch_index_gather_stats"] = (C.c_int, [_P, C.POINTER(C.c_uint64)])
 
 
 class CCountMoments(C.Structure):
@@ -767,6 +769,13 @@ class LibraryIndex:
         """dist_json(queries, refs, max_distance, old_mode)'s text for a bound below 1"""
         return _dist_text(self._dist_result(queries, max_distance, old_mode))
 
+    def gather(self, queries: Sketches, min_overlap: int = 1, max_rounds: int = 0, stats: Optional[dict] = None):
+        """gather(queries, refs, min_overlap, max_rounds)'s (offsets, rows), byte for byte, the rounds over the index's live
+        counters (finch_index_gather); `stats` receives gather()'s figures and pairs_touched, the pairs the device counted"""
+        p = _P()
+        _check(lib().finch_index_gather(self._handle(), queries._p, int(min_overlap), int(max_rounds), C.byref(p)))
+        return _gather_rows(p, len(queries), stats, from_index=True)
+
     def best_match(self, queries: Sketches, iq: int = 0) -> int:
         """best_match(refs, queries, iq): a top-1 search at the smallest positive threshold; a query that shares nothing with
         the library has no row and gets index 0, as the tie rule gives it there"""
@@ -802,6 +811,28 @@ def gather_query(refs: Sketches, queries: Sketches, iq: int, min_overlap: int = 
     return rows[:n.value]
 
 
+def _gather_rows(p, n_queries: int, stats: Optional[dict], from_index: bool = False):
+    """(offsets, rows) of a finch_gather_result, which is freed here"""
+    L = lib()
+    try:
+        n = L.finch_gather_len(p)
+        offsets = np.zeros(n_queries + 1, np.uint64)
+        _check(L.finch_gather_offsets(p, offsets.ctypes.data))
+        rows = np.empty(n, GATHER_DTYPE)
+        _check(L.finch_gather_copy(p, None, None, rows.ctypes.data))
+        if stats is not None:
+            ms, nl, nc, nrec = C.c_double(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+            _check(L.finch_gather_stats(p, C.byref(ms), C.byref(nl), C.byref(nc), C.byref(nrec)))
+            stats.update(kernel_ms=ms.value, launches=nl.value, candidates=nc.value, records_copied=nrec.value)
+            if from_index:
+                nt = C.c_uint64()
+                _check(L.finch_index_gather_stats(p, C.byref(nt)))
+                stats.update(pairs_touched=nt.value)
+    finally:
+        L.finch_gather_free(p)
+    return offsets, rows
+
+
 def gather(queries: Sketches, refs: Sketches, min_overlap: int = 1, max_rounds: int = 0, devices: Sequence[int] = (0,),
            stats: Optional[dict] = None):
     """gather_query for every query, the loop on the GPU -> (offsets, rows): the GATHER_DTYPE rows grouped by query in query order,
@@ -813,19 +844,7 @@ def gather(queries: Sketches, refs: Sketches, min_overlap: int = 1, max_rounds: 
     darr = (C.c_int * len(devs))(*devs)
     p = _P()
     _check(L.finch_gather(queries._p, refs._p, int(min_overlap), int(max_rounds), darr, len(devs), C.byref(p)))
-    try:
-        n = L.finch_gather_len(p)
-        offsets = np.zeros(len(queries) + 1, np.uint64)
-        _check(L.finch_gather_offsets(p, offsets.ctypes.data))
-        rows = np.empty(n, GATHER_DTYPE)
-        _check(L.finch_gather_copy(p, None, None, rows.ctypes.data))
-        if stats is not None:
-            ms, nl, nc, nrec = C.c_double(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-            _check(L.finch_gather_stats(p, C.byref(ms), C.byref(nl), C.byref(nc), C.byref(nrec)))
-            stats.update(kernel_ms=ms.value, launches=nl.value, candidates=nc.value, records_copied=nrec.value)
-    finally:
-        L.finch_gather_free(p)
-    return offsets, rows
+    return _gather_rows(p, len(queries), stats)
 
 
 # one row of finch_compare_counts: the indices of the pair, then finch_count_moments' fields

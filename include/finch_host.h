@@ -333,6 +333,37 @@ int finch_gather_copy(const finch_gather_result *r, uint32_t *query_idx, uint32_
 int finch_gather_stats(const finch_gather_result *r, double *kernel_ms, uint64_t *launches, uint64_t *candidates, uint64_t *records_copied);
 void finch_gather_free(finch_gather_result *r);
 
+/* gather through the index: the same decomposition at a cost that follows the pairs that share a hash.  THE CONTRACT:
+ * finch_index_gather(ix, queries, min_overlap, max_rounds) returns byte for byte what finch_gather(queries, refs, min_overlap,
+ * max_rounds, ...) returns for the library the index was built from -- offsets, the rows in their order, every integer and every
+ * double the same bits (two NaNs count as equal).  The gather's own contract is the comment above, unchanged: min_overlap below 1 is
+ * 1, max_rounds = 0 is no cap, ties go to the lower reference index; finch_gather_query is the judge.  The result is a
+ * finch_gather_result, read with finch_gather_len / _offsets / _copy / _stats and freed with finch_gather_free.
+ *   No `refs`: a row needs only ref_len of the library, which the index holds.  No threshold is refused: a candidate shares at
+ *   least one hash, and the index enumerates every pair that does.
+ *   The device, per chunk of index_chunk_queries queries (dealt over the index's device entries as finch_index_search deals
+ *   them), three launches: finch_index_search's count, which leaves |Q n H_r| in the query's counter of every reference r that
+ *   shares a hash; the candidates (counter >= min_overlap), the counters left as they are; and every round of every query of the
+ *   chunk, one workgroup per query: the winner is an arg-max over the candidates' counters -- nothing is recounted --, and each
+ *   hash the winner removes from the query lowers the counter of every reference that holds it, so that every counter is the
+ *   reference's count against what is left.  All rounds together lower no more counters than the count raised.  No position arrays
+ *   are built: the options gather_slice and gather_pos_bytes do not apply, and no query is refused for its candidates' positions.
+ *   FH_ERR_INVALID for a null argument, a query whose hashes are not strictly ascending (named); FH_ERR_UNSUPPORTED for a sketch of
+ *   2^32 - 1 hashes or more and for a query of more than 2^20 = 1 048 576 hashes (named, with the limit: the remaining set is a
+ *   bitmask in the rounds kernel's LDS, as in finch_gather) -- all before any device is touched.  Zero queries, or an index of a
+ *   library without a hash: FH_OK, no rows, no device needed.  One call at a time runs on an index, searches included (others
+ *   wait).  FH_ERR_STATE, never a wrong row, if the rounds kernel's own checks fail (a counter lowered below 0; a round that
+ *   removed another number of hashes than its winner's counter said; a winner whose counter is not 0 after its round), and for
+ *   every call after one that failed between its kernels: the index must be built again.  The caller's current device is the same
+ *   after the call.
+ * finch_gather_stats on the result: candidates = exactly the pairs with c_j(0) >= min_overlap, records_copied = exactly the rows,
+ *   launches = three per chunk of queries, kernel_ms = their time.
+ * finch_index_gather_stats: pairs_touched = the (query, reference) pairs the device counted, i.e. those that share a hash.
+ *   FH_ERR_INVALID, *pairs_touched untouched, for a result that finch_gather made. */
+int finch_index_gather(const finch_index *ix, const finch_sketches *queries, uint64_t min_overlap, uint64_t max_rounds,
+                       finch_gather_result **out);
+int finch_index_gather_stats(const finch_gather_result *r, uint64_t *pairs_touched);
+
 /* compare_counts (Sketch.compare_counts, lib/src/python.rs:496-559): the merge walk of a reference sketch and a query sketch
  * that also sums the abundances of the shared hashes and runs the one-pass recurrence for the higher moments of the query's
  * abundances over them.  The eight values are the reference's tuple, in its order:
