@@ -1,5 +1,5 @@
 // fh_host_model.h -- the host layer's data model, shared by fh_host.cpp (sketch_files / sketch_stream / filters / .sk
-// writer) and fh_serial.cpp (.sk reader, .bsk / .msh Cap'n Proto writers and readers).
+// writer), fh_library.cpp (the library calls) and fh_serial.cpp (.sk reader, .bsk / .msh Cap'n Proto writers and readers).
 //   KmerCount (sketch_schemes/mod.rs:16-22), FilterParams (filtering.rs:11-16), SketchParams (mod.rs:54-71),
 //   Sketch (serialization/mod.rs:46-55) of the reference.
 #pragma once
@@ -116,6 +116,15 @@ struct Sketch {
 
 // SketchParams::check_compatibility over a list (mod.rs:158-226): the error text of the first mismatch with sketch 0
 int check_compatible(const std::vector<Sketch> &sketches);
+
+// What fh_host.cpp defines for itself and for the library calls of fh_library.cpp (each is described where it is defined); not
+// part of the shared library's interface.
+#define FINCH_LOCAL __attribute__((visibility("hidden")))
+FINCH_LOCAL uint64_t scale_max_hash(double scale);
+FINCH_LOCAL void distance_from_counts(bool old_mode, uint64_t c, uint64_t i, uint64_t j, uint32_t kmer_length, bool with_mash, finch_distance_out *out);
+FINCH_LOCAL double pair_min_scale(const Sketch &qs, const Sketch &rs);
+FINCH_LOCAL void json_escape(std::string &o, const std::string &s);
+FINCH_LOCAL std::string json_f64(double v);
 
 } // namespace finch
 

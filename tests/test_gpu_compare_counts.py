@@ -155,3 +155,17 @@ def test_same_call_twice_same_bytes():
     a = with_options(lambda: H.compare_counts(case.rs, case.qs, 1), chunk=30 * len(QUERY_LENGTHS))
     b = with_options(lambda: H.compare_counts(case.rs, case.qs, 1), chunk=30 * len(QUERY_LENGTHS))
     assert len(a) and a.tobytes() == b.tobytes()
+
+
+def test_the_current_device_is_left_alone():
+    """(tells a call that leaves the device changed only where there is a second GPU: with one, the last device is device 0)"""
+    import ctypes as C
+    hip = C.CDLL("libamdhip64.so")
+    rs = collect([[(1, 2), (2, 1), (3, 5), (4, 1)], [], [(2, 3), (4, 4), (9, 1)]], "r")
+    qs = collect([[(2, 1), (3, 1), (4, 7)], [(5, 1)]], "q")
+    dev = C.c_int(-1)
+    assert hip.hipGetDevice(C.byref(dev)) == 0
+    before = dev.value
+    rows = H.compare_counts(rs, qs, devices=(F.device_count() - 1,))
+    assert rows["common"].tolist() == [3, 0, 2, 0, 0, 0]
+    assert hip.hipGetDevice(C.byref(dev)) == 0 and dev.value == before

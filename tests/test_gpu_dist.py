@@ -486,3 +486,40 @@ def test_chunks_below_the_query_count(devices, chunk, launches):
         F.set_option("dist_chunk_pairs", None)
     assert st["launches"] == launches
     same_rows(rows, expected(qs, rs), 1.0)
+
+
+def hand_sketches():
+    qs = collect([mk("q0", [1, 2, 3, 4]), mk("q1", [5, 7, 9])])
+    rs = collect([mk("r0", [1, 2, 3, 4]), mk("r1", []), mk("r2", [0, 2, 7, 8])])
+    return qs, rs
+
+
+def test_the_current_device_is_left_alone():
+    """(tells a call that leaves the device changed only where there is a second GPU: with one, the last device is device 0)"""
+    import ctypes as C
+    hip = C.CDLL("libamdhip64.so")
+    qs, rs = hand_sketches()
+    dev = C.c_int(-1)
+    assert hip.hipGetDevice(C.byref(dev)) == 0
+    before = dev.value
+    rows = H.dist(qs, rs, devices=(F.device_count() - 1,))
+    assert len(rows) == 6
+    assert hip.hipGetDevice(C.byref(dev)) == 0 and dev.value == before
+
+
+@pytest.mark.parametrize("devices, chunk, launches", [((0, 0, 0), None, 1), ((0, 0), "2", 3)])
+def test_more_device_entries_than_chunks(devices, chunk, launches):
+    """2 queries x 3 references: one chunk for three entries; then three chunks of one reference dealt over two entries.  The
+    rows are the single entry's, byte for byte"""
+    qs, rs = hand_sketches()
+    one = H.dist(qs, rs, devices=(0,))
+    same_rows(one, expected(qs, rs), 1.0)
+    assert list(zip(one["reference"].tolist(), one["query"].tolist())) == [(r, q) for r in range(3) for q in range(2)]
+    st = {}
+    try:
+        F.set_option("dist_chunk_pairs", chunk)
+        rows = H.dist(qs, rs, devices=devices, stats=st)
+    finally:
+        F.set_option("dist_chunk_pairs", None)
+    assert st["launches"] == launches
+    assert rows.dtype == one.dtype and rows.tobytes() == one.tobytes()
