@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "fh_dist.h"
+#include "fh_moments.h"
 
 namespace fh {
 
@@ -41,6 +42,19 @@ int index_dist_chunk(IndexDevice *d, const DistSide *queries, uint32_t q0, uint3
 int index_gather_chunk(IndexDevice *d, const DistSide &queries, const uint32_t *counts, uint32_t q0, uint32_t q1, uint32_t min_overlap,
                        uint32_t max_rounds, std::vector<GatherCand> *cands, std::vector<GatherRecord> *recs, uint64_t *touched,
                        double *kernel_ms, uint64_t *launches);
+// finch_index_attach_counts' share of one handle: the library's `count` column, n = the index's postings u32
+// parallel to its CSR of hashes, uploaded to the handle's device; kept until the handle is closed, replaced by the next call.
+// *device_bytes = what the attachment holds.  Synchronous.
+int index_attach_counts(IndexDevice *d, const uint32_t *counts, uint64_t n, uint64_t *device_bytes);
+// finch_index_compare_counts' chunk: the queries [q0, q1) of `queries`, q1 - q0 <= chunk_queries, `counts` parallel to
+// queries.hashes, min_common >= 1.  Counted as above; the selection reads every touched pair's c, stores 0 back -- the counters
+// are zero again after the second launch -- and keeps the pairs with c >= min_common; the third launch walks each of them
+// (fh_moments.hip: k_index_moments).  *recs = one record per passing pair, in no order, q the caller's index; overwritten.
+// *touched is added the pairs with c > 0, *kernel_ms the kernels' time, *launches one per kernel (3; 2 if no pair passes, 1 if
+// none is touched).  FH_ERR_STATE without attached counts, and where a walk's `common` is not the index's c (the handle stays
+// clean); a failure between the count and the end of the selection leaves the handle dirty.
+int index_compare_counts_chunk(IndexDevice *d, const DistSide &queries, const uint32_t *counts, uint32_t q0, uint32_t q1, uint32_t min_common,
+                               std::vector<MomentsRecord> *recs, uint64_t *touched, double *kernel_ms, uint64_t *launches);
 void index_close(IndexDevice *d);
 
 } // namespace fh

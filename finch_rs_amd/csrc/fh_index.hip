@@ -22,6 +22,10 @@
 //     reference in the posting run of every removed hash, the runs dealt flat over the workgroup as the count deals them.  The
 //     remaining set is a bitmask over query positions in LDS, as in fh_gather.hip; no position arrays are built.  The tail
 //     stores 0 to every touched counter, so the index is clean for the next launch.
+// finch_index_compare_counts walks only the pairs whose count passes:
+//   * k_index_moments_select: per touched pair c is read and 0 stored back; (q, r, c) is appended where c >= min_common;
+//   * k_index_moments (fh_moments.hip, the object without fused multiply-adds): one wave per appended pair, over this file's
+//     arrays and the library's counts that finch_index_attach_counts left beside its hashes.
 // The order in which atomics land decides only where an entry sits in a list; the host sorts.
 #include <hip/hip_runtime.h>
 
@@ -36,6 +40,7 @@
 #include "fh_index.h"
 #include "fh_internal.h"
 #include "fh_kernels.h"
+#include "fh_moments.h"
 
 using namespace fh;
 
@@ -282,6 +287,36 @@ __global__ void __launch_bounds__(THREADS) k_index_gather_candidates(IndexArgs a
     }
 }
 
+// grid: x = query of the chunk.  finch_index_compare_counts' selection: per touched pair c, and 0 back -- the
+// counters are clean after this kernel, whatever the moment walk does --; the entry (q, r, c) where c >= min_common, appended as
+// k_index_finish appends.
+__global__ void __launch_bounds__(THREADS) k_index_moments_select(IndexArgs a, uint32_t min_common, IndexPass *list, uint32_t list_cap,
+                                                                  uint32_t *cursor) {
+    const uint32_t qi = blockIdx.x, n = a.tcount[qi];
+    uint32_t *cnt = a.cnt + (uint64_t)qi * a.nr;
+    const uint32_t *touched = a.touched + (uint64_t)qi * a.nr;
+    for (uint32_t base = 0; base < n; base += THREADS) { // (whole waves go round: the ballot sees every lane)
+        const uint32_t t = base + threadIdx.x;
+        uint32_t r = 0, c = 0;
+        if (t < n) {
+            r = touched[t];
+            if (r < a.nr) c = cnt[r], cnt[r] = 0;
+        }
+        const bool pass = t < n && c >= min_common; // (min_common >= 1: a c of 0 never passes)
+        const uint64_t mask = __ballot(pass);
+        if (!mask) continue;
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        uint32_t first = 0;
+        if (pass && rank == 0) first = atomicAdd(cursor, (uint32_t)__popcll(mask));
+        first = __shfl(first, __ffsll((unsigned long long)mask) - 1, 64);
+        if (pass && first + rank < list_cap) { // (the host sized the list to the chunk's touched pairs)
+            IndexPass e;
+            e.q = a.q0 + qi, e.r = r, e.c = c;
+            list[first + rank] = e;
+        }
+    }
+}
+
 enum { W_BOUND = 0, W_WIN = 1, W_COUNT = 2, W_REF = 3, W_LEN = 4, W_N = 5 };
 
 // (count descending, candidate ascending): does (c2, i2) come before (c1, i1)?  NONE is no candidate
@@ -440,6 +475,13 @@ struct IndexDevice {
     void *gat[5] = {};
     size_t gat_cap[5] = {};
     uint32_t *gwords = nullptr, *gwords_h = nullptr;
+    // finch_index_compare_counts: the library's counts, parallel to lib[0] (finch_index_attach_counts; none until then); grown as
+    // needed: the chunk's counts, its pass list of (q, r, c), the records; the error word with the pair it names, and their
+    // pinned copy
+    uint32_t *rcnt = nullptr;
+    void *cmp[3] = {};
+    size_t cmp_cap[3] = {};
+    uint32_t *cwords = nullptr, *cwords_h = nullptr;
     bool rounds_lds_set = false;  // k_index_gather_rounds may ask for more dynamic LDS than a launch gets unasked
     std::vector<uint32_t> rlen_h; // the library's lengths: what a candidate's `common` is checked against
     hipEvent_t ev[6] = {};
@@ -460,6 +502,11 @@ void index_close(IndexDevice *d) {
         for (void *p : d->gat)
             if (p) (void)hipFree(p);
         if (d->gwords) (void)hipFree(d->gwords);
+        if (d->rcnt) (void)hipFree(d->rcnt);
+        for (void *p : d->cmp)
+            if (p) (void)hipFree(p);
+        if (d->cwords) (void)hipFree(d->cwords);
+        if (d->cwords_h) (void)hipHostFree(d->cwords_h);
         if (d->gwords_h) (void)hipHostFree(d->gwords_h);
         if (d->back_h) (void)hipHostFree(d->back_h);
         for (hipEvent_t e : d->ev)
@@ -802,6 +849,105 @@ int index_gather_chunk(IndexDevice *d, const DistSide &queries, const uint32_t *
         return api_fail(FH_ERR_INVALID, "index_gather_chunk: queries %u..%u of %u, %u per launch", q0, q1, queries.n, d->chunk);
     if (d->dirty) return api_fail(FH_ERR_STATE, "index gather: an earlier call on this index failed between its kernels; build the index again");
     return gather_chunk(d, queries, counts, q0, q1, min_overlap, max_rounds, cands, recs, touched, kernel_ms, launches);
+}
+
+// ---- finch_index_compare_counts ----------------------------------------------------------------------------------------
+
+int index_attach_counts(IndexDevice *d, const uint32_t *counts, uint64_t n, uint64_t *device_bytes) {
+    if (!d || !counts || n != d->n_post)
+        return api_fail(FH_ERR_INVALID, "index_attach_counts: %llu counts for %u postings", (unsigned long long)n, d ? d->n_post : 0);
+    IHIP_TRY(hipSetDevice(d->device));
+    const size_t bytes = (size_t)d->n_post * sizeof(uint32_t);
+    if (!d->rcnt) IHIP_TRY(api_dev_malloc((void **)&d->rcnt, bytes));
+    IHIP_TRY(hipMemcpy(d->rcnt, counts, bytes, hipMemcpyHostToDevice));
+    *device_bytes = bytes;
+    return FH_OK;
+}
+
+// finch_index_compare_counts' chunk: the count as above, the selection that also stores the zeros back, the moment walk.
+static int compare_counts_chunk(IndexDevice *d, const DistSide &q, const uint32_t *counts, uint32_t q0, uint32_t q1, uint32_t min_common,
+                                std::vector<MomentsRecord> *recs, uint64_t *touched, double *kernel_ms, uint64_t *launches) {
+    const uint32_t n = q1 - q0;
+    recs->clear();
+    IHIP_TRY(hipSetDevice(d->device));
+    IndexArgs a;
+    if (int rc = chunk_args(d, &q, q0, q1, &a)) return rc;
+    const uint64_t nh = q.offsets[q1] - a.qbase;
+    if (int rc = grow(&d->cmp[0], &d->cmp_cap[0], nh * sizeof(uint32_t))) return rc;
+    if (nh) IHIP_TRY(hipMemcpy(d->cmp[0], counts + a.qbase, nh * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!d->cwords) {
+        IHIP_TRY(api_dev_malloc((void **)&d->cwords, 3 * sizeof(uint32_t)));
+        IHIP_TRY(api_host_malloc((void **)&d->cwords_h, 3 * sizeof(uint32_t)));
+    }
+
+    // 1. the count; the touched lists' lengths cross, so that the pass list can be sized to what may pass
+    d->dirty = true; // until the selection has stored the zeros back
+    IHIP_TRY(hipEventRecord(d->ev[0], d->stream));
+    hipLaunchKernelGGL(k_index_count, dim3(n), dim3(THREADS), 0, d->stream, a);
+    IHIP_TRY(hipGetLastError());
+    IHIP_TRY(hipEventRecord(d->ev[1], d->stream));
+    IHIP_TRY(hipMemcpyAsync(d->back_h, d->tcount, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    IHIP_TRY(hipStreamSynchronize(d->stream));
+    uint64_t pairs = 0;
+    for (uint32_t i = 0; i < n; ++i) pairs += d->back_h[i];
+    float ms = 0.f;
+    IHIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
+    *kernel_ms += ms;
+    *touched += pairs;
+    *launches += 1;
+    if (pairs == 0) { // (nothing was counted: nothing to store back)
+        d->dirty = false;
+        return FH_OK;
+    }
+
+    // 2. the selection: c, and 0 back; the cursor crosses (pairs <= chunk x nr <= 2^31: index_open)
+    if (int rc = grow(&d->cmp[1], &d->cmp_cap[1], pairs * sizeof(IndexPass))) return rc;
+    IHIP_TRY(hipMemsetAsync(d->cursor, 0, sizeof(uint32_t), d->stream));
+    IHIP_TRY(hipEventRecord(d->ev[2], d->stream));
+    hipLaunchKernelGGL(k_index_moments_select, dim3(n), dim3(THREADS), 0, d->stream, a, min_common, (IndexPass *)d->cmp[1], (uint32_t)pairs,
+                       d->cursor);
+    IHIP_TRY(hipGetLastError());
+    IHIP_TRY(hipEventRecord(d->ev[3], d->stream));
+    IHIP_TRY(hipMemcpyAsync(d->back_h + d->chunk, d->cursor, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    IHIP_TRY(hipStreamSynchronize(d->stream));
+    d->dirty = false; // the counters are clean, whatever the walk does
+    IHIP_TRY(hipEventElapsedTime(&ms, d->ev[2], d->ev[3]));
+    *kernel_ms += ms;
+    *launches += 1;
+    const uint32_t np = d->back_h[d->chunk];
+    if (np > pairs) return api_fail(FH_ERR_STATE, "index compare_counts: %u pairs pass of %llu", np, (unsigned long long)pairs);
+    if (np == 0) return FH_OK;
+
+    // 3. the moment walk, one wave per passing pair; the records at their pairs' places in the pass list
+    if (int rc = grow(&d->cmp[2], &d->cmp_cap[2], (size_t)np * sizeof(MomentsRecord))) return rc;
+    IHIP_TRY(hipMemsetAsync(d->cwords, 0, 3 * sizeof(uint32_t), d->stream));
+    IndexMomentsArgs m;
+    m.qh = a.qh, m.qoff = a.qoff, m.qc = (const uint32_t *)d->cmp[0], m.qbase = a.qbase, m.q0 = q0, m.nq = n;
+    m.rh = a.rh, m.roff = a.roff, m.rc = d->rcnt, m.nr = d->nr;
+    m.pass = (const IndexPass *)d->cmp[1], m.n_pass = np, m.rec = (MomentsRecord *)d->cmp[2], m.err = d->cwords;
+    IHIP_TRY(hipEventRecord(d->ev[4], d->stream));
+    if (int rc = index_moments_launch(m, d->stream)) return rc;
+    IHIP_TRY(hipEventRecord(d->ev[5], d->stream));
+    IHIP_TRY(hipMemcpyAsync(d->cwords_h, d->cwords, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    IHIP_TRY(hipStreamSynchronize(d->stream));
+    IHIP_TRY(hipEventElapsedTime(&ms, d->ev[4], d->ev[5]));
+    *kernel_ms += ms;
+    *launches += 1;
+    if (d->cwords_h[0])
+        return api_fail(FH_ERR_STATE, "index compare_counts: index counters and walk disagree for pair (%u, %u)", d->cwords_h[1], d->cwords_h[2]);
+    recs->resize(np);
+    IHIP_TRY(hipMemcpy(recs->data(), d->cmp[2], (size_t)np * sizeof(MomentsRecord), hipMemcpyDeviceToHost));
+    return FH_OK;
+}
+
+int index_compare_counts_chunk(IndexDevice *d, const DistSide &queries, const uint32_t *counts, uint32_t q0, uint32_t q1, uint32_t min_common,
+                               std::vector<MomentsRecord> *recs, uint64_t *touched, double *kernel_ms, uint64_t *launches) {
+    if (!counts || !min_common || q1 <= q0 || q1 > queries.n || q1 - q0 > d->chunk)
+        return api_fail(FH_ERR_INVALID, "index_compare_counts_chunk: queries %u..%u of %u, %u per launch, min_common %u", q0, q1, queries.n,
+                        d->chunk, min_common);
+    if (!d->rcnt) return api_fail(FH_ERR_STATE, "index compare_counts: no counts are attached to the index (finch_index_attach_counts)");
+    if (d->dirty) return api_fail(FH_ERR_STATE, "index compare_counts: an earlier call on this index failed between its kernels; build the index again");
+    return compare_counts_chunk(d, queries, counts, q0, q1, min_common, recs, touched, kernel_ms, launches);
 }
 
 } // namespace fh

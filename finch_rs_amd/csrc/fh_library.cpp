@@ -1,6 +1,7 @@
 // fh_library.cpp -- the library calls of the C ABI (include/finch_host.h): dist, minmer_matrix, search, the index and its
-// search / dist / gather, gather, compare_counts, merge.  Many sketches against many, on one or several device entries; each
-// call checks its arguments, deals its work over the entries (fh_entries.h) and finishes the device's integers on the host.
+// search / dist / gather / compare_counts, gather, compare_counts, merge.  Many sketches against many, on one or several device
+// entries; each call checks its arguments, deals its work over the entries (fh_entries.h) and finishes the device's integers on
+// the host.
 // Reading, parsing and the single-sketch calls are fh_host.cpp's.
 //
 // Reference items mirrored (relative to the finch-rs tree) are cited at each function.
@@ -653,6 +654,8 @@ struct finch_index {
     uint64_t postings = 0, device_bytes = 0;
     double build_ms = 0.;
     std::vector<fh::IndexDevice *> entries; // one per device entry; none where the library has no hash
+    std::vector<uint32_t> rlen;             // the library's lengths: what finch_index_attach_counts holds its `refs` against
+    bool counts_attached = false;           // finch_index_attach_counts has left the library's counts on every entry
     std::mutex mu;                          // one search at a time: the counters belong to the index
     ~finch_index() {
         if (entries.empty()) return;
@@ -678,7 +681,7 @@ int finch_index_new(const finch_sketches *refs, const int *devices, uint32_t n_d
     if (int rc = check_ascending(Rs, "reference")) return rc;
     auto ix = std::make_unique<finch_index>();
     ix->nr = (uint32_t)Rs.size();
-    for (const Sketch &s : Rs) ix->postings += s.hashes.size();
+    for (const Sketch &s : Rs) ix->postings += s.hashes.size(), ix->rlen.push_back((uint32_t)s.hashes.size());
     const uint64_t max_postings = std::min<uint64_t>(cfg_u64("index_max_postings", fh::INDEX_MAX_POSTINGS), fh::INDEX_MAX_POSTINGS);
     if (ix->postings > max_postings)
         return hfail(FH_ERR_UNSUPPORTED, "reference library: %llu postings (hashes of all %u sketches), an index holds at most %llu",
@@ -1335,6 +1338,8 @@ struct finch_compare_counts_result {
     std::vector<finch_count_moments> rows;
     double kernel_ms = 0.;
     uint64_t launches = 0, copied = 0;
+    bool from_index = false; // made by finch_index_compare_counts: `touched` = the pairs its device counted
+    uint64_t touched = 0;
 };
 
 namespace {
@@ -1399,6 +1404,58 @@ FH_NO_CONTRACT_ATTR void compare_counts_walk(const std::vector<KmerCount> &refer
     moments_finish(common, query_m2, query_m3, query_m4, out);
 }
 
+// a launch's records and the pairs it covered: queries [q0, q1) x references [r0, r1)
+struct MomentsFound {
+    std::vector<fh::MomentsRecord> recs;
+    uint32_t q0 = 0, q1 = 0, r0 = 0, r1 = 0;
+};
+
+// what finch_compare_counts and finch_index_compare_counts do with the records the device left (`found`: lists in any order,
+// emptied here): by query, each query's sorted by reference; the three doubles are moments_finish's, as the pair call has them
+int compare_counts_finish(std::vector<MomentsFound> &found, uint32_t nq, uint32_t nr, finch_compare_counts_result *res) {
+    // the device's lists have no order: the records by query (a counting pass), each query's by reference index
+    std::vector<uint64_t> at((size_t)nq + 1, 0);
+    for (size_t k = 0; k < found.size(); ++k)
+        for (const fh::MomentsRecord &x : found[k].recs) {
+            if (x.q < found[k].q0 || x.q >= found[k].q1 || x.r < found[k].r0 || x.r >= found[k].r1)
+                return hfail(FH_ERR_STATE, "compare_counts: record (%u, %u) in chunk %zu of %u x %u", x.q, x.r, k, nq, nr);
+            ++at[x.q + 1];
+        }
+    for (uint32_t q = 0; q < nq; ++q) at[q + 1] += at[q];
+    const uint64_t total = at[nq];
+    std::vector<fh::MomentsRecord> recs(total);
+    {
+        std::vector<uint64_t> fill(at.begin(), at.end() - 1);
+        for (auto &f : found) {
+            for (const fh::MomentsRecord &x : f.recs) recs[fill[x.q]++] = x;
+            std::vector<fh::MomentsRecord>().swap(f.recs);
+        }
+    }
+    res->q.resize(total);
+    res->r.resize(total);
+    res->rows.resize(total);
+    const unsigned T = (unsigned)std::min<uint64_t>(DIST_MAX_ENTRIES, std::max<uint64_t>(1, total >> 16));
+    const uint32_t per = (nq + T - 1) / T;
+    fork_join(T, [&](unsigned t) {
+        for (uint32_t q = std::min(nq, t * per); q < std::min<uint64_t>(nq, (uint64_t)(t + 1) * per); ++q) {
+            std::sort(recs.begin() + at[q], recs.begin() + at[q + 1], [](const fh::MomentsRecord &a, const fh::MomentsRecord &b) { return a.r < b.r; });
+            for (uint64_t o = at[q]; o < at[q + 1]; ++o) {
+                const fh::MomentsRecord &x = recs[o];
+                finch_count_moments &row = res->rows[o];
+                res->q[o] = x.q;
+                res->r[o] = x.r;
+                row.common = x.common;
+                row.ref_pos = x.ref_pos;
+                row.query_pos = x.query_pos;
+                row.ref_count = x.ref_count;
+                row.query_count = x.query_count;
+                moments_finish(x.common, x.m2, x.m3, x.m4, &row);
+            }
+        }
+    });
+    return FH_OK;
+}
+
 constexpr uint64_t CMPC_CHUNK_PAIRS = 4u << 20; // pairs per launch: 256 MiB of records per list if every pair passes
 
 } // namespace
@@ -1442,7 +1499,8 @@ int finch_compare_counts(const finch_sketches *refs, const finch_sketches *queri
     const uint32_t slice = (uint32_t)std::min<uint64_t>(cfg_u64("cmpc_slice", fh::MOMENTS_MAX_SLICE), fh::MOMENTS_MAX_SLICE);
     // a sketch has fewer than 2^32 - 1 hashes, so no pair reaches a threshold above that
     const uint32_t min_c = (uint32_t)std::min<uint64_t>(min_common, UINT32_MAX);
-    std::vector<std::vector<fh::MomentsRecord>> found(n_chunks);
+    std::vector<MomentsFound> found(n_chunks);
+    for (uint32_t k = 0; k < n_chunks; ++k) found[k].q0 = 0, found[k].q1 = nq, found[k].r0 = k * per_chunk, found[k].r1 = std::min(nr, k * per_chunk + per_chunk);
     fh::EntryError err;
     std::mutex stat_mu;
 
@@ -1466,7 +1524,7 @@ int finch_compare_counts(const finch_sketches *refs, const finch_sketches *queri
             if (int rc = fh::moments_wait(md, slot, &recs, &n, &ms)) return rc;
             ms_sum += ms;
             copied += n;
-            found[mine[m]].assign(recs, recs + n);
+            found[mine[m]].recs.assign(recs, recs + n);
             return FH_OK;
         };
         entry_failed(err, fh::two_slot(mine.size(), err, launch, take));
@@ -1477,47 +1535,7 @@ int finch_compare_counts(const finch_sketches *refs, const finch_sketches *queri
     });
     if (err.failed()) return hfail(err.rc(), "%s", err.msg().c_str());
 
-    // the device's lists have no order: the records by query (a counting pass), each query's by reference index
-    std::vector<uint64_t> at((size_t)nq + 1, 0);
-    for (uint32_t k = 0; k < n_chunks; ++k) {
-        const uint32_t r0 = k * per_chunk, r1 = std::min(nr, r0 + per_chunk);
-        for (const fh::MomentsRecord &x : found[k]) {
-            if (x.q >= nq || x.r < r0 || x.r >= r1) return hfail(FH_ERR_STATE, "compare_counts: record (%u, %u) in chunk %u of %u x %u", x.q, x.r, k, nq, nr);
-            ++at[x.q + 1];
-        }
-    }
-    for (uint32_t q = 0; q < nq; ++q) at[q + 1] += at[q];
-    const uint64_t total = at[nq];
-    std::vector<fh::MomentsRecord> recs(total);
-    {
-        std::vector<uint64_t> fill(at.begin(), at.end() - 1);
-        for (auto &f : found) {
-            for (const fh::MomentsRecord &x : f) recs[fill[x.q]++] = x;
-            std::vector<fh::MomentsRecord>().swap(f);
-        }
-    }
-    res->q.resize(total);
-    res->r.resize(total);
-    res->rows.resize(total);
-    const unsigned T = (unsigned)std::min<uint64_t>(DIST_MAX_ENTRIES, std::max<uint64_t>(1, total >> 16));
-    const uint32_t per = (nq + T - 1) / T;
-    fork_join(T, [&](unsigned t) {
-        for (uint32_t q = std::min(nq, t * per); q < std::min<uint64_t>(nq, (uint64_t)(t + 1) * per); ++q) {
-            std::sort(recs.begin() + at[q], recs.begin() + at[q + 1], [](const fh::MomentsRecord &a, const fh::MomentsRecord &b) { return a.r < b.r; });
-            for (uint64_t o = at[q]; o < at[q + 1]; ++o) {
-                const fh::MomentsRecord &x = recs[o];
-                finch_count_moments &row = res->rows[o];
-                res->q[o] = x.q;
-                res->r[o] = x.r;
-                row.common = x.common;
-                row.ref_pos = x.ref_pos;
-                row.query_pos = x.query_pos;
-                row.ref_count = x.ref_count;
-                row.query_count = x.query_count;
-                moments_finish(x.common, x.m2, x.m3, x.m4, &row);
-            }
-        }
-    });
+    if (int rc = compare_counts_finish(found, nq, nr, res.get())) return rc;
     *out = res.release();
     return FH_OK;
 } FINCH_CATCH
@@ -1542,6 +1560,108 @@ int finch_compare_counts_stats(const finch_compare_counts_result *r, double *ker
 } FINCH_CATCH
 
 void finch_compare_counts_free(finch_compare_counts_result *r) { delete r; }
+
+// compare_counts through the library index (fh_index.hip, fh_moments.hip): a row needs common >= min_common
+// >= 1, the index's count leaves common = |Q n R| of every pair that shares a hash, and only the pairs that pass are walked;
+// their records come through finch_compare_counts' own finish.  The index holds the library's hashes; its counts are attached
+// here, once.
+int finch_index_attach_counts(const finch_index *cix, const finch_sketches *refs, uint64_t *device_bytes) try {
+    if (!cix || !refs) return hfail(FH_ERR_INVALID, "null argument");
+    finch_index *ix = const_cast<finch_index *>(cix); // (the attachment is the index's; `mu` serialises its use)
+    const std::vector<Sketch> &Rs = refs->v;
+    uint64_t postings = 0;
+    for (const Sketch &s : Rs) postings += s.hashes.size();
+    if (Rs.size() != ix->nr || postings != ix->postings)
+        return hfail(FH_ERR_INVALID, "finch_index_attach_counts: refs has %zu sketches and %llu hashes, the index was built from %u and %llu: "
+                                     "refs must be the library of the index", Rs.size(), (unsigned long long)postings, ix->nr,
+                     (unsigned long long)ix->postings);
+    for (uint32_t r = 0; r < ix->nr; ++r)
+        if (Rs[r].hashes.size() != ix->rlen[r])
+            return hfail(FH_ERR_INVALID, "finch_index_attach_counts: refs sketch %u (%s) has %zu hashes, the index was built from one of %u: "
+                                         "refs must be the library of the index", r, Rs[r].name.c_str(), Rs[r].hashes.size(), ix->rlen[r]);
+    std::lock_guard<std::mutex> one_call(ix->mu);
+    uint64_t total = 0;
+    if (!ix->entries.empty()) { // (a library without a hash: nothing to attach, no device)
+        DeviceGuard restore_device;
+        std::vector<uint32_t> counts;
+        counts.reserve(postings);
+        for (const Sketch &s : Rs)
+            for (const KmerCount &h : s.hashes) counts.push_back(h.count);
+        ix->counts_attached = false; // until every entry has the new counts
+        for (fh::IndexDevice *d : ix->entries) {
+            uint64_t bytes = 0;
+            if (int rc = fh::index_attach_counts(d, counts.data(), counts.size(), &bytes)) return hfail(rc, "%s", fh_last_error());
+            total += bytes;
+        }
+        ix->counts_attached = true;
+    }
+    if (device_bytes) *device_bytes = total;
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_index_compare_counts(const finch_index *cix, const finch_sketches *queries, uint64_t min_common,
+                               finch_compare_counts_result **out) try {
+    if (!cix || !queries || !out) return hfail(FH_ERR_INVALID, "null argument");
+    finch_index *ix = const_cast<finch_index *>(cix); // (the launch state is the index's; `mu` serialises its use)
+    if (min_common == 0)
+        return hfail(FH_ERR_INVALID, "finch_index_compare_counts: min_common 0: an index finds only the pairs that share a hash, and a "
+                                     "threshold of 0 keeps every pair -- use finch_compare_counts");
+    const std::vector<Sketch> &Qs = queries->v;
+    if (int rc = check_ascending(Qs, "query")) return rc;
+    const uint32_t nq = (uint32_t)Qs.size();
+    auto res = std::make_unique<finch_compare_counts_result>();
+    res->from_index = true;
+    if (nq == 0 || ix->entries.empty()) {
+        *out = res.release();
+        return FH_OK;
+    }
+    std::lock_guard<std::mutex> one_call(ix->mu);
+    if (!ix->counts_attached)
+        return hfail(FH_ERR_STATE, "finch_index_compare_counts: the index holds the library's hashes, not its counts -- call "
+                                   "finch_index_attach_counts first");
+    DeviceGuard restore_device;
+
+    // a sketch has fewer than 2^32 - 1 hashes, so no pair reaches a threshold above that
+    const uint32_t min_c = (uint32_t)std::min<uint64_t>(min_common, UINT32_MAX);
+    DistCsr qc;
+    qc.build(Qs, false, true);
+    const uint32_t n_chunks = (nq + ix->chunk - 1) / ix->chunk;
+    const uint32_t n_entries = (uint32_t)std::min<size_t>(ix->entries.size(), n_chunks);
+    std::vector<MomentsFound> found(n_chunks);
+    fh::EntryError err;
+    std::mutex stat_mu;
+
+    // one thread per device entry: chunks of queries e, e + n_entries, ...
+    fh::for_entries(n_entries, err, FH_ERR_CAPACITY, [&](unsigned e) {
+        double ms_sum = 0.;
+        uint64_t touched = 0, copied = 0, launches = 0;
+        for (uint32_t k = e; k < n_chunks && !err.failed(); k += n_entries) {
+            MomentsFound &f = found[k];
+            f.q0 = k * ix->chunk, f.q1 = (uint32_t)std::min<uint64_t>(nq, (uint64_t)f.q0 + ix->chunk), f.r0 = 0, f.r1 = ix->nr;
+            if (entry_failed(err, fh::index_compare_counts_chunk(ix->entries[e], qc.view(), qc.counts.data(), f.q0, f.q1, min_c, &f.recs, &touched,
+                                                                 &ms_sum, &launches)))
+                break;
+            copied += f.recs.size();
+        }
+        std::lock_guard<std::mutex> g(stat_mu);
+        res->kernel_ms += ms_sum;
+        res->launches += launches;
+        res->copied += copied;
+        res->touched += touched;
+    });
+    if (err.failed()) return hfail(err.rc(), "%s", err.msg().c_str());
+    if (int rc = compare_counts_finish(found, nq, ix->nr, res.get())) return rc;
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_index_compare_counts_stats(const finch_compare_counts_result *r, uint64_t *pairs_touched, uint64_t *pairs_walked) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    if (!r->from_index) return hfail(FH_ERR_INVALID, "finch_index_compare_counts_stats: the result was not made by finch_index_compare_counts");
+    if (pairs_touched) *pairs_touched = r->touched;
+    if (pairs_walked) *pairs_walked = r->copied; // (the moment kernel walks exactly the pairs whose records cross)
+    return FH_OK;
+} FINCH_CATCH
 
 } // extern "C"
 

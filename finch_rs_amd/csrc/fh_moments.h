@@ -41,4 +41,27 @@ int moments_launch(MomentsDevice *d, int buf, uint32_t r0, uint32_t r1);
 int moments_wait(MomentsDevice *d, int buf, const MomentsRecord **records, uint64_t *n, double *kernel_ms);
 void moments_close(MomentsDevice *d);
 
+// finch_index_compare_counts' moment walk: k_index_moments, launched by fh_index.hip over arrays the index
+// owns.  A pair that passed the index's selection: q is the caller's index, c the index's |Q n R| (> 0: neither side is empty).
+struct IndexPass {
+    uint32_t q, r, c;
+};
+// All pointers are device memory.  The chunk's queries as the index's kernels have them: hashes and counts from qbase on,
+// qoff[0 .. nq] as the whole call has them, q0 the chunk's first query; the library's CSR with the attached counts.
+struct IndexMomentsArgs {
+    const uint64_t *qh, *qoff;
+    const uint32_t *qc;
+    uint64_t qbase;
+    uint32_t q0, nq;
+    const uint64_t *rh, *roff;
+    const uint32_t *rc;
+    uint32_t nr;
+    const IndexPass *pass; // n_pass pairs ...
+    uint32_t n_pass;
+    MomentsRecord *rec;    // ... and the record of pair p at rec[p]
+    uint32_t *err;         // three words, zero before the launch: set; q and r of a pair whose walk is not what its entry says
+};
+// async on `stream` (a hipStream_t): one wave per pair walks the shorter side, 64 entries a step, and searches the longer one
+int index_moments_launch(const IndexMomentsArgs &a, void *stream);
+
 } // namespace fh

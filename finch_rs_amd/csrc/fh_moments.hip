@@ -15,6 +15,9 @@
 //     in hash order, and each reference's running state waits in LDS between slices;
 //   * after the last slice one wave ballots the block's pairs that pass common >= min_common, takes their places in the chunk's
 //     list with one atomic add and writes a 64-byte record per pair.
+// finch_index_compare_counts has the pairs that pass before anything is walked -- the index counted them --:
+// k_index_moments gives each a wave, which walks the shorter side from global memory and searches the longer one; no LDS, no
+// slices, the same recurrence.
 // The recurrence is IEEE double arithmetic as written: no contraction into fused multiply-adds in this file, no fast-math flag
 // in the build.
 #include <hip/hip_runtime.h>
@@ -24,6 +27,7 @@
 #include <vector>
 
 #include "../../include/finch_hip.h"
+#include "fh_dist_dev.h"
 #include "fh_internal.h"
 #include "fh_moments.h"
 
@@ -174,9 +178,81 @@ __global__ void __launch_bounds__(THREADS) k_compare_counts(MomentsArgs a) {
     }
 }
 
+// finch_index_compare_counts.  grid-stride over the pass list, one wave per pair, no LDS: the wave walks the
+// shorter side, 64 consecutive entries a step, one per lane, and each lane looks its hash up in the longer side with the
+// clamped bound search over global memory (no read leaves either side).  Lanes ascend with the walked side's hashes and steps
+// ascend, so the ballot's bits from low to high are hash order whichever side is walked; the recurrence is k_compare_counts':
+// every lane advances the same scalars with the match's query count.  The record goes to the pair's own place in the list.
+__global__ void __launch_bounds__(THREADS) k_index_moments(IndexMomentsArgs a) {
+#pragma clang fp contract(off)
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // (what follows is the same in every lane)
+    for (uint32_t p = blockIdx.x * WAVES + wave; p < a.n_pass; p += gridDim.x * WAVES) {
+        const IndexPass e = a.pass[p];
+        const uint32_t b = e.q - a.q0;
+        PairState st = {};
+        bool bad = b >= a.nq || e.r >= a.nr;
+        if (!bad) {
+            const uint64_t qa = a.qoff[b], ra = a.roff[e.r];
+            const uint32_t nqh = (uint32_t)(a.qoff[b + 1] - qa), nrh = (uint32_t)(a.roff[e.r + 1] - ra);
+            bad = !nqh || !nrh; // (c > 0: neither side is empty)
+            if (!bad) {
+                const uint64_t *Q = a.qh + (qa - a.qbase), *R = a.rh + ra;
+                const uint32_t *QC = a.qc + (qa - a.qbase), *RC = a.rc + ra;
+                const bool walk_q = nqh <= nrh;
+                const uint64_t *W = walk_q ? Q : R, *S = walk_q ? R : Q; // walked, searched
+                const uint32_t *WC = walk_q ? QC : RC, *SC = walk_q ? RC : QC;
+                const uint32_t nw = walk_q ? nqh : nrh, ns = walk_q ? nrh : nqh;
+                const uint32_t stop = 1u << (31 - __clz(ns));
+                uint64_t wsum = 0, ssum = 0;
+                for (uint32_t t0 = 0; t0 < nw; t0 += 64) { // (whole waves go round: the ballot sees every lane)
+                    const uint32_t t = t0 + lane;
+                    const bool valid = t < nw;
+                    const uint64_t x = valid ? W[t] : 0;
+                    const uint32_t pos = count_below<true>(S, ns, stop, x);
+                    const uint32_t at = pos ? pos - 1 : 0;
+                    const bool match = valid && pos && S[at] == x;
+                    const uint32_t wcnt = match ? WC[t] : 0, scnt = match ? SC[at] : 0;
+                    wsum += wcnt, ssum += scnt;
+                    const uint32_t qcnt = walk_q ? wcnt : scnt;
+                    uint64_t mask = __ballot(match);
+                    while (mask) {
+                        const int bit = __ffsll((unsigned long long)mask) - 1;
+                        mask &= mask - 1;
+                        moment_step(st, (uint32_t)__shfl((int)qcnt, bit, 64));
+                    }
+                }
+                wsum = wave_sum64(wsum), ssum = wave_sum64(ssum);
+                st.query_count = walk_q ? wsum : ssum;
+                st.ref_count = walk_q ? ssum : wsum;
+                st.ref_pos = count_below<true>(R, nrh, 1u << (31 - __clz(nrh)), Q[nqh - 1]); // #{r <= max Q}
+                st.query_pos = count_below<true>(Q, nqh, 1u << (31 - __clz(nqh)), R[nrh - 1]); // #{q <= max R}
+                bad = st.common != e.c;
+            }
+        }
+        if (lane == 0) {
+            if (bad && atomicCAS(&a.err[0], 0u, 1u) == 0) a.err[1] = e.q, a.err[2] = e.r; // (the first such pair is named)
+            MomentsRecord rec;
+            rec.q = e.q, rec.r = e.r, rec.common = st.common, rec.ref_pos = st.ref_pos, rec.query_pos = st.query_pos, rec.pad = 0;
+            rec.ref_count = st.ref_count, rec.query_count = st.query_count;
+            rec.m2 = st.m2, rec.m3 = st.m3, rec.m4 = st.m4;
+            a.rec[p] = rec;
+        }
+    }
+}
+
 } // namespace
 
 namespace fh {
+
+int index_moments_launch(const IndexMomentsArgs &a, void *stream) {
+    if (!a.n_pass || !a.pass || !a.rec || !a.err || !a.qc || !a.rc)
+        return api_fail(FH_ERR_INVALID, "index_moments_launch: %u pairs, or an array is missing", a.n_pass);
+    const uint32_t blocks = std::min<uint32_t>((a.n_pass + WAVES - 1) / WAVES, 8192u); // (a grid-stride loop takes the rest)
+    hipLaunchKernelGGL(k_index_moments, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, a);
+    CHIP_TRY(hipGetLastError());
+    return FH_OK;
+}
 
 struct MomentsDevice {
     int device = 0;

@@ -171,6 +171,9 @@ _SYMS["finch_compare_counts_len"] = (C.c_uint64, [_P])
 _SYMS["finch_compare_counts_copy"] = (C.c_int, [_P, _P, _P, _P])
 _SYMS["finch_compare_counts_stats"] = (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _SYMS["finch_compare_counts_free"] = (None, [_P])
+_SYMS["finch_index_attach_counts"] = (C.c_int, [_P, _P, C.POINTER(C.c_uint64)])
+_SYMS["finch_index_compare_counts"] = (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)])
+_SYMS["finch_index_compare_counts_stats"] = (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _SYMS["finch_merge_pair"] = (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(_P)])
 _SYMS["finch_merge_groups"] = (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P),
                                          C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)])
@@ -776,6 +779,29 @@ class LibraryIndex:
         _check(lib().finch_index_gather(self._handle(), queries._p, int(min_overlap), int(max_rounds), C.byref(p)))
         return _gather_rows(p, len(queries), stats, from_index=True)
 
+    def attach_counts(self) -> int:
+        """the `count` column of the library to every device entry of the index (finch_index_attach_counts), which holds only the
+        hashes until then; calling it again replaces what is there -> the bytes the attachment holds"""
+        nb = C.c_uint64()
+        _check(lib().finch_index_attach_counts(self._handle(), self.refs._p, C.byref(nb)))
+        self._counts_attached = True
+        return nb.value
+
+    def compare_counts(self, queries: Sketches, min_common: int = 1, stats: Optional[dict] = None) -> np.ndarray:
+        """compare_counts(refs, queries, min_common)'s rows, byte for byte, for min_common >= 1 (FinchError below that: the index
+        cannot see the pairs that share nothing); only the pairs that pass are walked (finch_index_compare_counts).  The
+        library's counts are attached on first use.  `stats` receives compare_counts()'s figures, pairs_touched (the pairs the
+        device counted) and pairs_walked (the pairs whose moments it computed)"""
+        if int(min_common) < 1:
+            raise FinchError("LibraryIndex.compare_counts: min_common %d keeps pairs that share nothing, which an index cannot "
+                             "enumerate -- use compare_counts" % int(min_common))
+        h = self._handle()
+        if not getattr(self, "_counts_attached", False):
+            self.attach_counts()
+        p = _P()
+        _check(lib().finch_index_compare_counts(h, queries._p, min(int(min_common), 2 ** 64 - 1), C.byref(p)))
+        return _counts_rows(p, stats, from_index=True)
+
     def best_match(self, queries: Sketches, iq: int = 0) -> int:
         """best_match(refs, queries, iq): a top-1 search at the smallest positive threshold; a query that shares nothing with
         the library has no row and gets index 0, as the tie rule gives it there"""
@@ -861,6 +887,30 @@ def compare_counts_pair(refs: Sketches, ir: int, queries: Sketches, iq: int):
     return (m.common, m.ref_pos, m.query_pos, m.ref_count, m.query_count, m.var, m.skew, m.kurt)
 
 
+def _counts_rows(p, stats: Optional[dict], from_index: bool = False) -> np.ndarray:
+    """the COUNTS_DTYPE rows of a finch_compare_counts_result, which is freed here"""
+    L = lib()
+    try:
+        n = L.finch_compare_counts_len(p)
+        qi, ri, m = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, _CMOMENTS_DTYPE)
+        _check(L.finch_compare_counts_copy(p, ri.ctypes.data, qi.ctypes.data, m.ctypes.data))
+        if stats is not None:
+            ms, nl, nc = C.c_double(), C.c_uint64(), C.c_uint64()
+            _check(L.finch_compare_counts_stats(p, C.byref(ms), C.byref(nl), C.byref(nc)))
+            stats.update(kernel_ms=ms.value, launches=nl.value, records_copied=nc.value)
+            if from_index:
+                nt, nw = C.c_uint64(), C.c_uint64()
+                _check(L.finch_index_compare_counts_stats(p, C.byref(nt), C.byref(nw)))
+                stats.update(pairs_touched=nt.value, pairs_walked=nw.value)
+    finally:
+        L.finch_compare_counts_free(p)
+    rows = np.empty(n, COUNTS_DTYPE)
+    rows["query"], rows["reference"] = qi, ri
+    for f in _CMOMENTS_DTYPE.names:
+        rows[f] = m[f]
+    return rows
+
+
 def compare_counts(refs: Sketches, queries: Sketches, min_common: int = 0, devices: Sequence[int] = (0,),
                    stats: Optional[dict] = None) -> np.ndarray:
     """Sketch.compare_counts for every (query, reference) pair with common >= min_common, on the GPU: COUNTS_DTYPE rows ordered by
@@ -871,21 +921,7 @@ def compare_counts(refs: Sketches, queries: Sketches, min_common: int = 0, devic
     darr = (C.c_int * len(devs))(*devs)
     p = _P()
     _check(L.finch_compare_counts(refs._p, queries._p, int(min_common), darr, len(devs), C.byref(p)))
-    try:
-        n = L.finch_compare_counts_len(p)
-        qi, ri, m = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, _CMOMENTS_DTYPE)
-        _check(L.finch_compare_counts_copy(p, ri.ctypes.data, qi.ctypes.data, m.ctypes.data))
-        if stats is not None:
-            ms, nl, nc = C.c_double(), C.c_uint64(), C.c_uint64()
-            _check(L.finch_compare_counts_stats(p, C.byref(ms), C.byref(nl), C.byref(nc)))
-            stats.update(kernel_ms=ms.value, launches=nl.value, records_copied=nc.value)
-    finally:
-        L.finch_compare_counts_free(p)
-    rows = np.empty(n, COUNTS_DTYPE)
-    rows["query"], rows["reference"] = qi, ri
-    for f in _CMOMENTS_DTYPE.names:
-        rows[f] = m[f]
-    return rows
+    return _counts_rows(p, stats)
 
 
 def merge_pair(a: Sketches, ia: int, b: Sketches, ib: int, size: Optional[int] = None) -> Sketches:

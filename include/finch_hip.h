@@ -93,8 +93,10 @@ const char *fh_last_error(void);
  * 15: fh_batch_new_wide and the rest of 14 unchanged, plus finch_index_new, finch_index_search, finch_index_stats,
  * finch_index_search_stats and finch_index_free in finch_host.h and the options index_chunk_queries, index_max_postings;
  * 16: fh_batch_new_wide and the rest of 15 unchanged, plus finch_index_dist and finch_index_dist_stats in finch_host.h;
- * 17: fh_batch_new_wide and the rest of 16 unchanged, plus finch_index_gather and finch_index_gather_stats in finch_host.h) */
-#define FH_ABI_VERSION 17
+ * 17: fh_batch_new_wide and the rest of 16 unchanged, plus finch_index_gather and finch_index_gather_stats in finch_host.h;
+ * 18: fh_batch_new_wide and the rest of 17 unchanged, plus finch_index_attach_counts, finch_index_compare_counts and
+ * finch_index_compare_counts_stats in finch_host.h) */
+#define FH_ABI_VERSION 18
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---

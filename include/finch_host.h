@@ -402,6 +402,41 @@ int finch_compare_counts_copy(const finch_compare_counts_result *r, uint32_t *re
 int finch_compare_counts_stats(const finch_compare_counts_result *r, double *kernel_ms, uint64_t *launches, uint64_t *records_copied);
 void finch_compare_counts_free(finch_compare_counts_result *r);
 
+/* compare_counts through the index: the same rows at a cost that follows the pairs that share a hash, and a moment walk for the
+ * pairs that pass only.  THE CONTRACT: for min_common >= 1, finch_index_compare_counts(ix, queries, min_common) returns byte for
+ * byte what finch_compare_counts(refs, queries, min_common, ...) returns for the library the index was built from, with the
+ * counts that were attached -- the rows, the query and reference indices, their order; doubles as bit patterns, NaNs as the
+ * dense call produces them.  The result is a finch_compare_counts_result, read with finch_compare_counts_len / _copy / _stats and
+ * freed with finch_compare_counts_free; it is made by the host code that makes the dense call's.
+ * finch_index_attach_counts: the index keeps the library's hashes, not its abundances, and ref_count needs them.  The call
+ *   uploads the `count` column of `refs` to every device entry of the index -- 4 bytes per posting, parallel to the index's CSR of
+ *   hashes --, where it stays until finch_index_free; a second call replaces it.  `refs` must be the library the index was built
+ *   from: FH_ERR_INVALID for another number of sketches or hashes (in finch_index_dist's words) and for a sketch of another length
+ *   (named).  *device_bytes (may be NULL) = what the attachment holds, summed over the entries; finch_index_stats is unchanged.
+ *   An index of a library without a hash attaches nothing and needs no device.  One call at a time runs on an index.
+ * finch_index_compare_counts: queries are dealt over the index's device entries in chunks of index_chunk_queries, as
+ *   finch_index_search deals them.  Per chunk, up to three launches: finch_index_search's count, which leaves c = |Q n R| in the
+ *   query's counter of every reference that shares a hash; a selection that reads c, stores 0 back and keeps (q, r, c) where
+ *   c >= min_common; and the moment walk, one wave per kept pair over the shorter side, whose 64-byte records are all that
+ *   crosses to the host.  Decided before any device is touched: FH_ERR_INVALID for a null argument, for min_common == 0 (which
+ *   keeps every pair, and an index cannot enumerate those: use finch_compare_counts) and for a query whose hashes are not strictly
+ *   ascending (named); FH_ERR_UNSUPPORTED for a sketch of 2^32 - 1 hashes or more; FH_ERR_STATE where the library has hashes and
+ *   no counts are attached (finch_index_attach_counts is named).  min_common above 2^32 - 1 is 2^32 - 1, as in the dense call.
+ *   Zero queries, or an index of a library without a hash: FH_OK, no rows, no device needed.  FH_ERR_STATE, never a wrong row,
+ *   where a walk's common is not the index's c ("index counters and walk disagree for pair (q, r)"; the counters are clean all
+ *   the same), and for every call after one that failed between the count and the end of the selection: the index must be built
+ *   again.  No pairwise form; plain set semantics over the hashes as stored, as compare_counts is.  The caller's current device
+ *   is the same after the call.
+ * finch_compare_counts_stats on the result: kernel_ms = all kernels of the call, launches = kernel launches (three per chunk
+ *   of queries; two where no pair passes, one where none shares a hash), records_copied = exactly the pairs with
+ *   common >= min_common.
+ * finch_index_compare_counts_stats: pairs_touched = the pairs the device counted (c > 0), pairs_walked = the pairs the moment
+ *   kernel walked (= records_copied).  FH_ERR_INVALID, outputs untouched, for a result that finch_compare_counts made. */
+int finch_index_attach_counts(const finch_index *ix, const finch_sketches *refs, uint64_t *device_bytes);
+int finch_index_compare_counts(const finch_index *ix, const finch_sketches *queries, uint64_t min_common,
+                               finch_compare_counts_result **out);
+int finch_index_compare_counts_stats(const finch_compare_counts_result *r, uint64_t *pairs_touched, uint64_t *pairs_walked);
+
 /* merge (Sketch.merge: merge_sketches, lib/src/python.rs:24-100).  Not fh_merge, the sharded sketcher's union of partial
  * sketches, which saturates, keeps the bottom n and both tails.  merge(first, second, size) is, in this order:
  *   1. seq_length and num_valid_kmers of the two added (u64, wrapping);
