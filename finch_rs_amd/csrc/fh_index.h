@@ -46,6 +46,8 @@ int index_gather_chunk(IndexDevice *d, const DistSide &queries, const uint32_t *
 // parallel to its CSR of hashes, uploaded to the handle's device; kept until the handle is closed, replaced by the next call.
 // *device_bytes = what the attachment holds.  Synchronous.
 int index_attach_counts(IndexDevice *d, const uint32_t *counts, uint64_t n, uint64_t *device_bytes);
+// frees what index_attach_counts left on the handle, if anything: the handle is as before its first attachment.  Cannot fail.
+void index_drop_counts(IndexDevice *d);
 // finch_index_compare_counts' chunk: the queries [q0, q1) of `queries`, q1 - q0 <= chunk_queries, `counts` parallel to
 // queries.hashes, min_common >= 1.  Counted as above; the selection reads every touched pair's c, stores 0 back -- the counters
 // are zero again after the second launch -- and keeps the pairs with c >= min_common; the third launch walks each of them
@@ -55,6 +57,25 @@ int index_attach_counts(IndexDevice *d, const uint32_t *counts, uint64_t n, uint
 // clean); a failure between the count and the end of the selection leaves the handle dirty.
 int index_compare_counts_chunk(IndexDevice *d, const DistSide &queries, const uint32_t *counts, uint32_t q0, uint32_t q1, uint32_t min_common,
                                std::vector<MomentsRecord> *recs, uint64_t *touched, double *kernel_ms, uint64_t *launches);
+// finch_index_add / finch_index_keep on one handle, in two phases.  index_add / index_keep build the updated
+// library's arrays BESIDE those in use -- peak device memory is old + new -- and leave the handle answering as before; index_commit
+// swaps them in and frees the old ones, and cannot fail; index_discard drops them.  A failed build has discarded its own.
+// chunk_queries: the counters of the updated library are allocated afresh for it, zeroed, and a dirty handle comes out clean.
+// tile: output postings per tile of the update kernels, 1..2048 (option index_update_tile).  *kernel_ms is added the update
+// kernels' time (HIP events).  Synchronous; the caller holds the index's lock from the first build to the last commit.
+//   index_add: `more`'s sketches become the references nr .. nr + more.n - 1.  Their postings are formed, sorted (stable) and
+//   merged into the index's by a tiled merge path; on equal hashes every old reference precedes every new one.  The CSR and the
+//   per-reference arrays are extended device to device plus the new part from the host; `counts`, parallel to more.hashes, are
+//   appended where counts are attached (required then, ignored otherwise).  The grown library has at most INDEX_MAX_POSTINGS.
+//   index_keep: keep[0 .. n_keep) strictly ascending and below nr; the survivors become 0 .. n_keep - 1.  A stable device-wide
+//   compaction of the postings (tile counts, their scan, a scatter that renames the references), and a kernel that moves each
+//   survivor's hashes (and counts) and gathers its per-reference values.  At least one hash must survive: a library without
+//   one has no handle (the caller closes it).
+int index_add(IndexDevice *d, const DistSide &more, const uint32_t *counts, uint32_t chunk_queries, uint32_t tile, double *kernel_ms);
+int index_keep(IndexDevice *d, const uint32_t *keep, uint32_t n_keep, uint32_t chunk_queries, uint32_t tile, double *kernel_ms);
+// -> the device memory the handle keeps allocated, as index_open counts it
+uint64_t index_commit(IndexDevice *d);
+void index_discard(IndexDevice *d);
 void index_close(IndexDevice *d);
 
 } // namespace fh

@@ -27,6 +27,13 @@
 //   * k_index_moments (fh_moments.hip, the object without fused multiply-adds): one wave per appended pair, over this file's
 //     arrays and the library's counts that finch_index_attach_counts left beside its hashes.
 // The order in which atomics land decides only where an entry sits in a list; the host sorts.
+// finch_index_add / finch_index_keep change the library in place, and there order is the contract -- the
+// postings they leave are the postings a build leaves:
+//   * k_index_merge: the added sketches' postings, sorted like the build's, merged into the index's by a tiled merge path
+//     (fh_merge_path.h); on equal hashes every old reference before every new one;
+//   * k_index_compact / k_index_tile_scan: the postings of the kept references, in their order, renamed; places from scans;
+//   * k_index_keep_refs: the kept references' hashes, counts and per-reference values to their new places.
+// Both build beside the arrays in use (IndexStage); index_commit swaps.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +47,7 @@
 #include "fh_index.h"
 #include "fh_internal.h"
 #include "fh_kernels.h"
+#include "fh_merge_path.h"
 #include "fh_moments.h"
 
 using namespace fh;
@@ -79,12 +87,182 @@ struct IndexArgs {
 __device__ inline uint32_t top_of(uint32_t n) { return n ? 1u << (31 - __clz(n)) : 0; }
 
 // grid: x = reference block.  Posting t of reference r -- (its t-th hash, r) -- goes to where the hash is in the CSR: reference order.
-__global__ void __launch_bounds__(THREADS) k_index_postings(const uint64_t *rh, const uint64_t *roff, uint32_t nr, uint64_t *keys, uint32_t *vals) {
-    for (uint32_t r = blockIdx.x; r < nr; r += gridDim.x) {
+// The build forms every reference's (first = 0); an add forms those of the references first .. nr - 1 only, and keys / vals start
+// at the first of them.
+__global__ void __launch_bounds__(THREADS) k_index_postings(const uint64_t *rh, const uint64_t *roff, uint32_t first, uint32_t nr, uint64_t *keys,
+                                                            uint32_t *vals) {
+    const uint64_t t0 = roff[first];
+    for (uint32_t r = first + blockIdx.x; r < nr; r += gridDim.x) {
         const uint64_t r0 = roff[r], r1 = roff[r + 1];
         for (uint64_t t = r0 + threadIdx.x; t < r1; t += THREADS) {
-            keys[t] = rh[t];
-            vals[t] = r;
+            keys[t - t0] = rh[t];
+            vals[t - t0] = r;
+        }
+    }
+}
+
+// ---- finch_index_add / finch_index_keep ---------------------------------------------------------------
+// Here, unlike every list above, output order is the contract: the postings stay sorted by hash with a hash's references
+// ascending, which is what a build leaves.  Positions come from searches and scans; no atomic cursor decides one.
+
+constexpr uint32_t UPDATE_MAX_TILE = 2048;
+
+constexpr uint32_t MERGE_ITEMS = UPDATE_MAX_TILE / THREADS; // postings of a tile per thread, at most
+
+// grid: x = tile of `tile` output postings (blocks go round).  a = the index's postings, b = the added ones, both ascending by
+// key, b's references all above a's: on equal keys every a goes before every b (fh_merge_path.h).  The tile's two diagonal cuts
+// are searched by the whole workgroup, 128 probes a round each (threads 0..127 the cut at the tile's start, 128..255 the one at
+// its end); the tile's runs of a and b are staged in LDS; every thread ranks its postings in the other run and keeps them in
+// registers; they go back to LDS at their ranks -- the same 24 KiB, six workgroups to a CU -- and the tile is written in order.
+__global__ void __launch_bounds__(THREADS) k_index_merge(const uint64_t *ak, const uint32_t *av, uint32_t na, const uint64_t *bk, const uint32_t *bv,
+                                                         uint32_t nb, uint64_t *ok, uint32_t *ov, uint32_t tile, uint32_t n_tiles) {
+    __shared__ uint64_t s_k[UPDATE_MAX_TILE];
+    __shared__ uint32_t s_v[UPDATE_MAX_TILE];
+    const uint64_t n = (uint64_t)na + nb; // (below 2^32: the host's bound on an index)
+    const uint32_t end = threadIdx.x >> 7, t = threadIdx.x & 127; // which cut this thread probes, and its probe
+    for (uint32_t ti = blockIdx.x; ti < n_tiles; ti += gridDim.x) {
+        const uint64_t d0 = min((uint64_t)ti * tile, n), d1 = min(d0 + tile, n);
+        // every thread follows both ranges: the loop and its barriers are uniform
+        uint32_t lo0 = merge_path_lo(nb, (uint32_t)d0), hi0 = merge_path_hi(na, (uint32_t)d0);
+        uint32_t lo1 = merge_path_lo(nb, (uint32_t)d1), hi1 = merge_path_hi(na, (uint32_t)d1);
+        while (lo0 < hi0 || lo1 < hi1) {
+            const uint32_t step0 = merge_path_step(lo0, hi0, 128), step1 = merge_path_step(lo1, hi1, 128);
+            const bool p = end ? merge_path_probe(ak, bk, (uint32_t)d1, lo1, hi1, step1, t) : merge_path_probe(ak, bk, (uint32_t)d0, lo0, hi0, step0, t);
+            const uint32_t n0 = (uint32_t)__syncthreads_count(p && !end), n1 = (uint32_t)__syncthreads_count(p && end);
+            merge_path_narrow(lo0, hi0, step0, n0);
+            merge_path_narrow(lo1, hi1, step1, n1);
+        }
+        const uint32_t a0 = lo0, a1 = lo1;
+        const uint32_t b0 = (uint32_t)d0 - a0, b1 = (uint32_t)d1 - a1;
+        // (a cut is at most na and at least d - nb, and it is monotone in d as d - cut is: la + lb = d1 - d0 <= tile; the
+        // guards keep every read inside a and b whatever the input)
+        const uint32_t la = a1 > a0 ? min(a1 - a0, tile) : 0, lb = b1 > b0 ? min(b1 - b0, tile - la) : 0;
+        for (uint32_t x = threadIdx.x; x < la + lb; x += THREADS) {
+            const bool from_a = x < la;
+            s_k[x] = from_a ? ak[a0 + x] : bk[b0 + (x - la)];
+            s_v[x] = from_a ? av[a0 + x] : bv[b0 + (x - la)];
+        }
+        __syncthreads();
+        uint64_t key[MERGE_ITEMS];
+        uint32_t val[MERGE_ITEMS], pos[MERGE_ITEMS];
+#pragma unroll
+        for (uint32_t m = 0; m < MERGE_ITEMS; ++m) {
+            const uint32_t x = threadIdx.x + m * THREADS;
+            key[m] = 0, val[m] = 0, pos[m] = UPDATE_MAX_TILE;
+            if (x < la + lb) {
+                key[m] = s_k[x], val[m] = s_v[x];
+                pos[m] = x < la ? x + merge_rank<false>(s_k + la, lb, key[m]) : (x - la) + merge_rank<true>(s_k, la, key[m]);
+            }
+        }
+        __syncthreads(); // every rank is taken from the runs as staged
+#pragma unroll
+        for (uint32_t m = 0; m < MERGE_ITEMS; ++m)
+            if (pos[m] < la + lb) s_k[pos[m]] = key[m], s_v[pos[m]] = val[m];
+        __syncthreads();
+        for (uint32_t x = threadIdx.x; x < la + lb; x += THREADS) {
+            ok[d0 + x] = s_k[x];
+            ov[d0 + x] = s_v[x];
+        }
+        __syncthreads(); // the next tile stages over what was just read
+    }
+}
+
+// grid: x = tile of `tile` postings (blocks go round).  A posting survives where map[its reference] is not NONE_REF.  WRITE =
+// false: count[ti] = the tile's survivors.  WRITE = true: count[] holds the exclusive scan of those, and the tile's survivors go,
+// in their order, to ok / ov from count[ti] on, the reference renamed through map.  256 postings at a time: a lane's place among
+// its wave's survivors by mbcnt, the waves' sums through LDS, the batches' through a running carry.
+constexpr uint32_t NONE_REF = 0xffffffffu;
+template <bool WRITE>
+__global__ void __launch_bounds__(THREADS) k_index_compact(const uint64_t *keys, const uint32_t *vals, uint32_t n, const uint32_t *map, uint32_t nr,
+                                                           uint32_t tile, uint32_t n_tiles, uint32_t *count, uint64_t *ok, uint32_t *ov, uint32_t n_out) {
+    __shared__ uint32_t s_w[WAVES];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t ti = blockIdx.x; ti < n_tiles; ti += gridDim.x) {
+        const uint64_t p0 = (uint64_t)ti * tile, p1 = min(p0 + tile, (uint64_t)n);
+        uint32_t carry = WRITE ? count[ti] : 0;
+        for (uint64_t base = p0; base < p1; base += THREADS) { // (whole workgroups go round: the barriers see every thread)
+            const uint64_t p = base + threadIdx.x;
+            uint32_t to = NONE_REF;
+            if (p < p1) {
+                const uint32_t r = vals[p];
+                to = r < nr ? map[r] : NONE_REF;
+            }
+            const bool live = to != NONE_REF;
+            const uint64_t mask = __ballot(live);
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+            if (lane == 0) s_w[wave] = (uint32_t)__popcll(mask);
+            __syncthreads();
+            uint32_t before = 0, total = 0;
+            for (uint32_t w = 0; w < WAVES; ++w) {
+                before += w < wave ? s_w[w] : 0;
+                total += s_w[w];
+            }
+            if (WRITE && live) {
+                const uint32_t o = carry + before + rank;
+                if (o < n_out) ok[o] = keys[p], ov[o] = to;
+            }
+            carry += total;
+            __syncthreads(); // the next batch writes s_w again
+        }
+        if (!WRITE && threadIdx.x == 0) count[ti] = carry;
+    }
+}
+
+// one workgroup of 1024: count[0 .. n) becomes its exclusive scan, 1024 at a time with a running carry; *total = the sum
+__global__ void __launch_bounds__(1024) k_index_tile_scan(uint32_t *count, uint32_t n, uint32_t *total) {
+    __shared__ uint32_t s_w[16];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    for (uint64_t base = 0; base < n; base += 1024) { // (whole workgroups go round)
+        const uint64_t t = base + threadIdx.x;
+        const uint32_t c = t < n ? count[t] : 0;
+        uint32_t inc = c;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t v = __shfl_up(inc, o, 64);
+            if ((int)lane >= o) inc += v;
+        }
+        if (lane == 63) s_w[wave] = inc;
+        __syncthreads();
+        uint32_t before = 0, sum = 0;
+        for (uint32_t w = 0; w < 16; ++w) {
+            before += w < wave ? s_w[w] : 0;
+            sum += s_w[w];
+        }
+        if (t < n) count[t] = carry + before + inc - c;
+        carry += sum;
+        __syncthreads(); // the next batch writes s_w again
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+struct KeepRefsArgs {
+    const uint64_t *rh, *roff, *rlast, *rmax; // the library as it is
+    const uint32_t *rlen, *rflag, *rcnt;      // (rcnt: nullptr where no counts are attached)
+    const double *rscale;
+    uint32_t nr;
+    const uint32_t *keep; // the survivors, ascending
+    uint32_t n_keep;
+    const uint64_t *noff; // ... and their offsets in the new CSR, n_keep + 1
+    uint64_t *nh, *nlast, *nmax;
+    uint32_t *nlen, *nflag, *ncnt;
+    double *nscale;
+};
+
+// grid: x = surviving reference (blocks go round): its run of hashes (and of counts) moves to its new offset, its per-reference
+// values to its new index
+__global__ void __launch_bounds__(THREADS) k_index_keep_refs(KeepRefsArgs k) {
+    for (uint32_t s = blockIdx.x; s < k.n_keep; s += gridDim.x) {
+        const uint32_t r = k.keep[s];
+        if (r >= k.nr) continue; // (the host checked the list)
+        const uint64_t o0 = k.roff[r], n0 = k.noff[s];
+        const uint64_t len = min(k.roff[r + 1] - o0, k.noff[s + 1] - n0); // (equal: the host made noff from these lengths)
+        for (uint64_t t = threadIdx.x; t < len; t += THREADS) {
+            k.nh[n0 + t] = k.rh[o0 + t];
+            if (k.rcnt) k.ncnt[n0 + t] = k.rcnt[o0 + t];
+        }
+        if (threadIdx.x == 0) {
+            k.nlast[s] = k.rlast[r], k.nmax[s] = k.rmax[r], k.nlen[s] = k.rlen[r], k.nflag[s] = k.rflag[r];
+            k.nscale[s] = k.rscale[r];
         }
     }
 }
@@ -459,6 +637,15 @@ __global__ void __launch_bounds__(ROUND_THREADS) k_index_gather_rounds(IndexArgs
 
 namespace fh {
 
+// what an update has built beside the arrays in use, until index_commit swaps it in or index_discard drops it
+struct IndexStage {
+    bool ready = false;
+    uint32_t nr = 0, n_post = 0, chunk = 0;
+    void *lib[9] = {};
+    uint32_t *rcnt = nullptr, *cnt = nullptr, *touched = nullptr, *tcount = nullptr, *back_h = nullptr;
+    std::vector<uint32_t> rlen_h;
+};
+
 struct IndexDevice {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -486,12 +673,24 @@ struct IndexDevice {
     std::vector<uint32_t> rlen_h; // the library's lengths: what a candidate's `common` is checked against
     hipEvent_t ev[6] = {};
     bool dirty = false;           // a launch failed between the count and the finish: the counters are not known to be zero
+    IndexStage next;              // index_add / index_keep: the arrays of the updated library
 };
+
+// frees what a stage holds; the device is current
+static void stage_drop(IndexStage *s) {
+    for (void *p : s->lib)
+        if (p) (void)hipFree(p);
+    for (uint32_t *p : {s->rcnt, s->cnt, s->touched, s->tcount})
+        if (p) (void)hipFree(p);
+    if (s->back_h) (void)hipHostFree(s->back_h);
+    *s = IndexStage();
+}
 
 void index_close(IndexDevice *d) {
     if (!d) return;
     if (hipSetDevice(d->device) == hipSuccess) {
         if (d->stream) (void)hipStreamSynchronize(d->stream);
+        stage_drop(&d->next);
         for (void *p : d->lib)
             if (p) (void)hipFree(p);
         for (void *p : d->qry)
@@ -564,7 +763,7 @@ static int open_into(IndexDevice *d, const DistSide &r, uint64_t *device_bytes, 
     IHIP_TRY(api_dev_malloc(&scratch.tmp, tmp_bytes));
     IHIP_TRY(hipEventRecord(d->ev[0], d->stream));
     hipLaunchKernelGGL(k_index_postings, dim3(std::min(d->nr, 4096u)), dim3(THREADS), 0, d->stream, (const uint64_t *)d->lib[0],
-                       (const uint64_t *)d->lib[1], d->nr, (uint64_t *)d->lib[7], (uint32_t *)d->lib[8]);
+                       (const uint64_t *)d->lib[1], 0u, d->nr, (uint64_t *)d->lib[7], (uint32_t *)d->lib[8]);
     IHIP_TRY(hipGetLastError());
     IHIP_TRY(big_sort_pairs(scratch.tmp, tmp_bytes, (uint64_t *)d->lib[7], (uint64_t *)scratch.keys, (uint32_t *)d->lib[8],
                             (uint32_t *)scratch.vals, d->n_post, d->stream));
@@ -864,6 +1063,14 @@ int index_attach_counts(IndexDevice *d, const uint32_t *counts, uint64_t n, uint
     return FH_OK;
 }
 
+void index_drop_counts(IndexDevice *d) {
+    if (!d || !d->rcnt) return;
+    if (hipSetDevice(d->device) == hipSuccess && d->stream) (void)hipStreamSynchronize(d->stream);
+    (void)hipFree(d->rcnt);
+    d->rcnt = nullptr;
+    (void)hipGetLastError();
+}
+
 // finch_index_compare_counts' chunk: the count as above, the selection that also stores the zeros back, the moment walk.
 static int compare_counts_chunk(IndexDevice *d, const DistSide &q, const uint32_t *counts, uint32_t q0, uint32_t q1, uint32_t min_common,
                                 std::vector<MomentsRecord> *recs, uint64_t *touched, double *kernel_ms, uint64_t *launches) {
@@ -948,6 +1155,248 @@ int index_compare_counts_chunk(IndexDevice *d, const DistSide &queries, const ui
     if (!d->rcnt) return api_fail(FH_ERR_STATE, "index compare_counts: no counts are attached to the index (finch_index_attach_counts)");
     if (d->dirty) return api_fail(FH_ERR_STATE, "index compare_counts: an earlier call on this index failed between its kernels; build the index again");
     return compare_counts_chunk(d, queries, counts, q0, q1, min_common, recs, touched, kernel_ms, launches);
+}
+
+// ---- finch_index_add / finch_index_keep ---------------------------------------------------------------
+
+// what open_into counts for a library of these sizes
+static uint64_t kept_bytes(uint32_t nr, uint64_t P, uint32_t chunk) {
+    auto up = [](uint64_t b) { return std::max<uint64_t>(b, 8); };
+    return up(P * 8) + up(((uint64_t)nr + 1) * 8) + 3 * up((uint64_t)nr * 8) + 2 * up((uint64_t)nr * 4) + P * 12 +
+           2 * (uint64_t)chunk * nr * sizeof(uint32_t) + ((uint64_t)chunk + 1) * sizeof(uint32_t);
+}
+
+// the stage's per-launch state as open_into makes it: the counters zeroed (on the stream)
+static int stage_state(IndexDevice *d, IndexStage *s) {
+    const size_t dense = (size_t)s->chunk * s->nr * sizeof(uint32_t);
+    IHIP_TRY(api_dev_malloc((void **)&s->cnt, dense));
+    IHIP_TRY(api_dev_malloc((void **)&s->touched, dense));
+    IHIP_TRY(api_dev_malloc((void **)&s->tcount, s->chunk * sizeof(uint32_t)));
+    IHIP_TRY(api_host_malloc((void **)&s->back_h, ((size_t)s->chunk + 1) * sizeof(uint32_t)));
+    IHIP_TRY(hipMemsetAsync(s->cnt, 0, dense, d->stream));
+    return FH_OK;
+}
+
+// a stage array: the first n_old elements from the device's `old` (on the stream), then n_more from the host's `more`
+static int extend(IndexDevice *d, void **dst, const void *old, size_t n_old, const void *more, size_t n_more, size_t elem) {
+    IHIP_TRY(api_dev_malloc(dst, std::max<size_t>((n_old + n_more) * elem, 8)));
+    if (n_old) IHIP_TRY(hipMemcpyAsync(*dst, old, n_old * elem, hipMemcpyDeviceToDevice, d->stream));
+    if (n_more) IHIP_TRY(hipMemcpy((char *)*dst + n_old * elem, more, n_more * elem, hipMemcpyHostToDevice));
+    return FH_OK;
+}
+
+struct UpdateScratch {
+    void *p[5] = {};
+    ~UpdateScratch() {
+        for (void *q : p)
+            if (q) (void)hipFree(q);
+    }
+};
+
+static uint32_t update_grid(uint32_t n_tiles) { return std::max(1u, std::min(n_tiles, 1u << 19)); }
+
+static int add_into(IndexDevice *d, const DistSide &m, const uint32_t *counts, uint32_t tile, double *kernel_ms) {
+    IndexStage *s = &d->next;
+    const uint32_t nm = m.n;
+    const uint64_t Pm = m.offsets[nm];
+    std::vector<uint64_t> rlast(nm), roff((size_t)s->nr + 1, 0);
+    std::vector<uint32_t> rlen(nm);
+    s->rlen_h = d->rlen_h;
+    for (uint32_t t = 0; t < nm; ++t) {
+        rlen[t] = (uint32_t)(m.offsets[t + 1] - m.offsets[t]);
+        rlast[t] = rlen[t] ? m.hashes[m.offsets[t + 1] - 1] : 0;
+        s->rlen_h.push_back(rlen[t]);
+    }
+    for (uint32_t r = 0; r < s->nr; ++r) roff[r + 1] = roff[r] + s->rlen_h[r];
+    if (roff[d->nr] != d->n_post || roff[s->nr] != s->n_post)
+        return api_fail(FH_ERR_STATE, "index add: the lengths the index keeps sum to %llu, it holds %u postings", (unsigned long long)roff[d->nr], d->n_post);
+
+    // the CSR and the per-reference arrays: what is there device to device, what is new from the host
+    if (int rc = extend(d, &s->lib[0], d->lib[0], d->n_post, m.hashes, Pm, sizeof(uint64_t))) return rc;
+    if (int rc = extend(d, &s->lib[1], nullptr, 0, roff.data(), roff.size(), sizeof(uint64_t))) return rc;
+    if (int rc = extend(d, &s->lib[2], d->lib[2], d->nr, rlast.data(), nm, sizeof(uint64_t))) return rc;
+    if (int rc = extend(d, &s->lib[3], d->lib[3], d->nr, m.max_hash, nm, sizeof(uint64_t))) return rc;
+    if (int rc = extend(d, &s->lib[4], d->lib[4], d->nr, rlen.data(), nm, sizeof(uint32_t))) return rc;
+    if (int rc = extend(d, &s->lib[5], d->lib[5], d->nr, m.flags, nm, sizeof(uint32_t))) return rc;
+    if (int rc = extend(d, &s->lib[6], d->lib[6], d->nr, m.scale, nm, sizeof(double))) return rc;
+    if (d->rcnt)
+        if (int rc = extend(d, (void **)&s->rcnt, d->rcnt, d->n_post, counts, Pm, sizeof(uint32_t))) return rc;
+    IHIP_TRY(api_dev_malloc(&s->lib[7], (size_t)s->n_post * sizeof(uint64_t)));
+    IHIP_TRY(api_dev_malloc(&s->lib[8], (size_t)s->n_post * sizeof(uint32_t)));
+
+    // the added postings in reference order, sorted by hash -- stable: a hash's new references ascend --, then merged in
+    UpdateScratch x; // keys, vals, their sort scratch, the sort's histogram space
+    size_t tmp_bytes = 0;
+    if (Pm) {
+        IHIP_TRY(big_sort_tmp_bytes((uint32_t)Pm, &tmp_bytes));
+        IHIP_TRY(api_dev_malloc(&x.p[0], Pm * sizeof(uint64_t)));
+        IHIP_TRY(api_dev_malloc(&x.p[1], Pm * sizeof(uint32_t)));
+        IHIP_TRY(api_dev_malloc(&x.p[2], Pm * sizeof(uint64_t)));
+        IHIP_TRY(api_dev_malloc(&x.p[3], Pm * sizeof(uint32_t)));
+        IHIP_TRY(api_dev_malloc(&x.p[4], std::max<size_t>(tmp_bytes, 8)));
+    }
+    IHIP_TRY(hipEventRecord(d->ev[0], d->stream));
+    if (Pm) {
+        hipLaunchKernelGGL(k_index_postings, dim3(std::min(nm, 4096u)), dim3(THREADS), 0, d->stream, (const uint64_t *)s->lib[0],
+                           (const uint64_t *)s->lib[1], d->nr, s->nr, (uint64_t *)x.p[0], (uint32_t *)x.p[1]);
+        IHIP_TRY(hipGetLastError());
+        IHIP_TRY(big_sort_pairs(x.p[4], tmp_bytes, (uint64_t *)x.p[0], (uint64_t *)x.p[2], (uint32_t *)x.p[1], (uint32_t *)x.p[3], (uint32_t)Pm,
+                                d->stream));
+    }
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)s->n_post + tile - 1) / tile);
+    hipLaunchKernelGGL(k_index_merge, dim3(update_grid(n_tiles)), dim3(THREADS), 0, d->stream, (const uint64_t *)d->lib[7],
+                       (const uint32_t *)d->lib[8], d->n_post, (const uint64_t *)x.p[0], (const uint32_t *)x.p[1], (uint32_t)Pm, (uint64_t *)s->lib[7],
+                       (uint32_t *)s->lib[8], tile, n_tiles);
+    IHIP_TRY(hipGetLastError());
+    IHIP_TRY(hipEventRecord(d->ev[1], d->stream));
+    if (int rc = stage_state(d, s)) return rc;
+    IHIP_TRY(hipStreamSynchronize(d->stream)); // (the scratch and this frame's vectors are free to go)
+    float ms = 0.f;
+    IHIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
+    *kernel_ms += ms;
+    return FH_OK;
+}
+
+static int keep_into(IndexDevice *d, const uint32_t *keep, uint32_t n_keep, uint32_t tile, double *kernel_ms) {
+    IndexStage *s = &d->next;
+    std::vector<uint32_t> map(d->nr, NONE_REF);
+    std::vector<uint64_t> noff((size_t)n_keep + 1, 0);
+    s->rlen_h.resize(n_keep);
+    for (uint32_t t = 0; t < n_keep; ++t) {
+        map[keep[t]] = t;
+        s->rlen_h[t] = d->rlen_h[keep[t]];
+        noff[t + 1] = noff[t] + s->rlen_h[t];
+    }
+    if (noff[n_keep] != s->n_post)
+        return api_fail(FH_ERR_STATE, "index keep: the survivors' lengths sum to %llu, not %u", (unsigned long long)noff[n_keep], s->n_post);
+
+    const size_t P = s->n_post;
+    IHIP_TRY(api_dev_malloc(&s->lib[0], P * sizeof(uint64_t)));
+    if (int rc = extend(d, &s->lib[1], nullptr, 0, noff.data(), noff.size(), sizeof(uint64_t))) return rc;
+    IHIP_TRY(api_dev_malloc(&s->lib[2], (size_t)n_keep * sizeof(uint64_t)));
+    IHIP_TRY(api_dev_malloc(&s->lib[3], (size_t)n_keep * sizeof(uint64_t)));
+    IHIP_TRY(api_dev_malloc(&s->lib[4], (size_t)n_keep * sizeof(uint32_t)));
+    IHIP_TRY(api_dev_malloc(&s->lib[5], (size_t)n_keep * sizeof(uint32_t)));
+    IHIP_TRY(api_dev_malloc(&s->lib[6], (size_t)n_keep * sizeof(double)));
+    IHIP_TRY(api_dev_malloc(&s->lib[7], P * sizeof(uint64_t)));
+    IHIP_TRY(api_dev_malloc(&s->lib[8], P * sizeof(uint32_t)));
+    if (d->rcnt) IHIP_TRY(api_dev_malloc((void **)&s->rcnt, P * sizeof(uint32_t)));
+
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)d->n_post + tile - 1) / tile);
+    UpdateScratch x; // map, the survivors, the tiles' counts and after them their sum
+    if (int rc = extend(d, &x.p[0], nullptr, 0, map.data(), map.size(), sizeof(uint32_t))) return rc;
+    if (int rc = extend(d, &x.p[1], nullptr, 0, keep, n_keep, sizeof(uint32_t))) return rc;
+    IHIP_TRY(api_dev_malloc(&x.p[2], ((size_t)n_tiles + 1) * sizeof(uint32_t)));
+    uint32_t *count = (uint32_t *)x.p[2];
+    const uint64_t *keys = (const uint64_t *)d->lib[7];
+    const uint32_t *vals = (const uint32_t *)d->lib[8], *map_d = (const uint32_t *)x.p[0];
+
+    IHIP_TRY(hipEventRecord(d->ev[0], d->stream));
+    hipLaunchKernelGGL(k_index_compact<false>, dim3(update_grid(n_tiles)), dim3(THREADS), 0, d->stream, keys, vals, d->n_post, map_d, d->nr, tile,
+                       n_tiles, count, (uint64_t *)nullptr, (uint32_t *)nullptr, 0u);
+    IHIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_index_tile_scan, dim3(1), dim3(1024), 0, d->stream, count, n_tiles, count + n_tiles);
+    IHIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_index_compact<true>, dim3(update_grid(n_tiles)), dim3(THREADS), 0, d->stream, keys, vals, d->n_post, map_d, d->nr, tile,
+                       n_tiles, count, (uint64_t *)s->lib[7], (uint32_t *)s->lib[8], s->n_post);
+    IHIP_TRY(hipGetLastError());
+    KeepRefsArgs k;
+    k.rh = (const uint64_t *)d->lib[0], k.roff = (const uint64_t *)d->lib[1], k.rlast = (const uint64_t *)d->lib[2];
+    k.rmax = (const uint64_t *)d->lib[3], k.rlen = (const uint32_t *)d->lib[4], k.rflag = (const uint32_t *)d->lib[5], k.rcnt = d->rcnt;
+    k.rscale = (const double *)d->lib[6], k.nr = d->nr;
+    k.keep = (const uint32_t *)x.p[1], k.n_keep = n_keep, k.noff = (const uint64_t *)s->lib[1];
+    k.nh = (uint64_t *)s->lib[0], k.nlast = (uint64_t *)s->lib[2], k.nmax = (uint64_t *)s->lib[3];
+    k.nlen = (uint32_t *)s->lib[4], k.nflag = (uint32_t *)s->lib[5], k.ncnt = s->rcnt, k.nscale = (double *)s->lib[6];
+    hipLaunchKernelGGL(k_index_keep_refs, dim3(std::min(n_keep, 4096u)), dim3(THREADS), 0, d->stream, k);
+    IHIP_TRY(hipGetLastError());
+    IHIP_TRY(hipEventRecord(d->ev[1], d->stream));
+    if (int rc = stage_state(d, s)) return rc;
+    IHIP_TRY(hipStreamSynchronize(d->stream)); // (the scratch and this frame's vectors are free to go)
+    uint32_t total = 0;
+    IHIP_TRY(hipMemcpy(&total, count + n_tiles, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (total != s->n_post) return api_fail(FH_ERR_STATE, "index keep: %u postings survive where the lengths say %u", total, s->n_post);
+    float ms = 0.f;
+    IHIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
+    *kernel_ms += ms;
+    return FH_OK;
+}
+
+// what both updates check and set before they build: the stage is empty and knows the sizes it is built for
+static int stage_begin(IndexDevice *d, const char *what, uint64_t nr, uint64_t P, uint32_t chunk_queries, uint32_t tile) {
+    if (!d || nr == 0 || nr > UINT32_MAX || P == 0 || P > INDEX_MAX_POSTINGS || chunk_queries == 0 || (uint64_t)chunk_queries * nr > (1ull << 31) ||
+        tile == 0 || tile > UPDATE_MAX_TILE)
+        return api_fail(FH_ERR_INVALID, "%s: %llu references, %llu postings, %u queries per launch, tiles of %u", what, (unsigned long long)nr,
+                        (unsigned long long)P, chunk_queries, tile);
+    IHIP_TRY(hipSetDevice(d->device));
+    IHIP_TRY(hipStreamSynchronize(d->stream));
+    stage_drop(&d->next);
+    d->next.nr = (uint32_t)nr, d->next.n_post = (uint32_t)P, d->next.chunk = chunk_queries;
+    return FH_OK;
+}
+
+int index_add(IndexDevice *d, const DistSide &more, const uint32_t *counts, uint32_t chunk_queries, uint32_t tile, double *kernel_ms) {
+    // (sketches without a hash bring no counts: an empty array may well be a null pointer)
+    if (d && d->rcnt && !counts && more.offsets[more.n] != 0)
+        return api_fail(FH_ERR_INVALID, "index_add: counts are attached to the index and none come with the sketches");
+    if (int rc = stage_begin(d, "index_add", (uint64_t)(d ? d->nr : 0) + more.n, (uint64_t)(d ? d->n_post : 0) + more.offsets[more.n], chunk_queries, tile))
+        return rc;
+    if (int rc = add_into(d, more, counts, tile, kernel_ms)) {
+        index_discard(d);
+        return rc;
+    }
+    d->next.ready = true;
+    return FH_OK;
+}
+
+int index_keep(IndexDevice *d, const uint32_t *keep, uint32_t n_keep, uint32_t chunk_queries, uint32_t tile, double *kernel_ms) {
+    uint64_t P = 0;
+    for (uint32_t t = 0; d && keep && t < n_keep; ++t) {
+        if (keep[t] >= d->nr || (t && keep[t] <= keep[t - 1])) return api_fail(FH_ERR_INVALID, "index_keep: keep[%u] = %u", t, keep[t]);
+        P += d->rlen_h[keep[t]];
+    }
+    if (!keep) return api_fail(FH_ERR_INVALID, "index_keep: null argument");
+    if (int rc = stage_begin(d, "index_keep", n_keep, P, chunk_queries, tile)) return rc;
+    if (int rc = keep_into(d, keep, n_keep, tile, kernel_ms)) {
+        index_discard(d);
+        return rc;
+    }
+    d->next.ready = true;
+    return FH_OK;
+}
+
+void index_discard(IndexDevice *d) {
+    if (!d) return;
+    if (hipSetDevice(d->device) == hipSuccess && d->stream) (void)hipStreamSynchronize(d->stream); // nothing in flight reads the stage
+    stage_drop(&d->next);
+    (void)hipGetLastError();
+}
+
+uint64_t index_commit(IndexDevice *d) {
+    IndexStage &s = d->next;
+    if (s.ready) {
+        (void)hipSetDevice(d->device);
+        (void)hipStreamSynchronize(d->stream);
+        for (void *p : d->lib) (void)hipFree(p);
+        for (uint32_t *p : {d->rcnt, d->cnt, d->touched, d->tcount, d->sel})
+            if (p) (void)hipFree(p);
+        (void)hipHostFree(d->back_h);
+        // what a chunk allocates by the old `chunk`: its first use allocates it again
+        for (void *&p : d->qry) {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+        }
+        if (d->jmin) (void)hipFree(d->jmin);
+        d->qry_hashes = 0, d->jmin = nullptr, d->sel = nullptr, d->sel_cap = 0;
+        for (int i = 0; i < 9; ++i) d->lib[i] = s.lib[i], s.lib[i] = nullptr;
+        d->rcnt = s.rcnt, d->cnt = s.cnt, d->touched = s.touched, d->tcount = s.tcount, d->back_h = s.back_h;
+        s.rcnt = s.cnt = s.touched = s.tcount = s.back_h = nullptr;
+        d->nr = s.nr, d->n_post = s.n_post, d->chunk = s.chunk;
+        d->rlen_h.swap(s.rlen_h);
+        d->dirty = false; // the counters are new, and zero
+        s = IndexStage();
+        (void)hipGetLastError();
+    }
+    return kept_bytes(d->nr, d->n_post, d->chunk);
 }
 
 } // namespace fh

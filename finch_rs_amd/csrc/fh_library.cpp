@@ -1,5 +1,5 @@
 // fh_library.cpp -- the library calls of the C ABI (include/finch_host.h): dist, minmer_matrix, search, the index and its
-// search / dist / gather / compare_counts, gather, compare_counts, merge.  Many sketches against many, on one or several device
+// search / dist / gather / compare_counts / add / keep, gather, compare_counts, merge.  Many sketches against many, on one or several device
 // entries; each call checks its arguments, deals its work over the entries (fh_entries.h) and finishes the device's integers on
 // the host.
 // Reading, parsing and the single-sketch calls are fh_host.cpp's.
@@ -656,7 +656,16 @@ struct finch_index {
     std::vector<fh::IndexDevice *> entries; // one per device entry; none where the library has no hash
     std::vector<uint32_t> rlen;             // the library's lengths: what finch_index_attach_counts holds its `refs` against
     bool counts_attached = false;           // finch_index_attach_counts has left the library's counts on every entry
-    std::mutex mu;                          // one search at a time: the counters belong to the index
+    // what finch_index_add / finch_index_keep need beyond the device's arrays: the device list and the index_chunk_queries
+    // that were in force at finch_index_new (has_chunk_opt: the option was set), and the per-sketch scale data, which an index
+    // without a hash has nowhere else when an add brings its first one
+    std::vector<int> devs;
+    bool has_chunk_opt = false;
+    uint64_t chunk_opt = 0;
+    std::vector<uint32_t> rflag;
+    std::vector<uint64_t> rmax;
+    std::vector<double> rscale;
+    mutable std::mutex mu;                  // one call at a time: the counters belong to the index, and an update swaps its arrays
     ~finch_index() {
         if (entries.empty()) return;
         const int prev = fh::matrix_current_device();
@@ -670,6 +679,17 @@ namespace {
 constexpr uint64_t INDEX_STATE_BYTES = 256ull << 20; // counters plus touched lists of a launch by default, at most
 constexpr uint64_t INDEX_CHUNK_MAX = 4096;           // ... and its queries, at most
 
+// queries per launch for a library of nr > 0 sketches: 8 bytes per (query, reference) -- a counter and a place in the touched
+// list --, or the option as it was at finch_index_new; a launch's list has a u32 cursor
+uint32_t index_chunk_for(const finch_index &ix, uint32_t nr) {
+    const uint64_t by_memory = std::min<uint64_t>(std::max<uint64_t>(1, INDEX_STATE_BYTES / (8ull * nr)), INDEX_CHUNK_MAX);
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, ix.has_chunk_opt ? ix.chunk_opt : by_memory), std::max<uint64_t>(1, (1ull << 31) / nr));
+}
+
+uint64_t index_max_postings() { return std::min<uint64_t>(cfg_u64("index_max_postings", fh::INDEX_MAX_POSTINGS), fh::INDEX_MAX_POSTINGS); }
+
+uint32_t index_update_tile() { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, cfg_u64("index_update_tile", 2048)), 2048); }
+
 } // namespace
 
 extern "C" {
@@ -682,10 +702,16 @@ int finch_index_new(const finch_sketches *refs, const int *devices, uint32_t n_d
     auto ix = std::make_unique<finch_index>();
     ix->nr = (uint32_t)Rs.size();
     for (const Sketch &s : Rs) ix->postings += s.hashes.size(), ix->rlen.push_back((uint32_t)s.hashes.size());
-    const uint64_t max_postings = std::min<uint64_t>(cfg_u64("index_max_postings", fh::INDEX_MAX_POSTINGS), fh::INDEX_MAX_POSTINGS);
+    const uint64_t max_postings = index_max_postings();
     if (ix->postings > max_postings)
         return hfail(FH_ERR_UNSUPPORTED, "reference library: %llu postings (hashes of all %u sketches), an index holds at most %llu",
                      (unsigned long long)ix->postings, ix->nr, (unsigned long long)max_postings);
+    DistCsr rc_;
+    rc_.build(Rs, false);
+    ix->rflag = rc_.flags, ix->rmax = rc_.max_hash, ix->rscale = rc_.scale;
+    ix->devs = n_devices ? std::vector<int>(devices, devices + n_devices) : std::vector<int>{0};
+    ix->has_chunk_opt = fh::cfg("index_chunk_queries") != nullptr;
+    ix->chunk_opt = cfg_u64("index_chunk_queries", 0);
     if (ix->postings == 0) { // no reference has a hash: no pair shares one
         *out = ix.release();
         return FH_OK;
@@ -694,12 +720,7 @@ int finch_index_new(const finch_sketches *refs, const int *devices, uint32_t n_d
     if (int rc = resolve_devices(devices, n_devices, devs)) return rc;
     DeviceGuard restore_device;
 
-    DistCsr rc_;
-    rc_.build(Rs, false);
-    // queries per launch: 8 bytes per (query, reference) -- a counter and a place in the touched list
-    const uint64_t by_memory = std::min<uint64_t>(std::max<uint64_t>(1, INDEX_STATE_BYTES / (8ull * ix->nr)), INDEX_CHUNK_MAX);
-    ix->chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, cfg_u64("index_chunk_queries", by_memory)),
-                                             std::max<uint64_t>(1, (1ull << 31) / ix->nr)); // (a launch's list has a u32 cursor)
+    ix->chunk = index_chunk_for(*ix, ix->nr);
     for (int d : devs) {
         fh::IndexDevice *dev = nullptr;
         uint64_t bytes = 0;
@@ -717,6 +738,7 @@ int finch_index_search(const finch_index *cix, const finch_sketches *queries, do
                        finch_search_result **out) try {
     if (!cix || !queries || !out) return hfail(FH_ERR_INVALID, "null argument");
     finch_index *ix = const_cast<finch_index *>(cix); // (the launch state is the index's; `mu` serialises its use)
+    std::lock_guard<std::mutex> one_search(ix->mu);   // (from here: finch_index_add / finch_index_keep change what is read below)
     if (min_containment <= 0.)
         return hfail(FH_ERR_INVALID, "finch_index_search: min_containment %g: an index finds only the pairs that share a hash, and a threshold "
                                      "<= 0 keeps every pair -- use finch_search", min_containment);
@@ -730,7 +752,6 @@ int finch_index_search(const finch_index *cix, const finch_sketches *queries, do
         *out = res.release();
         return FH_OK;
     }
-    std::lock_guard<std::mutex> one_search(ix->mu);
     DeviceGuard restore_device;
 
     DistCsr qc;
@@ -770,6 +791,7 @@ int finch_index_search(const finch_index *cix, const finch_sketches *queries, do
 
 int finch_index_stats(const finch_index *ix, uint64_t *n_refs, uint64_t *postings, uint64_t *device_bytes, double *build_kernel_ms) try {
     if (!ix) return hfail(FH_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(ix->mu);
     if (n_refs) *n_refs = ix->nr;
     if (postings) *postings = ix->postings;
     if (device_bytes) *device_bytes = ix->device_bytes;
@@ -827,6 +849,7 @@ int finch_index_dist(const finch_index *cix, const finch_sketches *refs, const f
                      finch_dist_result **out) try {
     if (!cix || !refs || !out) return hfail(FH_ERR_INVALID, "null argument");
     finch_index *ix = const_cast<finch_index *>(cix); // (the launch state is the index's; `mu` serialises its use)
+    std::lock_guard<std::mutex> one_call(ix->mu);     // (from here: finch_index_add / finch_index_keep change what is read below)
     if (max_distance >= 1.)
         return hfail(FH_ERR_INVALID, "finch_index_dist: max_distance %g: an index finds only the pairs that share a hash, and a bound "
                                      ">= 1 keeps every pair -- use finch_dist", max_distance);
@@ -893,7 +916,6 @@ int finch_index_dist(const finch_index *cix, const finch_sketches *refs, const f
                     }
 
     if (!ix->entries.empty()) { // (a library without a hash: every row is made above)
-        std::lock_guard<std::mutex> one_call(ix->mu);
         DeviceGuard restore_device;
 
         DistCsr qc;
@@ -1232,6 +1254,7 @@ int finch_index_gather(const finch_index *cix, const finch_sketches *queries, ui
                        finch_gather_result **out) try {
     if (!cix || !queries || !out) return hfail(FH_ERR_INVALID, "null argument");
     finch_index *ix = const_cast<finch_index *>(cix); // (the launch state is the index's; `mu` serialises its use)
+    std::lock_guard<std::mutex> one_call(ix->mu);     // (from here: finch_index_add / finch_index_keep change what is read below)
     const std::vector<Sketch> &Qs = queries->v;
     if (int rc = check_ascending(Qs, "query")) return rc;
     if (int rc = gather_check_query_lengths(Qs)) return rc;
@@ -1243,7 +1266,6 @@ int finch_index_gather(const finch_index *cix, const finch_sketches *queries, ui
         *out = res.release();
         return FH_OK;
     }
-    std::lock_guard<std::mutex> one_call(ix->mu);
     DeviceGuard restore_device;
 
     const uint32_t min_ov = gather_clamp(min_overlap, 1), max_r = gather_clamp(max_rounds, 0);
@@ -1568,6 +1590,7 @@ void finch_compare_counts_free(finch_compare_counts_result *r) { delete r; }
 int finch_index_attach_counts(const finch_index *cix, const finch_sketches *refs, uint64_t *device_bytes) try {
     if (!cix || !refs) return hfail(FH_ERR_INVALID, "null argument");
     finch_index *ix = const_cast<finch_index *>(cix); // (the attachment is the index's; `mu` serialises its use)
+    std::lock_guard<std::mutex> one_call(ix->mu);
     const std::vector<Sketch> &Rs = refs->v;
     uint64_t postings = 0;
     for (const Sketch &s : Rs) postings += s.hashes.size();
@@ -1579,9 +1602,9 @@ int finch_index_attach_counts(const finch_index *cix, const finch_sketches *refs
         if (Rs[r].hashes.size() != ix->rlen[r])
             return hfail(FH_ERR_INVALID, "finch_index_attach_counts: refs sketch %u (%s) has %zu hashes, the index was built from one of %u: "
                                          "refs must be the library of the index", r, Rs[r].name.c_str(), Rs[r].hashes.size(), ix->rlen[r]);
-    std::lock_guard<std::mutex> one_call(ix->mu);
     uint64_t total = 0;
-    if (!ix->entries.empty()) { // (a library without a hash: nothing to attach, no device)
+    if (ix->entries.empty()) ix->counts_attached = true; // (a library without a hash: nothing to attach, no device)
+    else {
         DeviceGuard restore_device;
         std::vector<uint32_t> counts;
         counts.reserve(postings);
@@ -1590,7 +1613,13 @@ int finch_index_attach_counts(const finch_index *cix, const finch_sketches *refs
         ix->counts_attached = false; // until every entry has the new counts
         for (fh::IndexDevice *d : ix->entries) {
             uint64_t bytes = 0;
-            if (int rc = fh::index_attach_counts(d, counts.data(), counts.size(), &bytes)) return hfail(rc, "%s", fh_last_error());
+            if (int rc = fh::index_attach_counts(d, counts.data(), counts.size(), &bytes)) {
+                // no half-made attachment: an entry that holds counts while the index says it has none would have
+                // finch_index_add extend them on that entry alone
+                const std::string why = fh_last_error();
+                for (fh::IndexDevice *e : ix->entries) fh::index_drop_counts(e);
+                return hfail(rc, "%s", why.c_str());
+            }
             total += bytes;
         }
         ix->counts_attached = true;
@@ -1603,6 +1632,7 @@ int finch_index_compare_counts(const finch_index *cix, const finch_sketches *que
                                finch_compare_counts_result **out) try {
     if (!cix || !queries || !out) return hfail(FH_ERR_INVALID, "null argument");
     finch_index *ix = const_cast<finch_index *>(cix); // (the launch state is the index's; `mu` serialises its use)
+    std::lock_guard<std::mutex> one_call(ix->mu);     // (from here: finch_index_add / finch_index_keep change what is read below)
     if (min_common == 0)
         return hfail(FH_ERR_INVALID, "finch_index_compare_counts: min_common 0: an index finds only the pairs that share a hash, and a "
                                      "threshold of 0 keeps every pair -- use finch_compare_counts");
@@ -1615,7 +1645,6 @@ int finch_index_compare_counts(const finch_index *cix, const finch_sketches *que
         *out = res.release();
         return FH_OK;
     }
-    std::lock_guard<std::mutex> one_call(ix->mu);
     if (!ix->counts_attached)
         return hfail(FH_ERR_STATE, "finch_index_compare_counts: the index holds the library's hashes, not its counts -- call "
                                    "finch_index_attach_counts first");
@@ -1660,6 +1689,150 @@ int finch_index_compare_counts_stats(const finch_compare_counts_result *r, uint6
     if (!r->from_index) return hfail(FH_ERR_INVALID, "finch_index_compare_counts_stats: the result was not made by finch_index_compare_counts");
     if (pairs_touched) *pairs_touched = r->touched;
     if (pairs_walked) *pairs_walked = r->copied; // (the moment kernel walks exactly the pairs whose records cross)
+    return FH_OK;
+} FINCH_CATCH
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// the index grown and shrunk in place (Multisketch.add, __delitem__, filter_to_matches, filter_to_names: python.rs:158-248;
+// fh_index.hip).  Everything an update needs of the library is on the device already; what crosses is what
+// changes.  Every entry builds its new arrays beside the old ones, and only when all have are they swapped in: a refusal or a
+// failure before that leaves the index as it was.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+void index_discard_all(finch_index *ix) {
+    for (fh::IndexDevice *d : ix->entries) fh::index_discard(d);
+}
+
+// every entry has built its stage: the swap, which cannot fail
+void index_commit_all(finch_index *ix, uint32_t chunk) {
+    ix->device_bytes = 0;
+    for (fh::IndexDevice *d : ix->entries) ix->device_bytes += fh::index_commit(d);
+    ix->chunk = chunk;
+}
+
+void index_close_all(std::vector<fh::IndexDevice *> &entries) {
+    for (fh::IndexDevice *d : entries) fh::index_close(d);
+    entries.clear();
+}
+
+} // namespace
+
+extern "C" {
+
+int finch_index_add(finch_index *ix, const finch_sketches *more, double *kernel_ms) try {
+    if (!ix || !more) return hfail(FH_ERR_INVALID, "null argument");
+    const std::vector<Sketch> &Ms = more->v;
+    if (int rc = check_ascending(Ms, "added")) return rc;
+    std::lock_guard<std::mutex> one_call(ix->mu);
+    if (kernel_ms) *kernel_ms = 0.;
+    if (Ms.empty()) return FH_OK;
+    uint64_t added = 0;
+    for (const Sketch &s : Ms) added += s.hashes.size();
+    const uint64_t nr2 = (uint64_t)ix->nr + Ms.size(), P2 = ix->postings + added, max_postings = index_max_postings();
+    if (nr2 > UINT32_MAX) return hfail(FH_ERR_UNSUPPORTED, "reference library: %llu sketches (at most 2^32 - 1)", (unsigned long long)nr2);
+    if (P2 > max_postings)
+        return hfail(FH_ERR_UNSUPPORTED, "reference library: %llu postings (hashes of all %llu sketches, %zu of them added), an index holds at most %llu",
+                     (unsigned long long)P2, (unsigned long long)nr2, Ms.size(), (unsigned long long)max_postings);
+    DistCsr mc;
+    mc.build(Ms, false, ix->counts_attached);
+    // room for the host's copies first: after the swap nothing may fail
+    ix->rlen.reserve(nr2), ix->rflag.reserve(nr2), ix->rmax.reserve(nr2), ix->rscale.reserve(nr2);
+    double ms = 0.;
+    if (P2 && ix->entries.empty()) {
+        // the first hash: the entries are opened as finch_index_new opens them, over the empty sketches there are and the added ones
+        std::vector<int> devs;
+        if (int rc = resolve_devices(ix->devs.data(), (uint32_t)ix->devs.size(), devs)) return rc;
+        DeviceGuard restore_device;
+        DistCsr all;
+        all.hashes = mc.hashes;
+        all.offsets.assign((size_t)ix->nr, 0);
+        all.offsets.insert(all.offsets.end(), mc.offsets.begin(), mc.offsets.end());
+        all.flags = ix->rflag, all.max_hash = ix->rmax, all.scale = ix->rscale;
+        all.flags.insert(all.flags.end(), mc.flags.begin(), mc.flags.end());
+        all.max_hash.insert(all.max_hash.end(), mc.max_hash.begin(), mc.max_hash.end());
+        all.scale.insert(all.scale.end(), mc.scale.begin(), mc.scale.end());
+        const uint32_t chunk = index_chunk_for(*ix, (uint32_t)nr2);
+        std::vector<fh::IndexDevice *> opened;
+        uint64_t bytes_sum = 0;
+        for (int d : devs) {
+            fh::IndexDevice *dev = nullptr;
+            uint64_t bytes = 0, attached = 0;
+            int rc = fh::index_open(d, all.view(), chunk, &dev, &bytes, &ms);
+            if (rc == FH_OK) {
+                opened.push_back(dev);
+                if (ix->counts_attached) rc = fh::index_attach_counts(dev, mc.counts.data(), mc.counts.size(), &attached);
+            }
+            if (rc != FH_OK) {
+                const std::string why = fh_last_error();
+                index_close_all(opened);
+                return hfail(rc, "%s", why.c_str());
+            }
+            bytes_sum += bytes;
+        }
+        ix->entries.swap(opened);
+        ix->device_bytes = bytes_sum;
+        ix->chunk = chunk;
+    } else if (P2) {
+        DeviceGuard restore_device;
+        const uint32_t chunk = index_chunk_for(*ix, (uint32_t)nr2), tile = index_update_tile();
+        for (fh::IndexDevice *d : ix->entries)
+            if (int rc = fh::index_add(d, mc.view(), ix->counts_attached ? mc.counts.data() : nullptr, chunk, tile, &ms)) {
+                const std::string why = fh_last_error();
+                index_discard_all(ix);
+                return hfail(rc, "%s", why.c_str());
+            }
+        index_commit_all(ix, chunk);
+    }
+    ix->nr = (uint32_t)nr2, ix->postings = P2;
+    for (const Sketch &s : Ms) ix->rlen.push_back((uint32_t)s.hashes.size());
+    ix->rflag.insert(ix->rflag.end(), mc.flags.begin(), mc.flags.end());
+    ix->rmax.insert(ix->rmax.end(), mc.max_hash.begin(), mc.max_hash.end());
+    ix->rscale.insert(ix->rscale.end(), mc.scale.begin(), mc.scale.end());
+    if (kernel_ms) *kernel_ms = ms;
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_index_keep(finch_index *ix, const uint32_t *keep, uint32_t n_keep, double *kernel_ms) try {
+    if (!ix || (n_keep && !keep)) return hfail(FH_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> one_call(ix->mu);
+    if (kernel_ms) *kernel_ms = 0.;
+    uint64_t P2 = 0;
+    for (uint32_t t = 0; t < n_keep; ++t) {
+        if (keep[t] >= ix->nr)
+            return hfail(FH_ERR_INVALID, "finch_index_keep: keep[%u] = %u: the index has %u references", t, keep[t], ix->nr);
+        if (t && keep[t] <= keep[t - 1])
+            return hfail(FH_ERR_INVALID, "finch_index_keep: keep[%u] = %u after %u: the list must ascend strictly", t, keep[t], keep[t - 1]);
+        P2 += ix->rlen[keep[t]];
+    }
+    // the host's copies first: if one cannot be made, nothing has changed yet
+    std::vector<uint32_t> rlen(n_keep), rflag(n_keep);
+    std::vector<uint64_t> rmax(n_keep);
+    std::vector<double> rscale(n_keep);
+    for (uint32_t t = 0; t < n_keep; ++t)
+        rlen[t] = ix->rlen[keep[t]], rflag[t] = ix->rflag[keep[t]], rmax[t] = ix->rmax[keep[t]], rscale[t] = ix->rscale[keep[t]];
+    double ms = 0.;
+    if (!ix->entries.empty()) {
+        DeviceGuard restore_device;
+        if (P2 == 0) { // no hash is left: no entries, as finch_index_new leaves such a library
+            index_close_all(ix->entries);
+            ix->device_bytes = 0, ix->chunk = 0;
+        } else {
+            const uint32_t chunk = index_chunk_for(*ix, n_keep), tile = index_update_tile();
+            for (fh::IndexDevice *d : ix->entries)
+                if (int rc = fh::index_keep(d, keep, n_keep, chunk, tile, &ms)) {
+                    const std::string why = fh_last_error();
+                    index_discard_all(ix);
+                    return hfail(rc, "%s", why.c_str());
+                }
+            index_commit_all(ix, chunk);
+        }
+    }
+    ix->nr = n_keep, ix->postings = P2;
+    ix->rlen.swap(rlen), ix->rflag.swap(rflag), ix->rmax.swap(rmax), ix->rscale.swap(rscale);
+    if (kernel_ms) *kernel_ms = ms;
     return FH_OK;
 } FINCH_CATCH
 

@@ -174,6 +174,8 @@ _SYMS["finch_compare_counts_free"] = (None, [_P])
 _SYMS["finch_index_attach_counts"] = (C.c_int, [_P, _P, C.POINTER(C.c_uint64)])
 _SYMS["finch_index_compare_counts"] = (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)])
 _SYMS["finch_index_compare_counts_stats"] = (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+_SYMS["finch_index_add"] = (C.c_int, [_P, _P, C.POINTER(C.c_double)])
+_SYMS["finch_index_keep"] = (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_double)])
 _SYMS["finch_merge_pair"] = (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(_P)])
 _SYMS["finch_merge_groups"] = (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P),
                                          C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)])
@@ -716,7 +718,9 @@ class LibraryIndex:
     min_containment > 0, .search(queries, min_containment, top_n) == search(queries, refs, min_containment, top_n), byte for
     byte, at a cost that follows the pairs that share a hash instead of len(queries) x len(refs).  The index keeps its own copy
     of what it needs on the device (`refs` itself for filter_to_matches' result and for dist's rows); a context manager, or
-    .close()"""
+    .close().  .refs is the library of the index at any time: .add() appends to the object it holds -- the caller's, until the
+    first .keep() --, .keep() and what is built on it put a new collection there and leave the caller's object as it was.  Read
+    the library from .refs after an update, not from the object the index was made from"""
 
     def __init__(self, refs: Sketches, devices: Sequence[int] = (0,)):
         devs = list(devices) if devices else [0]
@@ -801,6 +805,48 @@ class LibraryIndex:
         p = _P()
         _check(lib().finch_index_compare_counts(h, queries._p, min(int(min_common), 2 ** 64 - 1), C.byref(p)))
         return _counts_rows(p, stats, from_index=True)
+
+    def add(self, more: Sketches, stats: Optional[dict] = None) -> None:
+        """Multisketch.add (python.rs:191-194): the sketches of `more` after the library's last one, in the index
+        (finch_index_add: a merge on the device, nothing of the old library crosses the link) and in self.refs, which grows
+        as the Multisketch does: self.refs is appended to in place, and that is the caller's own object as long as no keep()
+        has replaced it.  `more` must be another object than self.refs (FinchError).  Attached counts are extended.  `stats`
+        receives kernel_ms, the update kernels' time"""
+        if more is self.refs:
+            raise FinchError("LibraryIndex.add: `more` is the library itself; add a copy (select(refs, range(len(refs))))")
+        ms = C.c_double()
+        _check(lib().finch_index_add(self._handle(), more._p, C.byref(ms)))
+        self.refs.append(more)
+        if stats is not None:
+            stats.update(kernel_ms=ms.value)
+
+    def keep(self, idx, stats: Optional[dict] = None) -> None:
+        """the library becomes select(refs, idx), idx strictly ascending (FinchError otherwise: the order of a library is
+        kept, as Multisketch.__delitem__, filter_to_matches and filter_to_names keep it), in the index (finch_index_keep: a
+        compaction on the device) and in self.refs, which becomes a NEW collection: an object the index was made from, or
+        that add() grew, stays as it is and no longer follows the index.  Attached counts are compacted.  `stats` receives
+        kernel_ms"""
+        idx = np.ascontiguousarray(idx, np.int64).ravel()
+        if len(idx) and (idx.min() < 0 or idx.max() >= 2 ** 32):
+            raise FinchError("LibraryIndex.keep: index %d out of range" % (idx.min() if idx.min() < 0 else idx.max()))
+        arr = idx.astype(np.uint32)
+        ms = C.c_double()
+        _check(lib().finch_index_keep(self._handle(), arr.ctypes.data_as(C.POINTER(C.c_uint32)) if len(arr) else None, len(arr), C.byref(ms)))
+        self.refs = select(self.refs, arr)
+        if stats is not None:
+            stats.update(kernel_ms=ms.value)
+
+    def filter_to_names(self, names, stats: Optional[dict] = None) -> None:
+        """Multisketch.filter_to_names (python.rs:242-248): keep the sketches whose name is listed, in library order"""
+        wanted, L = set(names), lib()
+        self.keep([i for i in range(len(self.refs)) if L.finch_sketch_name(self.refs._p, i).decode() in wanted], stats)
+
+    def delete(self, i: int, stats: Optional[dict] = None) -> None:
+        """Multisketch.__delitem__ (python.rs:158-164): keep every sketch but sketch i (a negative i counts from the end)"""
+        n = len(self.refs)
+        if not -n <= i < n:
+            raise FinchError("LibraryIndex.delete: index %d out of range for %d sketches" % (i, n))
+        self.keep([j for j in range(n) if j != i % n], stats)
 
     def best_match(self, queries: Sketches, iq: int = 0) -> int:
         """best_match(refs, queries, iq): a top-1 search at the smallest positive threshold; a query that shares nothing with

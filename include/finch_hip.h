@@ -95,8 +95,10 @@ const char *fh_last_error(void);
  * 16: fh_batch_new_wide and the rest of 15 unchanged, plus finch_index_dist and finch_index_dist_stats in finch_host.h;
  * 17: fh_batch_new_wide and the rest of 16 unchanged, plus finch_index_gather and finch_index_gather_stats in finch_host.h;
  * 18: fh_batch_new_wide and the rest of 17 unchanged, plus finch_index_attach_counts, finch_index_compare_counts and
- * finch_index_compare_counts_stats in finch_host.h) */
-#define FH_ABI_VERSION 18
+ * finch_index_compare_counts_stats in finch_host.h;
+ * 19: fh_batch_new_wide and the rest of 18 unchanged, plus finch_index_add and finch_index_keep in finch_host.h and the option
+ * index_update_tile) */
+#define FH_ABI_VERSION 19
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---

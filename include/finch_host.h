@@ -413,7 +413,9 @@ void finch_compare_counts_free(finch_compare_counts_result *r);
  *   hashes --, where it stays until finch_index_free; a second call replaces it.  `refs` must be the library the index was built
  *   from: FH_ERR_INVALID for another number of sketches or hashes (in finch_index_dist's words) and for a sketch of another length
  *   (named).  *device_bytes (may be NULL) = what the attachment holds, summed over the entries; finch_index_stats is unchanged.
- *   An index of a library without a hash attaches nothing and needs no device.  One call at a time runs on an index.
+ *   A call that fails on some entry leaves no counts on any: the index is as it was before its first attachment.
+ *   An index of a library without a hash attaches nothing and needs no device (the call is remembered: a finch_index_add that
+ *   brings the first hashes attaches their counts).  One call at a time runs on an index.
  * finch_index_compare_counts: queries are dealt over the index's device entries in chunks of index_chunk_queries, as
  *   finch_index_search deals them.  Per chunk, up to three launches: finch_index_search's count, which leaves c = |Q n R| in the
  *   query's counter of every reference that shares a hash; a selection that reads c, stores 0 back and keeps (q, r, c) where
@@ -436,6 +438,42 @@ int finch_index_attach_counts(const finch_index *ix, const finch_sketches *refs,
 int finch_index_compare_counts(const finch_index *ix, const finch_sketches *queries, uint64_t min_common,
                                finch_compare_counts_result **out);
 int finch_index_compare_counts_stats(const finch_compare_counts_result *r, uint64_t *pairs_touched, uint64_t *pairs_walked);
+
+/* the index grown and shrunk in place (Multisketch.add, __delitem__, filter_to_matches, filter_to_names: python.rs:158-248,
+ * which all change the library and keep its order).  THE CONTRACT: after any sequence of finch_index_add and finch_index_keep the
+ * index is indistinguishable from finch_index_new over the resulting list of sketches, through finch_index_search,
+ * finch_index_dist (pairwise included), finch_index_gather and finch_index_compare_counts: the same bytes and the same
+ * pairs_touched / pairs_walked / pairs_copied.  `refs` of finch_index_dist and finch_index_attach_counts is held against the
+ * updated lengths.  Host work and link traffic follow what changes, not the library: the library's CSR, its per-sketch arrays
+ * and its sorted postings stay on the device, and an update is a stable merge or a stable compaction of them.
+ * finch_index_add: appends the sketches of `more`, in their order, after the library's last: they become the references
+ *   nr .. nr + len(more) - 1.  Decided before any device work: FH_ERR_INVALID for a null argument and for a sketch of `more` whose
+ *   hashes are not strictly ascending ("added sketch <i> (<name>)"); FH_ERR_UNSUPPORTED where the grown library would hold more
+ *   postings than an index may (2^32 - 2048, or option index_max_postings as it is now).  An empty `more` is a no-op that
+ *   succeeds.
+ * finch_index_keep: keeps the references keep[0 .. n_keep), which must ascend strictly and be below the number of references
+ *   (FH_ERR_INVALID otherwise, the message names the offending position: "keep[<t>] = <r>"); the survivors are renumbered
+ *   0 .. n_keep - 1 in order.  n_keep == 0 (keep may be NULL then) leaves a library of no sketches.  Reordering is not offered:
+ *   a reorder would have to sort every run of equal hashes again.
+ * Both: *kernel_ms (may be NULL) = the update kernels' time (HIP events, summed over the device entries).  finch_index_stats
+ *   reports the new n_refs, postings and device_bytes; build_kernel_ms stays the build's.  Attached counts follow: an add appends
+ *   the counts of `more`, a keep compacts them, nothing is attached again; where none are attached none are made, and
+ *   finch_index_compare_counts stays refused until finch_index_attach_counts.
+ *   An update either happens or does not: every device entry first builds its new arrays BESIDE the old ones, and only when all
+ *   entries have are they swapped in and the old ones freed, a step that cannot fail.  A refusal or a HIP error before that
+ *   leaves the index answering exactly as before.  PEAK DEVICE MEMORY OF AN UPDATE IS OLD + NEW (plus the added postings' sort
+ *   space, or 4 bytes per old reference and per tile).  The counters are allocated afresh, zeroed, for the queries per launch
+ *   that finch_index_new's rule gives the new number of references (with index_chunk_queries as it was when the index was built);
+ *   an index marked unusable by a failed search comes out usable.
+ *   An index of a library without a hash has no device entries; it remembers its device list.  An add that brings the first hash
+ *   opens the entries as finch_index_new would (FH_ERR_NO_DEVICE as there); a keep that leaves no hash closes them; on such an
+ *   index both calls need no device while the result has no hash either.
+ *   One call at a time runs on an index, updates included (others wait).  The caller's current device is the same after the
+ *   call.  Option index_update_tile (1..2048, default 2048): output postings per tile of the update kernels; no result depends
+ *   on it.  Values below the default are for tests on small libraries: a keep allocates 4 bytes per tile of the old postings
+ *   beside old + new -- at a tile of 1 as much again as the postings' references -- and one workgroup scans them. */
+int finch_index_add(finch_index *ix, const finch_sketches *more, double *kernel_ms);
+int finch_index_keep(finch_index *ix, const uint32_t *keep, uint32_t n_keep, double *kernel_ms);
 
 /* merge (Sketch.merge: merge_sketches, lib/src/python.rs:24-100).  Not fh_merge, the sharded sketcher's union of partial
  * sketches, which saturates, keeps the bottom n and both tails.  merge(first, second, size) is, in this order:
