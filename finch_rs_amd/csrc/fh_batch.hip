@@ -37,8 +37,8 @@
 // any record sends the file the long way, where fh_finish resolves it.
 //
 // Mash sizes 3001..FH_BATCH_LARGE_MAX_N, k = 1..32 (fh_batch_new_large): the same handle and the same k2_batch -- which takes a
-// partition's geometry from its control block at run time -- over LARGER partitions, sized for the handle's n (large_geometry
-// below), and k_batch_epilogue_large (fh_batch_large.hip) in k_batch_epilogue's place: a file's ~4 n live entries no longer fit
+// partition's geometry from its control block at run time -- over LARGER partitions, sized for the handle's n (geometry,
+// fh_batch_plan.h), and k_batch_epilogue_large (fh_batch_large.hip) in k_batch_epilogue's place: a file's ~4 n live entries no longer fit
 // a workgroup's LDS, so its select runs over a key scratch in device memory, one per file.  The rule for "taken" is unchanged.
 #include <hip/hip_runtime.h>
 
@@ -49,6 +49,7 @@
 #include <vector>
 
 #include "../../include/finch_hip.h"
+#include "fh_batch_plan.h"
 #include "fh_core.h"
 #include "fh_counts.h"
 #include "fh_device.h"
@@ -67,58 +68,34 @@ namespace {
         if (_e != hipSuccess) return api_fail(FH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
-constexpr uint32_t PART_CAP = 32768;      // table entries per file: at most SMALL_MAX = 12288 hashes are ever wanted in one
-constexpr uint32_t PART_LIVE = 16384;     // live / dead list entries per file (> SMALL_MAX)
-constexpr uint32_t PART_SHARD_CAP = 512;  // entries per shard list (inserts are dealt over the 256 lists drain by drain)
-constexpr uint32_t PART_CLOG = 64;        // collision records per file (any collision sends the file the long way)
-constexpr uint64_t BATCH_MAX_N = 3000;    // kmers_to_sketch the in-LDS selection serves (fh_api.hip SMALL_N_MAX)
-constexpr uint64_t BATCH_LARGE_MAX_N = FH_BATCH_LARGE_MAX_N; // ... and the selection over device memory (fh_batch_large.hip)
-static_assert(BATCH_LARGE_MAX_N == (uint64_t)LARGE_MAX_ROWS, "the large epilogue keeps that many sorted keys in LDS");
-constexpr uint64_t LARGE_WANT = 4;        // a large file's threshold: LARGE_WANT x n hashes expected below it (option batch_large_want)
-// A large handle's partitions.  With every position a distinct k-mer and uniform hashes, the number of a file's hashes below its
-// threshold is Binomial(len, want n / len): mean 4 n, standard deviation below sqrt(4 n) = 256 at n = 16 384.  The live and
-// dropped-slot lists (and the key scratch) hold 4 n + 8192 -- 32 standard deviations at the largest n, more at every smaller
-// one -- rounded up to 1024; the table twice that, so it is at most half full; a shard list eight times its mean share
-// (live_cap / 32 against live_cap / 256: the small partitions' 512 against 48 is the same order).
-struct LargeGeometry {
-    uint32_t cap, live_cap, shard_cap;
-};
-LargeGeometry large_geometry(uint64_t n) {
-    LargeGeometry g;
-    g.live_cap = (uint32_t)((LARGE_WANT * n + 8192 + 1023) & ~1023ull);
-    g.cap = 2 * g.live_cap;
-    g.shard_cap = g.live_cap / 32;
-    return g;
-}
-// rows of a Scaled sketch: what the epilogue's workgroup holds the keys of in LDS.  The partition does not bind it: its table is
-// 37 % full at that many entries, its live and dropped-slot lists hold PART_LIVE, and the 256 shard lists take 512 each of
-// inserts that are dealt over them drain by drain (48 on average).
-constexpr uint64_t BATCH_SCALED_MAX = FH_BATCH_SCALED_MAX;
-static_assert(BATCH_SCALED_MAX == (uint64_t)SMALL_MAX && BATCH_SCALED_MAX <= PART_LIVE && 2 * BATCH_SCALED_MAX <= PART_CAP,
-              "a Scaled batch sketch fits the epilogue's LDS block and the partition");
-constexpr uint32_t BATCH_MAX_FILES = 4096;
-constexpr uint64_t BATCH_MAX_WAVES = 4096; // 16 per CU x 256 CUs
-// an AllCounts handle's staging buffer: below 2^21 tiles of the two-bit form, so that no file has 2^32 positions (the 4 KiB
-// rounding of stage_bytes stays below it too)
-constexpr uint64_t COUNTS_MAX_STAGE = (1ull << 21) * fh_pack2::TILE_BYTES - 4096;
+namespace bp = fh::bplan;
+using bp::Form;
 
-uint64_t expected_below(uint64_t n) { return n <= 2000 ? 4 * n : 3 * n; }
+// what fh_batch_plan.h mirrors of the device's headers
+static_assert(bp::EMPTY == EMPTY64 && bp::FIN_OK == FIN_OK_RESET && bp::SMALL_ROWS == (uint64_t)SMALL_MAX && bp::LARGE_ROWS == (uint64_t)LARGE_MAX_ROWS &&
+                  bp::COUNTS_MAX_K == (uint32_t)AC_LDS_MAX_K && bp::MAX_K == (uint32_t)FH_MAX_K && bp::SHARDS == (uint64_t)N_SHARDS &&
+                  bp::SHARD_CURSOR_STRIDE == (uint64_t)SHARD_STRIDE && bp::TWO_BIT_TILE == fh_pack2::TILE_BYTES,
+              "fh_batch_plan.h restates a constant of fh_device.h, fh_kernels.h or fh_pack2.h");
+static_assert(bp::ENTRY_BYTES == sizeof(Entry) && bp::CTL_BYTES == sizeof(Ctl) && bp::COLL_BYTES == sizeof(CollRec) && bp::FILE_BYTES == sizeof(BatchFile),
+              "fh_batch_plan.h restates the size of a structure of fh_device.h");
+constexpr uint32_t PART_CLOG = bp::PART_CLOG;
+constexpr uint64_t BATCH_MAX_WAVES = 4096; // 16 per CU x 256 CUs
 
 } // namespace
 
-struct fh_batch {
-    fh_params p{};
-    bool counts = false;   // made by fh_batch_new_counts: p.kind == FH_KIND_ALL_COUNTS, p.k = 1..7, the rest of p unused
-    bool large = false;    // made by fh_batch_new_large: Mash, 3000 < p.size <= FH_BATCH_LARGE_MAX_N, partitions of large_geometry(p.size)
-    uint32_t cap = PART_CAP, live_cap = PART_LIVE, shard_cap = PART_SHARD_CAP; // a partition's table, lists and shard lists
-    uint64_t dev_bytes = 0; // large: device memory the handle holds (what parking it costs, fh_batch_free)
-    uint64_t max_hash = 0; // FH_KIND_SCALED: the threshold of every file (EMPTY64 at scale 1: everything is admitted)
-    int device = 0;
+// (its sizes -- cap, live_cap, shard_cap, out_stride, out_words, header_bytes, data_bytes, dev_bytes -- are the plan's Geometry)
+struct fh_batch : bp::Geometry {
+    fh_batch(Form f, const fh_params &params, int dev, uint32_t files, uint64_t stage_bytes)
+        : bp::Geometry(bp::geometry(f, params, files, stage_bytes)), form(f), p(params), counts(f == Form::Counts), large(f == Form::Large),
+          max_hash(params.kind == FH_KIND_SCALED ? api_scaled_max_hash(params.scale) : 0), device(dev), max_files(files) {}
+    bp::PoolKey key() const { return bp::PoolKey{form, device, max_files, data_bytes, p}; }
+    const Form form;       // the door it was made through
+    const fh_params p;     // (counts: p.kind == FH_KIND_ALL_COUNTS, p.k = 1..7, the rest unused)
+    const bool counts, large;
+    const uint64_t max_hash; // FH_KIND_SCALED: the threshold of every file (EMPTY64 at scale 1: everything is admitted)
+    const int device;
     hipStream_t stream = nullptr;
-    uint32_t max_files = 0;
-    uint64_t data_bytes = 0, header_bytes = 0;
-    uint32_t out_stride = 0; // entries between the columns of one sketch
-    size_t out_words = 0;    // u64 words of one sketch's columns
+    const uint32_t max_files;
     // partitions
     Ctl *ctls = nullptr;
     Entry *tables = nullptr;
@@ -181,144 +158,109 @@ void destroy(fh_batch *b) {
     delete b;
 }
 
+// what a handle of any door holds, every size from the plan (the handle's Geometry base): the partitions (or a count's tables),
+// and per slot the staging buffers, the result columns and the epilogue's arguments
 int build(fh_batch *b) {
     const uint32_t F = b->max_files;
-    const bool wide = b->p.k > 32;
-    const uint32_t PCAP = b->cap, PLIVE = b->live_cap, PSHARD = b->shard_cap; // (the small geometry unless the handle is large)
+    const bool wide = b->form == Form::Wide, scaled = b->p.kind == FH_KIND_SCALED;
+    const uint32_t PCAP = b->cap, PLIVE = b->live_cap, PSHARD = b->shard_cap;
     BHIP_TRY(hipSetDevice(b->device));
     BHIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    if (wide) BHIP_TRY(api_dev_malloc((void **)&b->kmer_hi, (size_t)F * PCAP * sizeof(uint64_t)));
-    if (b->large) BHIP_TRY(api_dev_malloc((void **)&b->keys, (size_t)F * PLIVE * sizeof(uint64_t)));
-    BHIP_TRY(api_dev_malloc((void **)&b->ctls, (size_t)F * sizeof(Ctl)));
-    BHIP_TRY(api_dev_malloc((void **)&b->tables, (size_t)F * PCAP * sizeof(Entry)));
-    BHIP_TRY(api_dev_malloc((void **)&b->live, (size_t)F * PLIVE * sizeof(uint32_t)));
-    BHIP_TRY(api_dev_malloc((void **)&b->dead, (size_t)F * PLIVE * sizeof(uint32_t)));
-    BHIP_TRY(api_dev_malloc((void **)&b->shard_cnt, (size_t)F * N_SHARDS * SHARD_STRIDE * sizeof(uint32_t)));
-    BHIP_TRY(api_dev_malloc((void **)&b->shard_buf, (size_t)F * N_SHARDS * PSHARD * sizeof(uint32_t)));
-    BHIP_TRY(api_dev_malloc((void **)&b->clog, (size_t)F * PART_CLOG * sizeof(CollRec)));
-    BHIP_TRY(api_dev_malloc((void **)&b->d_parts, (size_t)F * sizeof(BatchPartition)));
-    std::vector<BatchPartition> parts(F);
-    for (uint32_t f = 0; f < F; ++f) {
-        BatchPartition &q = parts[f];
-        q.ctl = b->ctls + f;
-        q.table = b->tables + (size_t)f * PCAP;
-        q.live = b->live + (size_t)f * PLIVE;
-        q.shard_cnt = b->shard_cnt + (size_t)f * N_SHARDS * SHARD_STRIDE;
-        q.shard_buf = b->shard_buf + (size_t)f * N_SHARDS * PSHARD;
-        q.clog = b->clog + (size_t)f * PART_CLOG;
-        q.cap = PCAP;
-        q.live_cap = PLIVE;
-        q.clog_cap = PART_CLOG;
-        q.shard_cap = PSHARD;
-        q.kmer_hi = wide ? b->kmer_hi + (size_t)f * PCAP : nullptr;
+    std::vector<BatchPartition> parts(b->counts ? 0 : F);
+    if (b->counts) {
+        const size_t bytes = (size_t)F * (size_t)ac_bins((int)b->p.k) * sizeof(uint32_t);
+        BHIP_TRY(api_dev_malloc((void **)&b->ac_tables, bytes));
+        BHIP_TRY(hipMemsetAsync(b->ac_tables, 0, bytes, b->stream));
+    } else {
+        if (wide) BHIP_TRY(api_dev_malloc((void **)&b->kmer_hi, (size_t)F * PCAP * sizeof(uint64_t)));
+        if (b->large) BHIP_TRY(api_dev_malloc((void **)&b->keys, (size_t)F * PLIVE * sizeof(uint64_t)));
+        BHIP_TRY(api_dev_malloc((void **)&b->ctls, (size_t)F * sizeof(Ctl)));
+        BHIP_TRY(api_dev_malloc((void **)&b->tables, (size_t)F * PCAP * sizeof(Entry)));
+        BHIP_TRY(api_dev_malloc((void **)&b->live, (size_t)F * PLIVE * sizeof(uint32_t)));
+        BHIP_TRY(api_dev_malloc((void **)&b->dead, (size_t)F * PLIVE * sizeof(uint32_t)));
+        BHIP_TRY(api_dev_malloc((void **)&b->shard_cnt, (size_t)F * N_SHARDS * SHARD_STRIDE * sizeof(uint32_t)));
+        BHIP_TRY(api_dev_malloc((void **)&b->shard_buf, (size_t)F * N_SHARDS * PSHARD * sizeof(uint32_t)));
+        BHIP_TRY(api_dev_malloc((void **)&b->clog, (size_t)F * PART_CLOG * sizeof(CollRec)));
+        BHIP_TRY(api_dev_malloc((void **)&b->d_parts, (size_t)F * sizeof(BatchPartition)));
+        for (uint32_t f = 0; f < F; ++f) {
+            BatchPartition &q = parts[f];
+            q.ctl = b->ctls + f;
+            q.table = b->tables + (size_t)f * PCAP;
+            q.live = b->live + (size_t)f * PLIVE;
+            q.shard_cnt = b->shard_cnt + (size_t)f * N_SHARDS * SHARD_STRIDE;
+            q.shard_buf = b->shard_buf + (size_t)f * N_SHARDS * PSHARD;
+            q.clog = b->clog + (size_t)f * PART_CLOG;
+            q.cap = PCAP;
+            q.live_cap = PLIVE;
+            q.clog_cap = PART_CLOG;
+            q.shard_cap = PSHARD;
+            q.kmer_hi = wide ? b->kmer_hi + (size_t)f * PCAP : nullptr;
+        }
+        BHIP_TRY(hipMemcpyAsync(b->d_parts, parts.data(), (size_t)F * sizeof(BatchPartition), hipMemcpyHostToDevice, b->stream));
+        BHIP_TRY(launch_batch_init(b->d_parts, F, b->p.size, scaled ? b->max_hash : EMPTY64, scaled ? b->max_hash : 0ull, 1u, b->stream));
     }
-    BHIP_TRY(hipMemcpyAsync(b->d_parts, parts.data(), (size_t)F * sizeof(BatchPartition), hipMemcpyHostToDevice, b->stream));
-    const bool scaled = b->p.kind == FH_KIND_SCALED;
-    BHIP_TRY(launch_batch_init(b->d_parts, F, b->p.size, scaled ? b->max_hash : EMPTY64, scaled ? b->max_hash : 0ull, 1u, b->stream));
-    // a sketch's columns as fh_finish lays them out: hash | k-mer | first position | [k > 32: high k-mer word] | count | extra,
-    // out_stride entries apart
-    // (a Scaled sketch has up to BATCH_SCALED_MAX rows whatever its size)
-    const uint64_t rows = scaled ? BATCH_SCALED_MAX : std::min<uint64_t>(b->p.size + 1, b->large ? BATCH_LARGE_MAX_N + 1 : (uint64_t)SMALL_MAX);
-    b->out_stride = (uint32_t)(((size_t)rows + 2) & ~(size_t)1);
-    b->out_words = (size_t)b->out_stride * (wide ? 5 : 4); // (3 or 4) x 8 + 2 x 4 bytes per entry
-    b->header_bytes = (((uint64_t)F * sizeof(BatchFile)) + 4095) & ~4095ull;
+    // what the two epilogues' arguments share: file f's partition and where its result goes
+    auto epi_common = [&](auto &e, const fh_batch::Slot &s, uint32_t f) {
+        e.table = parts[f].table;
+        e.live = parts[f].live;
+        e.dead = b->dead + (size_t)f * PLIVE;
+        e.dead_cap = PLIVE;
+        e.ctl = parts[f].ctl;
+        e.size = b->p.size;
+        e.out = s.h_out + (size_t)f * b->out_words;
+        e.out_stride = b->out_stride;
+        e.h_ctl = s.h_ctl + f;
+    };
+    std::vector<EpiArgs> epi(b->counts || b->large ? 0 : F);
+    std::vector<EpiLargeArgs> epi_large(b->large ? F : 0);
     for (auto &s : b->slot) {
         BHIP_TRY(api_host_malloc((void **)&s.h_stage, b->header_bytes + b->data_bytes + 64));
         BHIP_TRY(api_dev_malloc((void **)&s.d_stage, b->header_bytes + b->data_bytes + 64));
-        if (b->large) BHIP_TRY(api_dev_malloc((void **)&s.d_epi_large, (size_t)F * sizeof(EpiLargeArgs)));
-        else BHIP_TRY(api_dev_malloc((void **)&s.d_epi, (size_t)F * sizeof(EpiArgs)));
-        BHIP_TRY(api_host_malloc((void **)&s.h_ctl, (size_t)F * sizeof(Ctl)));
         BHIP_TRY(api_host_malloc((void **)&s.h_out, (size_t)F * b->out_words * sizeof(uint64_t)));
         BHIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
         BHIP_TRY(hipEventCreate(&s.k0));
         BHIP_TRY(hipEventCreate(&s.k1));
-        std::vector<EpiLargeArgs> epi_large(b->large ? F : 0);
-        for (uint32_t f = 0; f < F && b->large; ++f) {
-            EpiLargeArgs &e = epi_large[f];
+        s.len.resize(F);
+        s.status.resize(F);
+        if (b->counts) {
+            BHIP_TRY(api_host_malloc((void **)&s.h_res, (size_t)F * sizeof(AcBatchResult)));
+            continue;
+        }
+        s.tau.resize(F);
+        BHIP_TRY(api_host_malloc((void **)&s.h_ctl, (size_t)F * sizeof(Ctl)));
+        for (EpiLargeArgs &e : epi_large) {
+            const uint32_t f = (uint32_t)(&e - epi_large.data());
             e = EpiLargeArgs{};
-            e.table = parts[f].table;
-            e.live = parts[f].live;
-            e.dead = b->dead + (size_t)f * PLIVE;
+            epi_common(e, s, f);
             e.shard_cnt = parts[f].shard_cnt;
             e.shard_buf = parts[f].shard_buf;
             e.keys = b->keys + (size_t)f * PLIVE;
-            e.ctl = parts[f].ctl;
-            e.size = b->p.size;
             e.cap = PCAP;
             e.live_cap = PLIVE;
-            e.dead_cap = PLIVE;
             e.shard_cap = PSHARD;
-            e.out = s.h_out + (size_t)f * b->out_words;
-            e.out_stride = b->out_stride;
-            e.h_ctl = s.h_ctl + f;
+        }
+        for (EpiArgs &e : epi) {
+            e = EpiArgs{};
+            epi_common(e, s, (uint32_t)(&e - epi.data()));
+            e.kind = b->p.kind;
+            e.max_hash = b->max_hash;
+            e.flags = EPI_FLATTEN | EPI_PRUNE_FORCE | EPI_SORT | EPI_GATHER | EPI_RESET | (scaled ? EPI_KEEP_ALL : 0u);
+            e.tau0 = scaled ? b->max_hash : EMPTY64;
+            e.wide = wide ? 1u : 0u;
         }
         if (b->large) {
+            BHIP_TRY(api_dev_malloc((void **)&s.d_epi_large, (size_t)F * sizeof(EpiLargeArgs)));
             BHIP_TRY(hipMemcpyAsync(s.d_epi_large, epi_large.data(), (size_t)F * sizeof(EpiLargeArgs), hipMemcpyHostToDevice, b->stream));
-            BHIP_TRY(hipStreamSynchronize(b->stream)); // (epi_large is a local)
-        }
-        std::vector<EpiArgs> epi(b->large ? 0 : F);
-        for (uint32_t f = 0; f < F && !b->large; ++f) {
-            EpiArgs &e = epi[f];
-            e = EpiArgs{};
-            e.table = parts[f].table;
-            e.live = parts[f].live;
-            e.dead = b->dead + (size_t)f * PLIVE;
-            e.dead_cap = PLIVE;
-            e.ctl = parts[f].ctl;
-            e.kind = b->p.kind;
-            e.size = b->p.size;
-            e.max_hash = b->max_hash;
-            e.trigger = 0;
-            e.flags = EPI_FLATTEN | EPI_PRUNE_FORCE | EPI_SORT | EPI_GATHER | EPI_RESET | (scaled ? EPI_KEEP_ALL : 0u);
-            e.n_units = 0;
-            e.check_units = 0;
-            e.tau0 = scaled ? b->max_hash : EMPTY64;
-            e.hist_on = 0;
-            e.out = s.h_out + (size_t)f * b->out_words;
-            e.out_stride = b->out_stride;
-            e.wide = wide ? 1u : 0u;
-            e.h_ctl = s.h_ctl + f;
-        }
-        if (!b->large) {
+        } else {
+            BHIP_TRY(api_dev_malloc((void **)&s.d_epi, (size_t)F * sizeof(EpiArgs)));
             BHIP_TRY(hipMemcpyAsync(s.d_epi, epi.data(), (size_t)F * sizeof(EpiArgs), hipMemcpyHostToDevice, b->stream));
-            BHIP_TRY(hipStreamSynchronize(b->stream)); // (epi / parts are locals)
         }
-        s.tau.resize(F);
-        s.len.resize(F);
-        s.status.resize(F);
+        BHIP_TRY(hipStreamSynchronize(b->stream)); // (the next slot refills epi / epi_large; parts is a local)
     }
     BHIP_TRY(hipStreamSynchronize(b->stream));
-    b->dev_bytes = (uint64_t)F * ((uint64_t)PCAP * (sizeof(Entry) + (wide ? 8 : 0)) + (uint64_t)PLIVE * (8 + (b->large ? 8 : 0)) +
-                                  (uint64_t)N_SHARDS * (PSHARD + SHARD_STRIDE) * 4 + sizeof(Ctl) + PART_CLOG * sizeof(CollRec)) +
-                   2 * (b->header_bytes + b->data_bytes + 64);
     return FH_OK;
 }
 
-int build_counts(fh_batch *b) {
-    const uint32_t F = b->max_files;
-    const size_t bins = (size_t)ac_bins((int)b->p.k);
-    BHIP_TRY(hipSetDevice(b->device));
-    BHIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    BHIP_TRY(api_dev_malloc((void **)&b->ac_tables, (size_t)F * bins * sizeof(uint32_t)));
-    BHIP_TRY(hipMemsetAsync(b->ac_tables, 0, (size_t)F * bins * sizeof(uint32_t), b->stream));
-    // a file's columns hold the most rows to_vec can emit from 4^k bins: (4^k + palindromes) / 2
-    b->out_stride = (ac_max_rows((int)b->p.k) + 1u) & ~1u;
-    b->out_words = (size_t)b->out_stride * 3 / 2; // 3 x 4 bytes per entry
-    b->header_bytes = (((uint64_t)F * sizeof(BatchFile)) + 4095) & ~4095ull;
-    for (auto &s : b->slot) {
-        BHIP_TRY(api_host_malloc((void **)&s.h_stage, b->header_bytes + b->data_bytes + 64));
-        BHIP_TRY(api_dev_malloc((void **)&s.d_stage, b->header_bytes + b->data_bytes + 64));
-        BHIP_TRY(api_host_malloc((void **)&s.h_res, (size_t)F * sizeof(AcBatchResult)));
-        BHIP_TRY(api_host_malloc((void **)&s.h_out, (size_t)F * b->out_words * sizeof(uint64_t)));
-        BHIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-        BHIP_TRY(hipEventCreate(&s.k0));
-        BHIP_TRY(hipEventCreate(&s.k1));
-        s.len.resize(F);
-        s.status.resize(F);
-    }
-    BHIP_TRY(hipStreamSynchronize(b->stream));
-    return FH_OK;
-}
 
 std::mutex g_pool_mu;
 std::vector<fh_batch *> g_pool;
@@ -351,250 +293,62 @@ static bool device_ok(int device) {
     return true;
 }
 
-// what fh_batch_new and fh_batch_new_wide share behind their parameter checks: the sizes, the device, a parked handle of the
-// same parameters (k among them, so neither constructor is handed the other's) or a new one
-static fh_batch *batch_new_checked(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
-    const bool scaled = params->kind == FH_KIND_SCALED;
-    if (max_files < 1 || max_files > BATCH_MAX_FILES || stage_bytes < 4096 || stage_bytes > (1ull << 36)) {
-        api_fail(FH_ERR_INVALID, "max_files 1..%u, stage_bytes 4 KiB..64 GiB", BATCH_MAX_FILES);
+// what the four doors share: the door's parameter check (fh_batch_plan.h), the device, a parked handle the plan's predicate
+// lets out through this door, or a new one
+static fh_batch *batch_new(Form form, const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
+    if (!params) {
+        api_fail(FH_ERR_INVALID, "null params");
+        return nullptr;
+    }
+    const bp::Verdict v = bp::check(form, params, max_files, stage_bytes);
+    if (v.code != FH_OK) {
+        api_fail(v.code, "%s", v.msg);
         return nullptr;
     }
     if (!device_ok(device)) return nullptr;
     {
+        const bp::PoolKey want{form, device, max_files, bp::stage_rounded(stage_bytes), *params};
         std::lock_guard<std::mutex> g(g_pool_mu);
         for (size_t i = 0; i < g_pool.size(); ++i) {
             fh_batch *c = g_pool[i];
-            if (!c->counts && !c->large && c->device == device && c->max_files == max_files && c->data_bytes == ((stage_bytes + 4095) & ~4095ull) &&
-                c->p.k == params->k && c->p.size == params->size && c->p.seed == params->seed && c->p.kind == params->kind &&
-                (!scaled || c->p.scale == params->scale)) {
+            if (bp::pool_match(c->key(), want)) {
                 g_pool.erase(g_pool.begin() + (long)i);
                 return c;
             }
         }
     }
-    fh_batch *b = new (std::nothrow) fh_batch;
-    if (!b) {
-        api_fail(FH_ERR_CAPACITY, "out of host memory");
-        return nullptr;
-    }
-    b->p = *params;
-    b->max_hash = scaled ? api_scaled_max_hash(params->scale) : 0;
-    b->device = device;
-    b->max_files = max_files;
-    b->data_bytes = (stage_bytes + 4095) & ~4095ull;
+    fh_batch *b = nullptr;
     try {
-        if (build(b) != FH_OK) {
-            destroy(b);
-            return nullptr;
-        }
+        b = new fh_batch(form, *params, device, max_files, stage_bytes);
+        if (build(b) == FH_OK) return b;
     } catch (...) {
-        destroy(b);
         api_fail(FH_ERR_CAPACITY, "out of host memory");
-        return nullptr;
     }
-    return b;
+    destroy(b);
+    return nullptr;
 }
 
 extern "C" {
 
 fh_batch *fh_batch_new(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
-    if (!params) {
-        api_fail(FH_ERR_INVALID, "null params");
-        return nullptr;
-    }
-    if (params->kind == FH_KIND_ALL_COUNTS) {
-        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher serves Mash sketches only: AllCounts sketches go through an fh_sketcher");
-        return nullptr;
-    }
-    if (params->kind != FH_KIND_MASH && params->kind != FH_KIND_SCALED) {
-        api_fail(FH_ERR_INVALID, "unknown sketch kind %u", params->kind);
-        return nullptr;
-    }
-    const bool scaled = params->kind == FH_KIND_SCALED;
-    if (params->k < 1 || params->k > 32 || params->hash_mask != 0 ||
-        (scaled ? params->size > BATCH_SCALED_MAX : (params->size < 1 || params->size > BATCH_MAX_N))) {
-        api_fail(FH_ERR_UNSUPPORTED,
-                 "the batch sketcher serves Mash sketches of 1..%llu hashes and Scaled sketches of size 0..%llu, k = 1..32, no test mask (k = 33..64: fh_batch_new_wide; Mash sketches of 3001..%u hashes: fh_batch_new_large)",
-                 (unsigned long long)BATCH_MAX_N, (unsigned long long)BATCH_SCALED_MAX, (unsigned)BATCH_LARGE_MAX_N);
-        return nullptr;
-    }
-    if (scaled && !(params->scale > 0.0 && params->scale <= 1.0)) { // (as fh_new)
-        api_fail(FH_ERR_INVALID, "scale must be in (0, 1]");
-        return nullptr;
-    }
-    return batch_new_checked(params, device, max_files, stage_bytes);
+    return batch_new(Form::Small, params, device, max_files, stage_bytes);
 }
 
 fh_batch *fh_batch_new_large(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
-    if (!params) {
-        api_fail(FH_ERR_INVALID, "null params");
-        return nullptr;
-    }
-    if (params->kind == FH_KIND_SCALED || params->kind == FH_KIND_ALL_COUNTS) {
-        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_large serves Mash sketches only: %s", params->kind == FH_KIND_SCALED
-                 ? "Scaled (kind 1) batches are fh_batch_new's (k = 1..32) and fh_batch_new_wide's"
-                 : "AllCounts (kind 2) batches are fh_batch_new_counts");
-        return nullptr;
-    }
-    if (params->kind != FH_KIND_MASH) {
-        api_fail(FH_ERR_INVALID, "unknown sketch kind %u (fh_batch_new_large: 0 Mash)", params->kind);
-        return nullptr;
-    }
-    if (params->size <= BATCH_MAX_N) {
-        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_large serves Mash sketches of %llu..%u hashes: size %llu is fh_batch_new's (1..%llu)",
-                 (unsigned long long)BATCH_MAX_N + 1, (unsigned)BATCH_LARGE_MAX_N, (unsigned long long)params->size, (unsigned long long)BATCH_MAX_N);
-        return nullptr;
-    }
-    if (params->size > BATCH_LARGE_MAX_N) {
-        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_large serves Mash sketches of %llu..%u hashes (FH_BATCH_LARGE_MAX_N): size %llu goes through an fh_sketcher",
-                 (unsigned long long)BATCH_MAX_N + 1, (unsigned)BATCH_LARGE_MAX_N, (unsigned long long)params->size);
-        return nullptr;
-    }
-    if (params->k < 1 || params->k > 32) {
-        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_large serves k = 1..32: k = %u goes through an fh_sketcher", params->k);
-        return nullptr;
-    }
-    if (params->hash_mask != 0) {
-        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher takes no test mask (hash_mask must be 0)");
-        return nullptr;
-    }
-    // (the bound of fh_batch_new_counts: a slot of fewer than 2^21 tiles of the two-bit form, so a file has fewer than 2^32 positions)
-    if (max_files < 1 || max_files > BATCH_MAX_FILES || stage_bytes < 4096 || stage_bytes > COUNTS_MAX_STAGE) {
-        api_fail(FH_ERR_INVALID, "max_files 1..%u, stage_bytes 4 KiB..%llu (a slot of fewer than 2^21 tiles of the two-bit form)", BATCH_MAX_FILES,
-                 (unsigned long long)COUNTS_MAX_STAGE);
-        return nullptr;
-    }
-    if (!device_ok(device)) return nullptr;
-    const uint64_t data_bytes = (stage_bytes + 4095) & ~4095ull;
-    {
-        // a parked handle: large, the same n (the partitions are sized for it), k and seed; never one of the other constructors'
-        std::lock_guard<std::mutex> g(g_pool_mu);
-        for (size_t i = 0; i < g_pool.size(); ++i) {
-            fh_batch *c = g_pool[i];
-            if (c->large && c->device == device && c->max_files == max_files && c->data_bytes == data_bytes && c->p.k == params->k &&
-                c->p.size == params->size && c->p.seed == params->seed) {
-                g_pool.erase(g_pool.begin() + (long)i);
-                return c;
-            }
-        }
-    }
-    fh_batch *b = new (std::nothrow) fh_batch;
-    if (!b) {
-        api_fail(FH_ERR_CAPACITY, "out of host memory");
-        return nullptr;
-    }
-    b->p = *params;
-    b->large = true;
-    const LargeGeometry geo = large_geometry(params->size);
-    b->cap = geo.cap;
-    b->live_cap = geo.live_cap;
-    b->shard_cap = geo.shard_cap;
-    b->device = device;
-    b->max_files = max_files;
-    b->data_bytes = data_bytes;
-    try {
-        if (build(b) != FH_OK) {
-            destroy(b);
-            return nullptr;
-        }
-    } catch (...) {
-        destroy(b);
-        api_fail(FH_ERR_CAPACITY, "out of host memory");
-        return nullptr;
-    }
-    return b;
+    return batch_new(Form::Large, params, device, max_files, stage_bytes);
 }
 
 fh_batch *fh_batch_new_wide(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes) {
-    if (!params) {
-        api_fail(FH_ERR_INVALID, "null params");
-        return nullptr;
-    }
-    if (params->kind == FH_KIND_ALL_COUNTS) {
-        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher for k = 33..64 serves Mash and Scaled sketches: AllCounts (kind 2) batches are fh_batch_new_counts, k = 1..%d",
-                 AC_LDS_MAX_K);
-        return nullptr;
-    }
-    if (params->kind != FH_KIND_MASH && params->kind != FH_KIND_SCALED) {
-        api_fail(FH_ERR_INVALID, "unknown sketch kind %u (0 Mash, 1 Scaled)", params->kind);
-        return nullptr;
-    }
-    if (params->k <= 32) {
-        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_wide serves k = 33..64: k = %u is fh_batch_new's (k = 1..32)", params->k);
-        return nullptr;
-    }
-    if (params->k > (uint32_t)FH_MAX_K) {
-        api_fail(FH_ERR_UNSUPPORTED, "fh_batch_new_wide serves k = 33..64: k = %u is beyond what the device hashes", params->k);
-        return nullptr;
-    }
-    if (params->hash_mask != 0) {
-        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher takes no test mask (hash_mask must be 0)");
-        return nullptr;
-    }
-    const bool scaled = params->kind == FH_KIND_SCALED;
-    if (scaled ? params->size > BATCH_SCALED_MAX : (params->size < 1 || params->size > BATCH_MAX_N)) {
-        api_fail(FH_ERR_UNSUPPORTED, "the batch sketcher serves Mash sketches of 1..%llu hashes and Scaled sketches of size 0..%llu: size %llu",
-                 (unsigned long long)BATCH_MAX_N, (unsigned long long)BATCH_SCALED_MAX, (unsigned long long)params->size);
-        return nullptr;
-    }
-    if (scaled && !(params->scale > 0.0 && params->scale <= 1.0)) { // (as fh_new)
-        api_fail(FH_ERR_INVALID, "scale must be in (0, 1]");
-        return nullptr;
-    }
-    return batch_new_checked(params, device, max_files, stage_bytes);
+    return batch_new(Form::Wide, params, device, max_files, stage_bytes);
 }
 
 fh_batch *fh_batch_new_counts(uint32_t k, int device, uint32_t max_files, uint64_t stage_bytes) {
-    if (k < 1) {
-        api_fail(FH_ERR_INVALID, "kmer_length must be at least 1");
-        return nullptr;
-    }
-    if (k > (uint32_t)AC_LDS_MAX_K) {
-        api_fail(FH_ERR_UNSUPPORTED, "the AllCounts batch sketcher serves k = 1..%d (one file's 4^k counts in a workgroup's LDS): k = %u goes through an fh_sketcher",
-                 AC_LDS_MAX_K, k);
-        return nullptr;
-    }
-    // fewer than 2^32 positions per file, whichever form it is staged in: a slot of fewer than 2^21 tiles of the two-bit form
-    if (max_files < 1 || max_files > BATCH_MAX_FILES || stage_bytes < 4096 || stage_bytes > COUNTS_MAX_STAGE) {
-        api_fail(FH_ERR_INVALID, "max_files 1..%u, stage_bytes 4 KiB..%llu (an AllCounts file has fewer than 2^32 positions)", BATCH_MAX_FILES,
-                 (unsigned long long)COUNTS_MAX_STAGE);
-        return nullptr;
-    }
-    if (!device_ok(device)) return nullptr;
-    const uint64_t data_bytes = (stage_bytes + 4095) & ~4095ull;
-    {
-        std::lock_guard<std::mutex> g(g_pool_mu);
-        for (size_t i = 0; i < g_pool.size(); ++i) {
-            fh_batch *c = g_pool[i];
-            if (c->counts && c->p.k == k && c->device == device && c->max_files == max_files && c->data_bytes == data_bytes) {
-                g_pool.erase(g_pool.begin() + (long)i);
-                return c;
-            }
-        }
-    }
-    fh_batch *b = new (std::nothrow) fh_batch;
-    if (!b) {
-        api_fail(FH_ERR_CAPACITY, "out of host memory");
-        return nullptr;
-    }
-    b->counts = true;
-    b->p.kind = FH_KIND_ALL_COUNTS;
-    b->p.k = k;
-    b->device = device;
-    b->max_files = max_files;
-    b->data_bytes = data_bytes;
-    try {
-        if (build_counts(b) != FH_OK) {
-            destroy(b);
-            return nullptr;
-        }
-    } catch (...) {
-        destroy(b);
-        api_fail(FH_ERR_CAPACITY, "out of host memory");
-        return nullptr;
-    }
-    return b;
+    fh_params p{};
+    p.kind = FH_KIND_ALL_COUNTS;
+    p.k = k;
+    return batch_new(Form::Counts, &p, device, max_files, stage_bytes);
 }
+
 
 // A batch handle owns ~130 MiB of pinned and ~200 MiB of device memory, and pinning alone takes tens of milliseconds:
 // like fh_free, fh_batch_free parks an idle handle (state clean: every partition is left reset by its epilogue) and
@@ -682,19 +436,8 @@ static int batch_submit(fh_batch *b, int slot, const uint64_t *offsets, const ui
         d.seq = s.d_stage + b->header_bytes + offsets[f];
         d.len = lens[f];
         d.ctl = b->counts ? nullptr : b->ctls + f;
-        // the threshold below which E of the file's positions' hashes are expected (every position a distinct k-mer, hashes uniform)
-        // (large: option batch_large_want in place of the factor -- tests force a short guess or a full live list with it)
-        const uint64_t E = b->large ? std::max<uint64_t>(1, cfg_u64("batch_large_want", LARGE_WANT)) * b->p.size : expected_below(b->p.size);
-        uint64_t tau = EMPTY64;
-        if (b->counts) {
-            tau = 0; // (not looked at)
-        } else if (b->p.kind == FH_KIND_SCALED) {
-            tau = b->max_hash; // (u64::MAX at scale 1 is EMPTY64: everything is admitted, and the one hash that cannot be a
-                               // table key is counted in sp_count, which sends the file the long way)
-        } else if (lens[f] > E) {
-            tau = (uint64_t)((((unsigned __int128)E) << 64) / lens[f]);
-            if (tau >= EMPTY64 - 1) tau = EMPTY64;
-        }
+        // (large: option batch_large_want in place of the plan's factor -- tests force a short guess or a full live list with it)
+        const uint64_t tau = bp::tau(b->form, b->p.kind, b->p.size, b->max_hash, lens[f], b->large ? cfg_u64("batch_large_want", bp::LARGE_WANT) : 0);
         d.tau = tau;
         d.tile0 = (uint32_t)tiles;
         d.n_tiles = (uint32_t)n_tiles;
@@ -812,14 +555,7 @@ int fh_batch_wait(fh_batch *b, int slot, uint8_t *status) {
         }
         for (uint32_t f = 0; !b->counts && f < s.n_files; ++f) {
             const Ctl &c = s.h_ctl[f];
-            // taken iff the epilogue finished the sketch and left the partition reset, the guess held (or admitted everything),
-            // no two k-mers shared a hash and the one hash value that cannot be a table key did not occur
-            const bool fin = c.sorted == FIN_OK_RESET && c.overflow == 0 && c.need_big == 0;
-            // Scaled: every live entry is <= max_hash by construction; they are the sketch iff there are at least `size` of them
-            const bool scaled = b->p.kind == FH_KIND_SCALED;
-            const bool full = scaled ? (uint64_t)c.n_live >= b->p.size : (s.tau[f] == EMPTY64 || c.inserted_total >= b->p.size);
-            const bool rows = scaled ? (uint64_t)c.n_live <= BATCH_SCALED_MAX : (uint64_t)c.n_live <= b->p.size;
-            const bool ok = fin && full && c.n_coll == 0 && c.sp_count == 0 && rows;
+            const bool ok = bp::taken(b->p.kind, b->p.size, bp::Outcome{c.sorted, c.overflow, c.need_big, c.n_coll, c.n_live, c.sp_count, c.inserted_total}, s.tau[f]);
             s.status[f] = ok ? 0 : 1;
             if (ok) b->n_taken++;
             else b->n_not_taken++;

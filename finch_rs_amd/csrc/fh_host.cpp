@@ -34,6 +34,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "fh_batch_plan.h"
 #include "fh_host_model.h"
 #include "fh_options.h"
 #include "fh_inflate.h"
@@ -3945,6 +3946,300 @@ int finch_sketch_buffer(const uint8_t *data, uint64_t len, const char *name, con
     return FH_OK;
 } FINCH_CATCH
 
+} // extern "C"
+
+namespace {
+
+// What the workers of one finch_sketch_files call share: its arguments and results, what the plan (fh_batch_plan.h) says of its
+// files, and the first error by file index.
+struct FilesCall {
+    const char *const *filenames;
+    const finch_sketch_params &sp;
+    const finch_filter_params &filters;
+    std::vector<Sketch> &out;
+    unsigned read_threads;
+    fh::bplan::FilePlan plan{};                       // ok: the files go many per launch, through a handle of plan.form for plan.group_n hashes
+    uint64_t max_hash = 0;                            // ... of Scaled sketches: the threshold of every file
+    uint32_t group_files = fh::bplan::GROUP_FILES;    // files per group, and per handle
+    size_t read_piece = 0;                            // bytes of a file read and packed at a time
+    std::mutex err_mu;
+    int first_err_code = FH_OK;
+    uint32_t first_err_idx = UINT32_MAX;
+    std::string first_err_msg;
+    void record_error(uint32_t i, int rc, const std::string &msg) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (i < first_err_idx) {
+            first_err_idx = i;
+            first_err_code = rc;
+            first_err_msg = msg;
+        }
+    }
+};
+
+// fd's `size` bytes (what fstat said) into buf, at most `piece` at a time -- every piece behind the last one if `append`, else
+// each at buf -- and each handed to take(ptr, n).  false: a read failed, the file does not begin with '>', or it has one byte
+// more than fstat said (it grew: not for the batch path).  t_read: where the time of the reads is added (or null).
+template <class Take>
+bool read_fasta_unchanged(int fd, size_t size, uint8_t *buf, size_t piece, bool append, double *t_read, Take take) {
+    for (size_t got = 0; got < size;) {
+        uint8_t *const at = buf + (append ? got : 0);
+        const double p0 = t_read ? now_s() : 0;
+        const ssize_t r = pread(fd, at, std::min(piece, size - got), (off_t)got);
+        if (r <= 0 || (got == 0 && at[0] != '>')) return false;
+        if (t_read) *t_read += now_s() - p0;
+        take(at, (size_t)r);
+        got += (size_t)r;
+    }
+    uint8_t extra;
+    return pread(fd, &extra, 1, (off_t)size) <= 0;
+}
+
+// One worker of finch_sketch_files: the sketchers its files go through one by one (sketch_stream), and the many-files-per-launch
+// path (fh_batch_*, fh_k2b.hip): the worker stages the packed streams of plain FASTA files side by side in a slot of its batch
+// handle and has them sketched by ONE launch, finished by ONE epilogue launch (a workgroup per file), behind one copy and in
+// front of one synchronisation -- while it stages the next group in the other slot.  Applies to what a batch of genomes is and
+// the batch sketcher's doors take (fh_batch_plan.h: check, plan_files): Mash sketches (after the cut to final_size the small
+// sketcher makes) and Scaled ones, k <= 64 (above 32 through a handle of fh_batch_new_wide), the larger Mash sizes at k <= 32
+// (`-n 10000`) through a handle of fh_batch_new_large, whose partitions are several MiB a file -- such groups hold
+// `batch_large_files` files (default 16), not 64; no filtering (the default for FASTA, lib.rs:70-76), regular uncompressed
+// files that begin with '>'.
+// Anything else, and every file the batch path reports as not taken, goes through sketch_stream.
+// Scaled sketches (kind 1): a file is sketched at max_hash and taken iff it holds between kmers_to_sketch and
+// FH_BATCH_SCALED_MAX distinct hashes at or below it (fh_batch.hip); process_post_filter leaves a Scaled sketch as it is.
+// AllCounts (kind 2) through a handle of fh_batch_new_counts: every staged file is taken (a count is exact for any
+// input), there is no strict error and no truncation (process_post_filter does nothing, mod.rs:115-128), seq_length is 0.
+class FileWorker {
+public:
+    FileWorker(FilesCall &call, const fh_params &full, int device, uint32_t w)
+        : c_(call), w_(w), two_bit_(!(cfg("batch_two_bit") && cfg("batch_two_bit")[0] == '0')), trace_(trace_on()), t_worker0_(now_s()) {
+        handles_.full = full;
+        handles_.final_size = call.sp.final_size;
+        handles_.device = device;
+    }
+    ~FileWorker() {
+        if (bt_) fh_batch_free(bt_); // (left by an exception only)
+    }
+
+    void through_sketcher(uint32_t i) { // one file through its own sketcher (sketch_stream, lib.rs:51-94)
+        int rc = FH_OK;
+        std::string msg;
+        const std::string fn = c_.filenames[i];
+        FILE *f = fn == "-" ? stdin : fopen(fn.c_str(), "rb");
+        if (!f) {
+            rc = FH_ERR_INVALID;
+            msg = fn + ": " + strerror(errno) + " (os error " + std::to_string(errno) + ")";
+        } else {
+            rc = sketch_stream(std::make_unique<FileSource>(f, f != stdin, c_.read_threads), fn, c_.sp, c_.filters, handles_, c_.out[i]);
+            if (rc != FH_OK) msg = g_host_err;
+        }
+        if (rc != FH_OK) c_.record_error(i, rc, msg);
+    }
+
+    bool try_stage(uint32_t i) { // true: file i is part of the current group
+        if (!c_.plan.ok || bt_failed_) return false;
+        const char *fn = c_.filenames[i];
+        if (strcmp(fn, "-") == 0) return false;
+        const int fd = open(fn, O_RDONLY | O_CLOEXEC);
+        if (fd < 0) return false; // (sketch_stream reports it)
+        const bool staged = stage_fd(fd, i);
+        close(fd);
+        return staged;
+    }
+
+    void finish() { // the last groups, the counters, the handle back
+        if (!bt_) return;
+        submit_cur();
+        collect(0);
+        collect(1);
+        if (g_ktimes_on.load(std::memory_order_relaxed)) {
+            double ms = 0;
+            uint64_t nl = 0, np = 0;
+            if (fh_batch_kernel_time(bt_, &ms, &nl, &np) == FH_OK) {
+                g_ktimes_us += (uint64_t)(ms * 1000.0 + 0.5);
+                g_ktimes_launches += nl;
+                g_ktimes_positions += np;
+            }
+        }
+        uint64_t tk = 0, nt = 0;
+        if (fh_batch_counters(bt_, &tk, &nt) == FH_OK) g_batch_taken += tk, g_batch_not_taken += nt;
+        if (trace_ && w_ == 0)
+            fprintf(stderr, "[finch] worker 0 of a batch: %.1f ms in all: reading %.1f, packing %.1f, submits %.1f, waiting for the device %.1f, results %.1f ms (%llu files taken)\n",
+                    (now_s() - t_worker0_) * 1e3, t_read_ * 1e3, t_pack_ * 1e3, t_submit_ * 1e3, t_wait_ * 1e3, t_collect_ * 1e3, (unsigned long long)tk);
+        fh_batch_free(bt_);
+        bt_ = nullptr;
+    }
+
+private:
+    struct Group {
+        std::vector<uint32_t> idx;
+        std::vector<uint64_t> off, len;
+        std::vector<FastxStats> st;
+        uint64_t fill = 0;
+        bool in_flight = false;
+        void clear() {
+            idx.clear(), off.clear(), len.clear(), st.clear();
+            fill = 0;
+        }
+    };
+
+    bool open_handle() { // the worker's batch handle, through the door the plan names, and its two staging buffers
+        fh_params bp = to_fh(c_.sp, 0);
+        bp.size = c_.plan.group_n;
+        switch (c_.plan.form) {
+        case fh::bplan::Form::Counts: bt_ = fh_batch_new_counts(c_.sp.kmer_length, handles_.device, c_.group_files, fh::bplan::GROUP_STAGE); break;
+        case fh::bplan::Form::Large: bt_ = fh_batch_new_large(&bp, handles_.device, c_.group_files, fh::bplan::GROUP_STAGE); break;
+        case fh::bplan::Form::Wide: bt_ = fh_batch_new_wide(&bp, handles_.device, c_.group_files, fh::bplan::GROUP_STAGE); break; // (two-word k-mers: fh_k2bw.hip)
+        case fh::bplan::Form::Small: bt_ = fh_batch_new(&bp, handles_.device, c_.group_files, fh::bplan::GROUP_STAGE); break;
+        }
+        if (bt_ && (fh_batch_stage(bt_, 0, &stage_[0], &stage_cap_) != FH_OK || fh_batch_stage(bt_, 1, &stage_[1], &stage_cap_) != FH_OK)) {
+            fh_batch_free(bt_);
+            bt_ = nullptr;
+        }
+        if (!bt_) {
+            bt_failed_ = true; // (no memory for it, say: every file the long way)
+            return false;
+        }
+        if (g_ktimes_on.load(std::memory_order_relaxed)) fh_batch_set_profiling(bt_, 1);
+        return true;
+    }
+
+    bool stage_fd(int fd, uint32_t i) { // file i, open as fd, into the current group (the caller closes fd)
+        struct stat sb;
+        if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size < 1 || (uint64_t)sb.st_size + 4096 > fh::bplan::GROUP_STAGE) return false;
+        if (c_.sp.kind == 1 && !fh::bplan::scaled_may_fit((uint64_t)sb.st_size, c_.max_hash)) return false;
+        const size_t size = (size_t)sb.st_size;
+        if (!bt_ && !open_handle()) return false;
+        const uint64_t room_needed = two_bit_ ? fh_pack2::region_bytes(size) + 64 : (uint64_t)size + 64;
+        if (grp_[cur_].idx.size() >= c_.group_files || grp_[cur_].fill + room_needed > stage_cap_) submit_cur();
+        Group &g = grp_[cur_];
+        FastxStats st;
+        st.format = 1;
+        size_t m = 0;
+        uint64_t occupied;
+        double *const t_read = trace_ ? &t_read_ : nullptr;
+        double r1 = 0;
+        if (two_bit_) {
+            // piece by piece: read, strip, pack while the piece is in the core's cache
+            if (!packer_) {
+                packer_.reset(new fh_pack2::Packer);
+                packer_->force_form((unsigned)cfg_u64("pack_scalar", 0));
+            }
+            if (raw_.size() < c_.read_piece + 64) raw_.resize(c_.read_piece + 64);
+            FastaTwoBit walk(*packer_, st, stage_[cur_] + g.fill);
+            const bool whole = read_fasta_unchanged(fd, size, raw_.data(), c_.read_piece, false, t_read, [&](const uint8_t *p, size_t n) {
+                const double p1 = trace_ ? now_s() : 0;
+                walk.piece(p, n);
+                if (trace_) t_pack_ += now_s() - p1;
+            });
+            if (!whole) return false; // (its region is abandoned: g.fill stays)
+            m = (size_t)walk.finish();
+            occupied = fh_pack2::region_bytes(m);
+            r1 = trace_ ? now_s() : 0;
+        } else {
+            if (raw_.size() < size + 64) raw_.resize(size + 64 + (size >> 2));
+            if (!read_fasta_unchanged(fd, size, raw_.data(), size, true, t_read, [](const uint8_t *, size_t) {})) return false;
+            r1 = trace_ ? now_s() : 0;
+            if (!pack_fasta_text(raw_.data(), size, stage_[cur_] + g.fill, (size_t)(stage_cap_ - g.fill), st, m)) return false;
+            occupied = m;
+        }
+        g.idx.push_back(i);
+        g.off.push_back(g.fill);
+        g.len.push_back(m);
+        g.st.push_back(st);
+        g.fill = (g.fill + occupied + 63) & ~63ull;
+        if (trace_) t_pack_ += now_s() - r1;
+        return true;
+    }
+
+    void submit_cur() { // hand the current group to the device, go on in the other slot (its previous group collected)
+        Group &g = grp_[cur_];
+        if (g.idx.empty()) return;
+        const double s0 = trace_ ? now_s() : 0;
+        const int src = two_bit_ ? fh_batch_submit_packed(bt_, cur_, g.off.data(), g.len.data(), (uint32_t)g.idx.size())
+                                 : fh_batch_submit(bt_, cur_, g.off.data(), g.len.data(), (uint32_t)g.idx.size());
+        if (trace_) t_submit_ += now_s() - s0;
+        if (src != FH_OK) {
+            for (uint32_t i : g.idx) through_sketcher(i);
+            g.clear();
+            return;
+        }
+        g.in_flight = true;
+        cur_ ^= 1;
+        collect(cur_);
+    }
+
+    void collect(int slot) { // wait for the group in `slot`, turn its results into Sketches
+        Group &g = grp_[slot];
+        if (!g.in_flight) return;
+        g.in_flight = false;
+        const finch_sketch_params &sp = c_.sp;
+        const bool whole_rows = sp.kind == 1 || sp.kind == 2; // Scaled, AllCounts: no cut to final_size, no strict error
+        status_.assign(g.idx.size() + 1, 1);
+        const double w0 = trace_ ? now_s() : 0;
+        int rc = fh_batch_wait(bt_, slot, status_.data());
+        const double w1 = trace_ ? now_s() : 0;
+        t_wait_ += w1 - w0;
+        for (size_t j = 0; j < g.idx.size(); ++j) {
+            const uint32_t i = g.idx[j];
+            if (rc != FH_OK || status_[j] != 0) { // not taken (or the batch failed as a whole): the long way, which is exact for anything
+                through_sketcher(i);
+                continue;
+            }
+            uint64_t n = 0, tk = 0;
+            int r2 = fh_batch_result(bt_, slot, (uint32_t)j, &n, &tk);
+            const size_t keep = whole_rows ? (size_t)n : (size_t)std::min<uint64_t>(n, sp.final_size); // process_post_filter (mod.rs:115-128)
+            const uint32_t k = sp.kmer_length;
+            std::unique_ptr<fh_kmer_count[]> recs(new fh_kmer_count[n + 1]);
+            std::unique_ptr<uint8_t[]> km(new uint8_t[n * (size_t)k + 1]);
+            if (r2 == FH_OK) r2 = fh_batch_copy_out_records(bt_, slot, (uint32_t)j, recs.get(), km.get());
+            if (r2 != FH_OK) {
+                c_.record_error(i, r2, fh_last_error());
+                continue;
+            }
+            const std::string name = c_.filenames[i];
+            if (!whole_rows && !sp.no_strict && keep < sp.final_size) {
+                char buf[512];
+                snprintf(buf, sizeof buf, "%s had too few kmers (%zu) to sketch", name.c_str(), keep);
+                c_.record_error(i, FH_ERR_INVALID, buf);
+                continue;
+            }
+            Sketch &out = c_.out[i];
+            out.name = name;
+            out.seq_length = sp.kind == 2 ? 0 : g.st[j].total_bases; // (AllCountsSketcher never counts its bases: counts.rs:9, 36-37)
+            out.num_valid_kmers = tk;
+            out.comment = "";
+            out.hashes.resize(keep);
+            for (size_t q = 0; q < keep; ++q)
+                out.hashes[q] = KmerCount{recs[q].hash, KmerBytes((const char *)km.get() + q * (size_t)k, (size_t)k), recs[q].count, recs[q].extra_count};
+            out.filter_params = c_.filters;
+            out.filter_params.filter_on = 0; // lib.rs:70-76: FASTA defaults to no filtering (plan_files: not asked for either)
+            out.sketch_params = sp;
+        }
+        g.clear();
+        if (trace_) t_collect_ += now_s() - w1;
+    }
+
+    FilesCall &c_;
+    HandleSet handles_;
+    const uint32_t w_;
+    fh_batch *bt_ = nullptr;
+    bool bt_failed_ = false;
+    Group grp_[2];
+    int cur_ = 0;
+    uint8_t *stage_[2] = {nullptr, nullptr};
+    uint64_t stage_cap_ = 0;
+    std::vector<uint8_t> raw_, status_; // a file's text as read; a group's verdicts
+    const bool two_bit_;                // how a group's files cross the link
+    std::unique_ptr<fh_pack2::Packer> packer_;
+    const bool trace_;
+    double t_read_ = 0, t_pack_ = 0, t_submit_ = 0, t_wait_ = 0, t_collect_ = 0;
+    const double t_worker0_;
+};
+
+} // namespace
+
+extern "C" {
+
 int finch_sketch_files(const char *const *filenames, uint32_t n_files, const finch_sketch_params *sp,
                        const finch_filter_params *filters, const int *devices, uint32_t n_devices, uint32_t n_threads,
                        finch_sketches **out) try {
@@ -3967,10 +4262,6 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     auto res = std::make_unique<finch_sketches>();
     res->v.resize(n_files);
     std::atomic<uint32_t> next{0};
-    std::mutex err_mu;
-    int first_err_code = FH_OK;
-    uint32_t first_err_idx = UINT32_MAX;
-    std::string first_err_msg;
     // lib.rs:34-36: par_iter over the files; here one worker = one device sketcher reused across its files
     // many files: one modest sketcher per worker (2 M positions in flight, 16 MiB staging) instead of one
     // sized for a 10 Gbase stream
@@ -3990,278 +4281,23 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     const char *rt_env = cfg("read_threads");
     const unsigned read_total = read_threads_total(rt_env);
     const unsigned read_threads = std::max(1u, read_total / n_threads);
-    // Many files per launch (fh_batch_*, fh_k2b.hip): a worker stages the packed streams of plain FASTA files side by side in
-    // a slot of its batch handle and has them sketched by ONE launch, finished by ONE epilogue launch (a workgroup per file),
-    // behind one copy and in front of one synchronisation -- while it stages the next group in the other slot.  Applies to
-    // what a batch of genomes is: Mash sketches of <= 3000 hashes (after the cut to final_size the small sketcher makes),
-    // k <= 64 (above 32 through a handle of fh_batch_new_wide), no filtering (the default for FASTA, lib.rs:70-76), regular
-    // uncompressed files that begin with '>'.
-    // Mash sketches of 3001..FH_BATCH_LARGE_MAX_N hashes at k <= 32 (`-n 10000`): through a handle of fh_batch_new_large, whose
-    // partitions are several MiB a file -- such groups hold `batch_large_files` files (default 16), not 64.  k = 33..64 at those
-    // sizes keeps going one by one.
-    // Anything else, and every file the batch path reports as not taken, goes through sketch_stream as before.
-    // Scaled sketches (kind 1) likewise: a file is sketched at max_hash and taken iff it holds between kmers_to_sketch and
-    // FH_BATCH_SCALED_MAX distinct hashes at or below it (fh_batch.hip); process_post_filter leaves a Scaled sketch as it is.
-    // AllCounts (kind 2, k <= 7) through a handle of fh_batch_new_counts: every staged file is taken (a count is exact for any
-    // input), there is no strict error and no truncation (process_post_filter does nothing, mod.rs:115-128), seq_length is 0.
-    const bool group_counts = sp->kind == 2;
-    const bool group_scaled = sp->kind == 1;
-    const uint64_t group_n = group_scaled ? sp->kmers_to_sketch
-                                          : ((sp->final_size >= 1 && sp->final_size < sp->kmers_to_sketch) ? sp->final_size : sp->kmers_to_sketch);
-    const bool group_large = sp->kind == 0 && group_n > 3000 && group_n <= FH_BATCH_LARGE_MAX_N && sp->kmer_length <= 32;
-    const bool group_ok = batch && (group_counts ? sp->kmer_length <= 7 : group_scaled ? (group_n <= FH_BATCH_SCALED_MAX && sp->scale > 0.0 && sp->scale <= 1.0) : (sp->kind == 0 && group_n >= 1 && (group_n <= 3000 || group_large))) &&
-                          sp->kmer_length >= 1 && sp->kmer_length <= 64 && filters->filter_on <= 0 && file_batch_enabled();
-    // A Scaled file whose size says it cannot fit is not staged at all (sending it would cost a wasted pass): if every byte began
-    // a distinct k-mer, st_size x max_hash / 2^64 hashes would lie at or below max_hash.  Margin: staged up to 5/4 of the cap --
-    // headers, line ends, N and repeated k-mers make the true number smaller than that estimate, never larger, so a file up to a
-    // quarter above the cap may still fit; one further above is all but certain not to (the count is a sum of ~independent
-    // draws: at 12 288 its standard deviation is ~110, the margin 28 of them).
-    const uint64_t group_max_hash = group_scaled && group_ok ? fh::api_scaled_max_hash(sp->scale) : 0;
-    const uint64_t group_max_expect = (uint64_t)FH_BATCH_SCALED_MAX + FH_BATCH_SCALED_MAX / 4;
-    constexpr uint64_t GROUP_STAGE = 32ull << 20;
+    // which door of the batch sketcher serves the call's files many per launch, if any (FileWorker above, fh_batch_plan.h)
+    FilesCall call{filenames, *sp, *filters, res->v, read_threads};
+    call.plan = fh::bplan::plan_files(sp->kind, sp->kmer_length, sp->kmers_to_sketch, sp->final_size, sp->scale, filters->filter_on, n_files);
+    call.plan.ok = call.plan.ok && file_batch_enabled();
+    call.max_hash = sp->kind == 1 && call.plan.ok ? fh::api_scaled_max_hash(sp->scale) : 0;
     // files per group, and per handle: 64, or what a large handle's memory allows (6 MiB of device memory a file at n = 10 000,
     // include/finch_hip.h: 16 files are 161 MiB a worker, and sixteen workgroups of the epilogue a launch)
-    const uint32_t GROUP_FILES = group_large ? (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, cfg_u64("batch_large_files", 16))) : 64u;
-    const size_t READ_PIECE = std::max<uint64_t>(4096, cfg_u64("batch_read_piece", 256u << 10)); // bytes of a file read and packed at a time
+    if (call.plan.form == fh::bplan::Form::Large) call.group_files = (uint32_t)std::min<uint64_t>(call.group_files, std::max<uint64_t>(1, cfg_u64("batch_large_files", 16)));
+    call.read_piece = std::max<uint64_t>(4096, cfg_u64("batch_read_piece", 256u << 10));
     auto worker = [&](uint32_t w) {
-        HandleSet handles;
-        handles.full = to_fh(*sp, batch ? ml : single_ml, batch ? (16ull << 20) : single_stage);
-        handles.final_size = sp->final_size;
-        handles.device = devs[w % devs.size()];
-        auto record_error = [&](uint32_t i, int rc, const std::string &msg) {
-            std::lock_guard<std::mutex> g(err_mu);
-            if (i < first_err_idx) {
-                first_err_idx = i;
-                first_err_code = rc;
-                first_err_msg = msg;
-            }
-        };
-        auto through_sketcher = [&](uint32_t i) { // one file through its own sketcher (sketch_stream, lib.rs:51-94)
-            int rc = FH_OK;
-            std::string msg;
-            const std::string fn = filenames[i];
-            FILE *f = fn == "-" ? stdin : fopen(fn.c_str(), "rb");
-            if (!f) {
-                rc = FH_ERR_INVALID;
-                msg = fn + ": " + strerror(errno) + " (os error " + std::to_string(errno) + ")";
-            } else {
-                rc = sketch_stream(std::make_unique<FileSource>(f, f != stdin, read_threads), fn, *sp, *filters, handles, res->v[i]);
-                if (rc != FH_OK) msg = g_host_err;
-            }
-            if (rc != FH_OK) record_error(i, rc, msg);
-        };
-        // --- the worker's groups ---
-        struct Group {
-            std::vector<uint32_t> idx;
-            std::vector<uint64_t> off, len;
-            std::vector<FastxStats> st;
-            uint64_t fill = 0;
-            bool in_flight = false;
-        } grp[2];
-        fh_batch *bt = nullptr;
-        bool bt_failed = false;
-        int cur = 0;
-        uint8_t *stage[2] = {nullptr, nullptr};
-        uint64_t stage_cap = 0;
-        std::vector<uint8_t> raw; // a file's text as read
-        const bool two_bit = !(cfg("batch_two_bit") && cfg("batch_two_bit")[0] == '0'); // how a group's files cross the link
-        std::unique_ptr<fh_pack2::Packer> packer;
-        std::vector<uint8_t> status;
-        const bool trace = trace_on();
-        double t_read = 0, t_pack = 0, t_submit = 0, t_wait = 0, t_collect = 0;
-        const double t_worker0 = now_s();
-        auto collect = [&](int slot) { // wait for the group in `slot`, turn its results into Sketches
-            Group &g = grp[slot];
-            if (!g.in_flight) return;
-            g.in_flight = false;
-            status.assign(g.idx.size() + 1, 1);
-            const double w0 = trace ? now_s() : 0;
-            int rc = fh_batch_wait(bt, slot, status.data());
-            const double w1 = trace ? now_s() : 0;
-            t_wait += w1 - w0;
-            for (size_t j = 0; j < g.idx.size(); ++j) {
-                const uint32_t i = g.idx[j];
-                if (rc != FH_OK || status[j] != 0) { // not taken (or the batch failed as a whole): the long way, which is exact for anything
-                    through_sketcher(i);
-                    continue;
-                }
-                uint64_t n = 0, tk = 0;
-                int r2 = fh_batch_result(bt, slot, (uint32_t)j, &n, &tk);
-                const size_t keep = group_scaled || group_counts ? (size_t)n : (size_t)std::min<uint64_t>(n, sp->final_size); // process_post_filter (mod.rs:115-128)
-                const uint32_t k = sp->kmer_length;
-                std::unique_ptr<fh_kmer_count[]> recs(new fh_kmer_count[n + 1]);
-                std::unique_ptr<uint8_t[]> km(new uint8_t[n * (size_t)k + 1]);
-                if (r2 == FH_OK) r2 = fh_batch_copy_out_records(bt, slot, (uint32_t)j, recs.get(), km.get());
-                if (r2 != FH_OK) {
-                    record_error(i, r2, fh_last_error());
-                    continue;
-                }
-                const std::string name = filenames[i];
-                if (!group_scaled && !group_counts && !sp->no_strict && keep < sp->final_size) {
-                    char buf[512];
-                    snprintf(buf, sizeof buf, "%s had too few kmers (%zu) to sketch", name.c_str(), keep);
-                    record_error(i, FH_ERR_INVALID, buf);
-                    continue;
-                }
-                Sketch &out = res->v[i];
-                out.name = name;
-                out.seq_length = group_counts ? 0 : g.st[j].total_bases; // (AllCountsSketcher never counts its bases: counts.rs:9, 36-37)
-                out.num_valid_kmers = tk;
-                out.comment = "";
-                out.hashes.resize(keep);
-                for (size_t q = 0; q < keep; ++q)
-                    out.hashes[q] = KmerCount{recs[q].hash, KmerBytes((const char *)km.get() + q * (size_t)k, (size_t)k), recs[q].count, recs[q].extra_count};
-                out.filter_params = *filters;
-                out.filter_params.filter_on = 0; // lib.rs:70-76: FASTA defaults to no filtering (group_ok: not asked for either)
-                out.sketch_params = *sp;
-            }
-            g.idx.clear();
-            g.off.clear();
-            g.len.clear();
-            g.st.clear();
-            g.fill = 0;
-            if (trace) t_collect += now_s() - w1;
-        };
-        auto submit_cur = [&]() { // hand the current group to the device, go on in the other slot (its previous group collected)
-            Group &g = grp[cur];
-            if (g.idx.empty()) return;
-            const double s0 = trace ? now_s() : 0;
-            const int src = two_bit ? fh_batch_submit_packed(bt, cur, g.off.data(), g.len.data(), (uint32_t)g.idx.size())
-                                    : fh_batch_submit(bt, cur, g.off.data(), g.len.data(), (uint32_t)g.idx.size());
-            if (trace) t_submit += now_s() - s0;
-            if (src != FH_OK) {
-                for (uint32_t i : g.idx) through_sketcher(i);
-                g.idx.clear(), g.off.clear(), g.len.clear(), g.st.clear();
-                g.fill = 0;
-                return;
-            }
-            g.in_flight = true;
-            cur ^= 1;
-            collect(cur);
-        };
-        auto try_stage = [&](uint32_t i) -> bool { // true: file i is part of the current group
-            if (!group_ok || bt_failed) return false;
-            const char *fn = filenames[i];
-            if (strcmp(fn, "-") == 0) return false;
-            const int fd = open(fn, O_RDONLY | O_CLOEXEC);
-            if (fd < 0) return false; // (sketch_stream reports it)
-            struct stat sb;
-            if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size < 1 || (uint64_t)sb.st_size + 4096 > GROUP_STAGE) {
-                close(fd);
-                return false;
-            }
-            if (group_scaled && (uint64_t)(((unsigned __int128)(uint64_t)sb.st_size * group_max_hash) >> 64) > group_max_expect) {
-                close(fd);
-                return false;
-            }
-            const size_t size = (size_t)sb.st_size;
-            if (!bt) {
-                fh_params bp = to_fh(*sp, 0);
-                bp.size = group_n;
-                bt = group_counts ? fh_batch_new_counts(sp->kmer_length, handles.device, GROUP_FILES, GROUP_STAGE)
-                                  : group_large ? fh_batch_new_large(&bp, handles.device, GROUP_FILES, GROUP_STAGE)
-                                  : sp->kmer_length > 32 ? fh_batch_new_wide(&bp, handles.device, GROUP_FILES, GROUP_STAGE) // (two-word k-mers: fh_k2bw.hip)
-                                                         : fh_batch_new(&bp, handles.device, GROUP_FILES, GROUP_STAGE);
-                if (bt && (fh_batch_stage(bt, 0, &stage[0], &stage_cap) != FH_OK || fh_batch_stage(bt, 1, &stage[1], &stage_cap) != FH_OK)) {
-                    fh_batch_free(bt);
-                    bt = nullptr;
-                }
-                if (!bt) {
-                    bt_failed = true; // (no memory for it, say: every file the long way)
-                    close(fd);
-                    return false;
-                }
-                if (g_ktimes_on.load(std::memory_order_relaxed)) fh_batch_set_profiling(bt, 1);
-            }
-            const uint64_t room_needed = two_bit ? fh_pack2::region_bytes(size) + 64 : (uint64_t)size + 64;
-            if (grp[cur].idx.size() >= GROUP_FILES || grp[cur].fill + room_needed > stage_cap) submit_cur();
-            Group &g = grp[cur];
-            FastxStats st;
-            st.format = 1;
-            size_t m = 0;
-            uint64_t occupied;
-            const double r0 = trace ? now_s() : 0;
-            double r1 = r0;
-            if (two_bit) {
-                // piece by piece: read, strip, pack while the piece is in the core's cache
-                if (!packer) {
-                    packer.reset(new fh_pack2::Packer);
-                    packer->force_form((unsigned)cfg_u64("pack_scalar", 0));
-                }
-                if (raw.size() < READ_PIECE + 64) raw.resize(READ_PIECE + 64);
-                FastaTwoBit walk(*packer, st, stage[cur] + g.fill);
-                size_t got = 0;
-                bool bad = false;
-                while (got < size) {
-                    const double p0 = trace ? now_s() : 0;
-                    const ssize_t r = pread(fd, raw.data(), std::min<size_t>(READ_PIECE, size - got), (off_t)got);
-                    if (r <= 0 || (got == 0 && raw[0] != '>')) {
-                        bad = true;
-                        break;
-                    }
-                    const double p1 = trace ? now_s() : 0;
-                    walk.piece(raw.data(), (size_t)r);
-                    got += (size_t)r;
-                    if (trace) t_read += p1 - p0, t_pack += now_s() - p1;
-                }
-                // one byte more than fstat said = the file grew: not for this path (its region is abandoned: g.fill stays)
-                uint8_t extra;
-                const bool grew = !bad && pread(fd, &extra, 1, (off_t)size) > 0;
-                close(fd);
-                if (bad || grew) return false;
-                m = (size_t)walk.finish();
-                occupied = fh_pack2::region_bytes(m);
-                r1 = trace ? now_s() : 0;
-            } else {
-                if (raw.size() < size + 64) raw.resize(size + 64 + (size >> 2));
-                size_t got = 0;
-                while (got < size) {
-                    const ssize_t r = pread(fd, raw.data() + got, size - got, (off_t)got);
-                    if (r <= 0) break;
-                    got += (size_t)r;
-                }
-                uint8_t extra;
-                const bool grew = got == size && pread(fd, &extra, 1, (off_t)size) > 0;
-                close(fd);
-                if (got != size || grew || raw[0] != '>') return false;
-                r1 = trace ? now_s() : 0;
-                t_read += r1 - r0;
-                if (!pack_fasta_text(raw.data(), size, stage[cur] + g.fill, (size_t)(stage_cap - g.fill), st, m)) return false;
-                occupied = m;
-            }
-            g.idx.push_back(i);
-            g.off.push_back(g.fill);
-            g.len.push_back(m);
-            g.st.push_back(st);
-            g.fill = (g.fill + occupied + 63) & ~63ull;
-            if (trace) t_pack += now_s() - r1;
-            return true;
-        };
+        FileWorker fw(call, to_fh(*sp, batch ? ml : single_ml, batch ? (16ull << 20) : single_stage), devs[w % devs.size()], w);
         for (;;) {
             const uint32_t i = next.fetch_add(1);
             if (i >= n_files) break;
-            if (!try_stage(i)) through_sketcher(i);
+            if (!fw.try_stage(i)) fw.through_sketcher(i);
         }
-        if (bt) {
-            submit_cur();
-            collect(0);
-            collect(1);
-            if (g_ktimes_on.load(std::memory_order_relaxed)) {
-                double ms = 0;
-                uint64_t nl = 0, np = 0;
-                if (fh_batch_kernel_time(bt, &ms, &nl, &np) == FH_OK) {
-                    g_ktimes_us += (uint64_t)(ms * 1000.0 + 0.5);
-                    g_ktimes_launches += nl;
-                    g_ktimes_positions += np;
-                }
-            }
-            uint64_t tk = 0, nt = 0;
-            if (fh_batch_counters(bt, &tk, &nt) == FH_OK) g_batch_taken += tk, g_batch_not_taken += nt;
-            if (trace && w == 0)
-                fprintf(stderr, "[finch] worker 0 of a batch: %.1f ms in all: reading %.1f, packing %.1f, submits %.1f, waiting for the device %.1f, results %.1f ms (%llu files taken)\n",
-                        (now_s() - t_worker0) * 1e3, t_read * 1e3, t_pack * 1e3, t_submit * 1e3, t_wait * 1e3, t_collect * 1e3, (unsigned long long)tk);
-            fh_batch_free(bt);
-        }
+        fw.finish();
     };
     {
         std::vector<std::thread> th;
@@ -4289,7 +4325,7 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - call_t0).count());
         if (worker_threw) return hfail(FH_ERR_CAPACITY, "out of host memory");
     }
-    if (first_err_code != FH_OK) return hfail(first_err_code, "%s", first_err_msg.c_str());
+    if (call.first_err_code != FH_OK) return hfail(call.first_err_code, "%s", call.first_err_msg.c_str());
     *out = res.release();
     return FH_OK;
 } FINCH_CATCH
