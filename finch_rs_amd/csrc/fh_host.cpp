@@ -264,8 +264,7 @@ uint64_t scale_max_hash(double scale) {
 
 // distance.rs:66-126 (raw_distance) up to its divisions: c = common hashes, *i / *j = where the walk and the scale step left
 // the two cursors
-static void raw_counts(const uint64_t *q, size_t nq, const uint64_t *r, size_t nr, double scale, uint64_t &c, uint64_t &i_out,
-                       uint64_t &j_out) {
+void raw_counts(const uint64_t *q, size_t nq, const uint64_t *r, size_t nr, double scale, uint64_t &c, uint64_t &i_out, uint64_t &j_out) {
     size_t i = 0, j = 0;
     uint64_t common = 0;
     while (i < nq && j < nr) {
@@ -288,7 +287,7 @@ static void raw_counts(const uint64_t *q, size_t nq, const uint64_t *r, size_t n
 }
 
 // distance.rs:136-157 (old_distance) up to its divisions; the reference indexes query_sketch[0] unconditionally
-static int old_counts(const uint64_t *q, size_t nq, const uint64_t *r, size_t nr, uint64_t &common_out, uint64_t &total_out) {
+int old_counts(const uint64_t *q, size_t nq, const uint64_t *r, size_t nr, uint64_t &common_out, uint64_t &total_out) {
     if (nq == 0 && nr > 0) return hfail(FH_ERR_INVALID, "old_distance: empty query sketch");
     size_t i = 0;
     uint64_t common = 0, total = 0;

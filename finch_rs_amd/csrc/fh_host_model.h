@@ -123,6 +123,8 @@ int check_compatible(const std::vector<Sketch> &sketches);
 FINCH_LOCAL uint64_t scale_max_hash(double scale);
 FINCH_LOCAL void distance_from_counts(bool old_mode, uint64_t c, uint64_t i, uint64_t j, uint32_t kmer_length, bool with_mash, finch_distance_out *out);
 FINCH_LOCAL double pair_min_scale(const Sketch &qs, const Sketch &rs);
+FINCH_LOCAL void raw_counts(const uint64_t *q, size_t nq, const uint64_t *r, size_t nr, double scale, uint64_t &c, uint64_t &i_out, uint64_t &j_out);
+FINCH_LOCAL int old_counts(const uint64_t *q, size_t nq, const uint64_t *r, size_t nr, uint64_t &common_out, uint64_t &total_out);
 FINCH_LOCAL void json_escape(std::string &o, const std::string &s);
 FINCH_LOCAL std::string json_f64(double v);
 

@@ -32,6 +32,19 @@ int index_search_chunk(IndexDevice *d, const DistSide &queries, uint32_t q0, uin
 // again afterwards, as after a search.
 int index_dist_chunk(IndexDevice *d, const DistSide *queries, uint32_t q0, uint32_t q1, bool old_mode, const double *jmin,
                      std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms);
+// finch_index_cluster on one handle, between index_cluster_begin and index_cluster_end: a union-find of one
+// word per reference on the device, the identity at first, that lives for the one call and through all of its chunks.
+//   index_cluster_chunk: the library's own sketches q0 .. q1 as queries, counted and completed as index_dist_chunk's pairwise
+//   form does.  Per touched pair: jaccard >= jhi[q - q0] or jaccard == 1: q and r are united on the device (not where q == r)
+//   and nothing crosses; jaccard < jlo[q - q0]: dropped; else (q, r, c, i, j) is appended to *entries for the caller's exact
+//   test.  The counters are zero again afterwards; the dirty flag as for every chunk.
+//   index_cluster_end: labels[0 .. nr) = every reference's root, the smallest index of its tree; *united is added the ordered
+//   pairs q != r the device united, *kernel_ms the labels kernel's time; the call's device memory is freed whatever happens.
+//   labels == nullptr (the call failed elsewhere): only the freeing, FH_OK.
+int index_cluster_begin(IndexDevice *d);
+int index_cluster_chunk(IndexDevice *d, uint32_t q0, uint32_t q1, bool old_mode, const double *jlo, const double *jhi,
+                        std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms);
+int index_cluster_end(IndexDevice *d, uint32_t *labels, uint64_t *united, double *kernel_ms);
 // finch_index_gather's chunk: the queries [q0, q1) of `queries`, q1 - q0 <= chunk_queries, `counts` parallel to
 // queries.hashes.  Counted as above; *cands = the pairs with c >= min_overlap as (q, r, common), sorted by (q, r), q the caller's
 // index; then every round of every query in one launch over the live counters: *recs = one record per round, in no order, q the

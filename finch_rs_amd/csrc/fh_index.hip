@@ -15,6 +15,11 @@
 //   * k_index_dist_finish: finch_index_dist's finish after the same count: c, and 0 back; (i, j) as above, or
 //     old mode's total = |R|; the pair is appended where its jaccard reaches the host's conservative bound for the query.  The
 //     queries may be the library's own sketches (pairwise), read from the CSR the index holds.
+// finch_index_cluster turns the same pairwise finish into single-linkage clusters:
+//   * k_index_cluster_finish: k_index_dist_finish's sibling with a bound on either side: a pair above the upper one is united on
+//     the device in a lock-free union-find of one word per reference, a pair below the lower one is dropped, and only the band
+//     between crosses to the host's exact test;
+//   * k_index_cluster_labels: after an entry's last chunk, every reference's root.
 // finch_index_gather keeps the counters of the same count live through the rounds of finch_gather's loop:
 //   * k_index_gather_candidates: per touched pair c is read and LEFT; (q, r, c) is appended where c >= min_overlap;
 //   * k_index_gather_rounds: one workgroup of 1024 per query, the whole loop inside.  cnt[r] == |S_t n H_r| for every touched r:
@@ -414,6 +419,119 @@ __global__ void __launch_bounds__(THREADS) k_index_dist_finish(IndexArgs a, cons
     }
 }
 
+// ---- finch_index_cluster -----------------------------------------------------------------------------------------------
+// A lock-free union-find over the references, one word each.  What holds at every moment, whatever the lanes'
+// order:
+//   (1) parent[v] <= v;
+//   (2) a word that has stopped being a root (parent[v] < v) never becomes one again, and only ever moves to a smaller member
+//       of its own tree -- an ancestor it had;
+//   (3) a root (parent[v] == v) is only ever changed by the one atomicCAS(&parent[v], v, lo) of cluster_unite, lo < v a root
+//       of another tree when it was read.
+// So trees only merge, a walk up the parents descends and ends by itself, no lane waits for another, and the root of a tree is
+// its smallest member: when every union has run, the root of a component is its smallest index whatever the order was.  Every
+// value a read can return -- a stale one included -- is one the word has held, and (1)-(3) make each of those as good as the
+// newest for a walk: what a stale read costs is a CAS that fails.  The word is the data: no payload, no fence.
+
+// every read of parent inside the finish: relaxed, agent scope -- not a value kept in a register, not a line of this CU's L1
+__device__ inline uint32_t cluster_parent(const uint32_t *parent, uint32_t v) {
+    return __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// v's root as far as this lane can see, halving the path on the way: parent[v] to the grandparent by atomicMin, which keeps (2)
+// against a lane that has moved it further meanwhile.  Every index read is below v: inside parent[0 .. nr).
+__device__ inline uint32_t cluster_root(uint32_t *parent, uint32_t v) {
+    for (;;) {
+        const uint32_t p = cluster_parent(parent, v);
+        if (p >= v) return v;
+        const uint32_t g = cluster_parent(parent, p);
+        if (g < p) atomicMin(&parent[v], g);
+        v = p;
+    }
+}
+
+// the larger root under the smaller by one CAS; a CAS that fails returns the word's value -- the root has a parent now --, and
+// the loop goes round from there: the larger of the two indices falls with every round, so it ends.
+__device__ inline void cluster_unite(uint32_t *parent, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = cluster_root(parent, a), b = cluster_root(parent, b);
+        if (a == b) return;
+        const uint32_t hi = max(a, b), lo = min(a, b);
+        const uint32_t seen = atomicCAS(&parent[hi], hi, lo);
+        if (seen == hi) return;
+        a = seen, b = lo;
+    }
+}
+
+// grid: x = query of the chunk (pairwise: the library's own sketch q0 + x).  finch_index_cluster's finish, k_index_dist_finish's
+// sibling: per touched pair c, and 0 back, (i, j) and the jaccard as there.  Then three bands: jaccard >= jhi[q], or jaccard 1
+// -- distance exactly 0 at every k --: sure, q and r are united here and nothing crosses; jaccard < jlo[q]: dropped; between:
+// (q, r, c, i, j) is appended as k_index_dist_finish appends it, for the host's exact test.  A self pair is neither united nor
+// counted.  *united: the sure pairs with q != r, added once per wave as the cursor is.
+__global__ void __launch_bounds__(THREADS) k_index_cluster_finish(IndexArgs a, const double *jlo, const double *jhi, uint32_t old_mode,
+                                                                  uint32_t *parent, unsigned long long *united) {
+    const uint32_t qi = blockIdx.x, n = a.tcount[qi];
+    const uint32_t nqh = (uint32_t)(a.qoff[qi + 1] - a.qoff[qi]);
+    const uint64_t *Q = a.qh + (a.qoff[qi] - a.qbase);
+    const uint32_t qtop = top_of(nqh);
+    const uint64_t max_q = nqh ? Q[nqh - 1] : 0;
+    const double jl = jlo[qi], jh = jhi[qi];
+    const uint32_t q = a.q0 + qi;
+    uint32_t *cnt = a.cnt + (uint64_t)qi * a.nr;
+    const uint32_t *touched = a.touched + (uint64_t)qi * a.nr;
+    for (uint32_t base = 0; base < n; base += THREADS) { // (whole waves go round: the ballots see every lane)
+        const uint32_t t = base + threadIdx.x;
+        uint32_t r = 0, c = 0, i = 0, j = 0;
+        bool sure = false, band = false;
+        if (t < n) {
+            r = touched[t];
+            c = cnt[r];
+            cnt[r] = 0;
+            const uint32_t nrh = a.rlen[r];
+            if (old_mode) {
+                i = nrh;
+            } else if (nqh && nrh) {
+                const uint64_t *R = a.rh + a.roff[r];
+                const uint32_t rtop = top_of(nrh);
+                i = count_below<true>(Q, nqh, qtop, a.rlast[r]);
+                j = count_below<true>(R, nrh, rtop, max_q);
+                uint64_t m = 0;
+                if (pair_max_hash(a, qi, r, m)) {
+                    i = max(i, count_below<false>(Q, nqh, qtop, m));
+                    j = max(j, count_below<false>(R, nrh, rtop, m));
+                }
+            }
+            const double jac = jaccard_of(old_mode != 0, c, i, j);
+            sure = jac >= jh || jac == 1.0;
+            band = !sure && jac >= jl;
+        }
+        const bool mine = sure && q != r && q < a.nr; // (q < nr: pairwise; r < nr: k_index_count)
+        if (mine) cluster_unite(parent, q, r);
+        const uint64_t done = __ballot(mine);
+        if (done && (threadIdx.x & 63) == (uint32_t)(__ffsll((unsigned long long)done) - 1))
+            atomicAdd(united, (unsigned long long)__popcll(done));
+        const uint64_t mask = __ballot(band);
+        if (!mask) continue;
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        uint32_t first = 0;
+        if (band && rank == 0) first = atomicAdd(a.cursor, (uint32_t)__popcll(mask));
+        first = __shfl(first, __ffsll((unsigned long long)mask) - 1, 64);
+        if (band && first + rank < a.sel_cap) { // (the host sized the list to the chunk's touched pairs)
+            uint32_t *e = a.sel + (uint64_t)(first + rank) * 5;
+            e[0] = q, e[1] = r, e[2] = c, e[3] = i, e[4] = j;
+        }
+    }
+}
+
+// grid: x = block of references.  After an entry's last chunk: labels[v] = v's root, a walk that reads only -- the kernel
+// boundary has made every finish kernel's atomics visible --, into an array of its own: 4 bytes per reference cross.
+__global__ void __launch_bounds__(THREADS) k_index_cluster_labels(const uint32_t *parent, uint32_t nr, uint32_t *labels) {
+    for (uint64_t v = (uint64_t)blockIdx.x * THREADS + threadIdx.x; v < nr; v += (uint64_t)gridDim.x * THREADS) {
+        uint32_t x = (uint32_t)v, p;
+        while ((p = parent[x]) < x) x = p; // ((1): every index read is below v)
+        labels[v] = x;
+    }
+}
+
 // ---- finch_index_gather ------------------------------------------------------------------------------------------------
 
 constexpr uint32_t ROUND_THREADS = 1024, ROUND_WAVES = ROUND_THREADS / 64;
@@ -657,6 +775,11 @@ struct IndexDevice {
     uint64_t sel_cap = 0;         // entries that sel holds
     uint32_t *back_h = nullptr;   // pinned: chunk touched-list lengths, then the cursor
     double *jmin = nullptr;       // finch_index_dist: the chunk's jaccard bounds, one per query (allocated by its first chunk)
+    // finch_index_cluster, from index_cluster_begin to index_cluster_end: the chunk's upper bounds, the union-find's nr words and
+    // the labels' nr, the count of united pairs
+    double *jhi = nullptr;
+    uint32_t *parent = nullptr, *labels = nullptr;
+    unsigned long long *united = nullptr;
     // finch_index_gather, grown as needed: the chunk's counts, its list of (q, r, common), the candidates (r, common) by (q, r),
     // each query's range of them, the records; two words -- the records' cursor, the error word -- and their pinned copy
     void *gat[5] = {};
@@ -686,6 +809,15 @@ static void stage_drop(IndexStage *s) {
     *s = IndexStage();
 }
 
+// frees what a cluster call holds; the device is current
+static void cluster_drop(IndexDevice *d) {
+    if (d->jhi) (void)hipFree(d->jhi);
+    if (d->parent) (void)hipFree(d->parent);
+    if (d->labels) (void)hipFree(d->labels);
+    if (d->united) (void)hipFree(d->united);
+    d->jhi = nullptr, d->parent = d->labels = nullptr, d->united = nullptr;
+}
+
 void index_close(IndexDevice *d) {
     if (!d) return;
     if (hipSetDevice(d->device) == hipSuccess) {
@@ -698,6 +830,7 @@ void index_close(IndexDevice *d) {
         for (uint32_t *p : {d->cnt, d->touched, d->tcount, d->cursor, d->sel})
             if (p) (void)hipFree(p);
         if (d->jmin) (void)hipFree(d->jmin);
+        cluster_drop(d);
         for (void *p : d->gat)
             if (p) (void)hipFree(p);
         if (d->gwords) (void)hipFree(d->gwords);
@@ -854,9 +987,10 @@ static int chunk_args(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q
 }
 
 // one chunk of either route.  q = nullptr: the queries are the library's own sketches q0 .. q1 (pairwise), read where the index
-// keeps them.  jmin = nullptr: the search's finish with min_containment; else finch_index_dist's with the chunk's bounds.
-static int run_chunk(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q1, double min_containment, const double *jmin, bool old_mode,
-                     std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms) {
+// keeps them.  jmin = nullptr: the search's finish with min_containment; else finch_index_dist's with the chunk's bounds, or --
+// jhi too -- finch_index_cluster's with both, over the call's union-find (index_cluster_begin).
+static int run_chunk(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q1, double min_containment, const double *jmin, const double *jhi,
+                     bool old_mode, std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms) {
     const uint32_t n = q1 - q0;
     IHIP_TRY(hipSetDevice(d->device));
     IndexArgs a;
@@ -866,6 +1000,7 @@ static int run_chunk(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q1
         if (!d->jmin) IHIP_TRY(api_dev_malloc((void **)&d->jmin, (size_t)d->chunk * sizeof(double)));
         IHIP_TRY(hipMemcpy(d->jmin, jmin, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
     }
+    if (jhi) IHIP_TRY(hipMemcpy(d->jhi, jhi, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
 
     // the count; the touched lists' lengths cross, so that the chunk's list can be sized to what may pass
     d->dirty = true; // until the finish has stored the zeros back
@@ -898,7 +1033,10 @@ static int run_chunk(IndexDevice *d, const DistSide *q, uint32_t q0, uint32_t q1
 
     IHIP_TRY(hipMemsetAsync(d->cursor, 0, sizeof(uint32_t), d->stream));
     IHIP_TRY(hipEventRecord(d->ev[2], d->stream));
-    if (jmin) hipLaunchKernelGGL(k_index_dist_finish, dim3(n), dim3(THREADS), 0, d->stream, a, (const double *)d->jmin, old_mode ? 1u : 0u);
+    if (jhi)
+        hipLaunchKernelGGL(k_index_cluster_finish, dim3(n), dim3(THREADS), 0, d->stream, a, (const double *)d->jmin, (const double *)d->jhi,
+                           old_mode ? 1u : 0u, d->parent, d->united);
+    else if (jmin) hipLaunchKernelGGL(k_index_dist_finish, dim3(n), dim3(THREADS), 0, d->stream, a, (const double *)d->jmin, old_mode ? 1u : 0u);
     else hipLaunchKernelGGL(k_index_finish, dim3(n), dim3(THREADS), 0, d->stream, a);
     IHIP_TRY(hipGetLastError());
     IHIP_TRY(hipEventRecord(d->ev[3], d->stream));
@@ -920,7 +1058,7 @@ int index_search_chunk(IndexDevice *d, const DistSide &queries, uint32_t q0, uin
     if (q1 <= q0 || q1 > queries.n || q1 - q0 > d->chunk)
         return api_fail(FH_ERR_INVALID, "index_search_chunk: queries %u..%u of %u, %u per launch", q0, q1, queries.n, d->chunk);
     if (d->dirty) return api_fail(FH_ERR_STATE, "index search: an earlier search on this index failed between its two kernels; build the index again");
-    return run_chunk(d, &queries, q0, q1, min_containment, nullptr, false, entries, touched, kernel_ms);
+    return run_chunk(d, &queries, q0, q1, min_containment, nullptr, nullptr, false, entries, touched, kernel_ms);
 }
 
 int index_dist_chunk(IndexDevice *d, const DistSide *queries, uint32_t q0, uint32_t q1, bool old_mode, const double *jmin,
@@ -928,7 +1066,56 @@ int index_dist_chunk(IndexDevice *d, const DistSide *queries, uint32_t q0, uint3
     if (!jmin || q1 <= q0 || q1 > (queries ? queries->n : d->nr) || q1 - q0 > d->chunk)
         return api_fail(FH_ERR_INVALID, "index_dist_chunk: queries %u..%u of %u, %u per launch", q0, q1, queries ? queries->n : d->nr, d->chunk);
     if (d->dirty) return api_fail(FH_ERR_STATE, "index dist: an earlier call on this index failed between its two kernels; build the index again");
-    return run_chunk(d, queries, q0, q1, 0., jmin, old_mode, entries, touched, kernel_ms);
+    return run_chunk(d, queries, q0, q1, 0., jmin, nullptr, old_mode, entries, touched, kernel_ms);
+}
+
+int index_cluster_begin(IndexDevice *d) {
+    if (d->dirty) return api_fail(FH_ERR_STATE, "index cluster: an earlier call on this index failed between its two kernels; build the index again");
+    IHIP_TRY(hipSetDevice(d->device));
+    cluster_drop(d); // (what a failed call may have left)
+    IHIP_TRY(api_dev_malloc((void **)&d->jhi, (size_t)d->chunk * sizeof(double)));
+    IHIP_TRY(api_dev_malloc((void **)&d->parent, (size_t)d->nr * sizeof(uint32_t)));
+    IHIP_TRY(api_dev_malloc((void **)&d->labels, (size_t)d->nr * sizeof(uint32_t)));
+    IHIP_TRY(api_dev_malloc((void **)&d->united, sizeof(unsigned long long)));
+    std::vector<uint32_t> identity(d->nr);
+    for (uint32_t v = 0; v < d->nr; ++v) identity[v] = v;
+    IHIP_TRY(hipMemcpy(d->parent, identity.data(), (size_t)d->nr * sizeof(uint32_t), hipMemcpyHostToDevice));
+    IHIP_TRY(hipMemsetAsync(d->united, 0, sizeof(unsigned long long), d->stream)); // (in front of the first chunk's kernels)
+    return FH_OK;
+}
+
+int index_cluster_chunk(IndexDevice *d, uint32_t q0, uint32_t q1, bool old_mode, const double *jlo, const double *jhi,
+                        std::vector<uint32_t> *entries, uint64_t *touched, double *kernel_ms) {
+    if (!jlo || !jhi || !d->parent || q1 <= q0 || q1 > d->nr || q1 - q0 > d->chunk)
+        return api_fail(FH_ERR_INVALID, "index_cluster_chunk: queries %u..%u of %u, %u per launch", q0, q1, d->nr, d->chunk);
+    if (d->dirty) return api_fail(FH_ERR_STATE, "index cluster: an earlier call on this index failed between its two kernels; build the index again");
+    return run_chunk(d, nullptr, q0, q1, 0., jlo, jhi, old_mode, entries, touched, kernel_ms);
+}
+
+int index_cluster_end(IndexDevice *d, uint32_t *labels, uint64_t *united, double *kernel_ms) {
+    if (hipSetDevice(d->device) != hipSuccess || !d->parent || !labels) { // (a call that failed: only the freeing)
+        cluster_drop(d);
+        (void)hipGetLastError();
+        return labels ? api_fail(FH_ERR_STATE, "index_cluster_end: no cluster call is open on this index") : FH_OK;
+    }
+    struct Drop {
+        IndexDevice *d;
+        ~Drop() { cluster_drop(d); }
+    } drop{d};
+    IHIP_TRY(hipEventRecord(d->ev[0], d->stream));
+    hipLaunchKernelGGL(k_index_cluster_labels, dim3(std::min((d->nr + THREADS - 1) / THREADS, 4096u)), dim3(THREADS), 0, d->stream,
+                       (const uint32_t *)d->parent, d->nr, d->labels);
+    IHIP_TRY(hipGetLastError());
+    IHIP_TRY(hipEventRecord(d->ev[1], d->stream));
+    IHIP_TRY(hipStreamSynchronize(d->stream));
+    float ms = 0.f;
+    IHIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
+    *kernel_ms += ms;
+    unsigned long long n = 0;
+    IHIP_TRY(hipMemcpy(labels, d->labels, (size_t)d->nr * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    IHIP_TRY(hipMemcpy(&n, d->united, sizeof n, hipMemcpyDeviceToHost));
+    *united += n;
+    return FH_OK;
 }
 
 // finch_index_gather's chunk: the count as above, the candidates, then every round of every query in one launch.

@@ -1,5 +1,5 @@
 // fh_library.cpp -- the library calls of the C ABI (include/finch_host.h): dist, minmer_matrix, search, the index and its
-// search / dist / gather / compare_counts / add / keep, gather, compare_counts, merge.  Many sketches against many, on one or several device
+// search / dist / cluster / gather / compare_counts / add / keep, gather, compare_counts, merge.  Many sketches against many, on one or several device
 // entries; each call checks its arguments, deals its work over the entries (fh_entries.h) and finishes the device's integers on
 // the host.
 // Reading, parsing and the single-sketch calls are fh_host.cpp's.
@@ -22,6 +22,7 @@
 #include "fh_options.h"
 #include "fh_dist.h"
 #include "fh_index.h"
+#include "fh_cluster.h"
 #include "fh_matrix.h"
 #include "fh_moments.h"
 #include "fh_merge_lib.h"
@@ -982,6 +983,203 @@ int finch_index_dist_stats(const finch_dist_result *r, uint64_t *pairs_touched, 
     if (!r->from_index) return hfail(FH_ERR_INVALID, "finch_index_dist_stats: the result was not made by finch_index_dist");
     if (pairs_touched) *pairs_touched = r->touched;
     if (pairs_copied) *pairs_copied = r->copied;
+    return FH_OK;
+} FINCH_CATCH
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// single-linkage clusters of a library (the contract is finch_host.h's comment; not in the reference): a and b are linked when
+// (a, b) or (b, a) is a row finch_dist(refs, refs) would keep within max_distance, the name-based self-skip aside;
+// labels[v] = the smallest index of v's component.  finch_cluster_host is that sentence on the host, every ordered pair;
+// finch_index_cluster goes through the index: the device unites what is surely within the bound in a union-find of its own,
+// drops what is surely not, and only the band between crosses to distance_from_counts here.  DESIGN.md §3.20.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// what both calls decide before anything else: -> FH_OK with *trivial set where labels are the identity already
+int cluster_check(const char *who, const std::vector<Sketch> &Rs, int old_mode, double max_distance, uint32_t *labels, uint64_t n_labels,
+                  uint64_t postings, bool *trivial) {
+    if (n_labels != Rs.size())
+        return hfail(FH_ERR_INVALID, "%s: n_labels %llu, the library has %zu sketches", who, (unsigned long long)n_labels, Rs.size());
+    if (n_labels && !labels) return hfail(FH_ERR_INVALID, "null argument");
+    if (int rc = check_ascending(Rs, "reference")) return rc;
+    if (old_mode) { // pairwise makes every sketch a query: old_distance refuses an empty query against a non-empty reference
+        bool empty_q = false;
+        for (const Sketch &s : Rs) empty_q = empty_q || s.hashes.empty();
+        if (empty_q && postings) return hfail(FH_ERR_INVALID, "old_distance: empty query sketch");
+    }
+    for (uint64_t v = 0; v < n_labels; ++v) labels[v] = (uint32_t)v;
+    *trivial = Rs.empty() || !(max_distance >= 0.); // (a NaN or negative bound links nothing: every distance is in [0, 1])
+    return FH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int finch_cluster_host(const finch_sketches *refs, int old_mode, double max_distance, uint32_t *labels, uint64_t n_labels,
+                       uint64_t *edges) try {
+    if (!refs) return hfail(FH_ERR_INVALID, "null argument");
+    const std::vector<Sketch> &Rs = refs->v;
+    uint64_t postings = 0;
+    for (const Sketch &s : Rs) postings += s.hashes.size();
+    bool trivial = false;
+    if (int rc = cluster_check("finch_cluster_host", Rs, old_mode, max_distance, labels, n_labels, postings, &trivial)) return rc;
+    if (edges) *edges = 0;
+    if (trivial) return FH_OK;
+    const uint32_t nr = (uint32_t)Rs.size();
+    std::vector<std::vector<uint64_t>> H(nr);
+    for (uint32_t s = 0; s < nr; ++s) {
+        H[s].reserve(Rs[s].hashes.size());
+        for (const KmerCount &h : Rs[s].hashes) H[s].push_back(h.hash);
+    }
+    fh::cluster::UnionFind uf(nr);
+    uint64_t n_edges = 0;
+    for (uint32_t r = 0; r < nr; ++r)
+        for (uint32_t q = 0; q < nr; ++q) {
+            if (q == r) continue;
+            uint64_t c = 0, i = 0, j = 0;
+            if (old_mode) {
+                if (int rc = old_counts(H[q].data(), H[q].size(), H[r].data(), H[r].size(), c, i)) return rc;
+            } else {
+                raw_counts(H[q].data(), H[q].size(), H[r].data(), H[r].size(), pair_min_scale(Rs[q], Rs[r]), c, i, j);
+            }
+            finch_distance_out d;
+            distance_from_counts(old_mode != 0, c, i, j, Rs[q].sketch_params.kmer_length, true, &d);
+            if (!(d.mash_distance <= max_distance)) continue;
+            ++n_edges;
+            uf.unite(q, r);
+        }
+    uf.labels(labels);
+    if (edges) *edges = n_edges;
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_index_cluster(const finch_index *cix, const finch_sketches *refs, int old_mode, double max_distance, uint32_t *labels,
+                        uint64_t n_labels, finch_cluster_stats *stats) try {
+    if (!cix || !refs) return hfail(FH_ERR_INVALID, "null argument");
+    finch_index *ix = const_cast<finch_index *>(cix); // (the launch state is the index's; `mu` serialises its use)
+    std::lock_guard<std::mutex> one_call(ix->mu);     // (from here: finch_index_add / finch_index_keep change what is read below)
+    if (max_distance >= 1.)
+        return hfail(FH_ERR_INVALID, "finch_index_cluster: max_distance %g: an index finds only the pairs that share a hash, and every "
+                                     "pair is within a bound >= 1 -- the library is one cluster", max_distance);
+    double margin = 0.;
+    if (!fh::cluster::margin_parse(fh::cfg("index_cluster_margin"), &margin))
+        return hfail(FH_ERR_INVALID, "finch_index_cluster: option index_cluster_margin = %s: a number in [2^-20, 0.5] (nothing sweeps the "
+                                     "bands' soundness below 2^-20)", fh::cfg("index_cluster_margin"));
+    const std::vector<Sketch> &Rs = refs->v;
+    uint64_t postings = 0;
+    for (const Sketch &s : Rs) postings += s.hashes.size();
+    if (Rs.size() != ix->nr || postings != ix->postings)
+        return hfail(FH_ERR_INVALID, "finch_index_cluster: refs has %zu sketches and %llu hashes, the index was built from %u and %llu: "
+                                     "refs must be the library of the index", Rs.size(), (unsigned long long)postings, ix->nr,
+                     (unsigned long long)ix->postings);
+    bool trivial = false;
+    if (int rc = cluster_check("finch_index_cluster", Rs, old_mode, max_distance, labels, n_labels, postings, &trivial)) return rc;
+    finch_cluster_stats st{};
+    st.clusters = n_labels;
+    if (trivial) {
+        if (stats) *stats = st;
+        return FH_OK;
+    }
+    const uint32_t nr = (uint32_t)Rs.size();
+    fh::cluster::UnionFind uf(nr);
+    fh::cluster::Edges count;
+    // the exact test of an ordered pair q != r from its counts: finch_dist's function and comparison
+    auto passes = [&](uint32_t q, uint32_t r, uint64_t c, uint64_t i, uint64_t j) {
+        finch_distance_out d;
+        distance_from_counts(old_mode != 0, c, old_mode ? Rs[r].hashes.size() : i, j, Rs[q].sketch_params.kmer_length, true, &d);
+        return d.mash_distance <= max_distance;
+    };
+
+    // the pairs with an empty side, host-made as finch_index_dist makes them
+    for (uint32_t r = 0; r < nr; ++r)
+        if (Rs[r].hashes.empty())
+            for (uint32_t q = 0; q < nr; ++q) {
+                if (q == r) continue;
+                uint64_t i = 0, j = 0;
+                if (!old_mode) empty_side_counts(Rs[q], Rs[r], i, j);
+                if (passes(q, r, 0, i, j)) ++count.empty_side, uf.unite(q, r);
+            }
+    if (!old_mode)
+        for (uint32_t q = 0; q < nr; ++q)
+            if (Rs[q].hashes.empty())
+                for (uint32_t r = 0; r < nr; ++r)
+                    if (!Rs[r].hashes.empty()) {
+                        uint64_t i = 0, j = 0;
+                        empty_side_counts(Rs[q], Rs[r], i, j);
+                        if (passes(q, r, 0, i, j)) ++count.empty_side, uf.unite(q, r);
+                    }
+
+    if (!ix->entries.empty()) { // (a library without a hash: every edge is made above)
+        DeviceGuard restore_device;
+
+        std::vector<double> jlo(nr), jhi(nr);
+        for (uint32_t q = 0; q < nr; ++q) {
+            jlo[q] = index_dist_jmin(Rs[q].sketch_params.kmer_length, max_distance); // (== fh::cluster::jlo)
+            jhi[q] = fh::cluster::jhi(Rs[q].sketch_params.kmer_length, max_distance, margin);
+        }
+        const uint32_t n_chunks = (nr + ix->chunk - 1) / ix->chunk;
+        const uint32_t n_entries = (uint32_t)std::min<size_t>(ix->entries.size(), n_chunks);
+        fh::EntryError err;
+        std::mutex stat_mu;
+        struct Pair {
+            uint32_t a, b;
+        };
+
+        // one thread per device entry: chunks of queries e, e + n_entries, ...; the entry's union-find lives through them
+        fh::for_entries(n_entries, err, FH_ERR_CAPACITY, [&](unsigned e) {
+            fh::IndexDevice *d = ix->entries[e];
+            std::vector<uint32_t> ent, lab;
+            std::vector<Pair> kept;
+            double ms_sum = 0.;
+            uint64_t touched = 0, copied = 0, kept_host = 0, launches = 0, united = 0;
+            bool ok = !entry_failed(err, fh::index_cluster_begin(d));
+            for (uint32_t k = e; ok && k < n_chunks && !err.failed(); k += n_entries) {
+                const uint32_t q0 = k * ix->chunk, q1 = (uint32_t)std::min<uint64_t>(nr, (uint64_t)q0 + ix->chunk);
+                ent.clear();
+                if (entry_failed(err, fh::index_cluster_chunk(d, q0, q1, old_mode != 0, jlo.data() + q0, jhi.data() + q0, &ent, &touched, &ms_sum))) {
+                    ok = false;
+                    break;
+                }
+                ++launches;
+                copied += ent.size() / 5;
+                for (size_t t = 0; t + 5 <= ent.size(); t += 5) {
+                    const uint32_t *x = ent.data() + t;
+                    if (x[0] < q0 || x[0] >= q1 || x[1] >= nr) {
+                        err.fail(FH_ERR_STATE, "index cluster: an entry names pair (" + std::to_string(x[0]) + ", " + std::to_string(x[1]) + ")");
+                        ok = false;
+                        break;
+                    }
+                    if (x[0] != x[1] && passes(x[0], x[1], x[2], x[3], x[4])) ++kept_host, kept.push_back(Pair{x[0], x[1]});
+                }
+            }
+            ok = ok && !err.failed();
+            if (ok) lab.resize(nr);
+            if (entry_failed(err, fh::index_cluster_end(d, ok ? lab.data() : nullptr, &united, &ms_sum))) ok = false;
+            std::lock_guard<std::mutex> g(stat_mu);
+            st.kernel_ms += ms_sum;
+            st.launches += launches;
+            st.pairs_touched += touched;
+            count.copied += copied;
+            count.kept_host += kept_host;
+            count.united += united;
+            if (!ok) return;
+            for (uint32_t v = 0; v < nr; ++v) {
+                if (lab[v] > v) {
+                    err.fail(FH_ERR_STATE, "index cluster: reference " + std::to_string(v) + " has label " + std::to_string(lab[v]));
+                    return;
+                }
+                uf.unite(v, lab[v]);
+            }
+            for (const Pair &p : kept) uf.unite(p.a, p.b);
+        });
+        if (err.failed()) return hfail(err.rc(), "%s", err.msg().c_str());
+    }
+    st.clusters = uf.labels(labels);
+    st.pairs_united = count.united, st.pairs_copied = count.copied, st.pairs_kept_host = count.kept_host, st.edges = count.edges();
+    if (stats) *stats = st;
     return FH_OK;
 } FINCH_CATCH
 

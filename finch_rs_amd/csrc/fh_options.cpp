@@ -96,6 +96,8 @@ const OptDef DEFS[] = {
     {"index_chunk_queries", "queries per launch of an index search, read when the index is built (default: counters plus touched lists within 256 MiB, at most 4096; tests: 1 = many launches)"},
     {"index_max_postings", "postings (hashes of all its sketches) of a library that finch_index_new accepts, at most 2^32 - 2048 (the default; tests: the refusal)"},
     {"index_update_tile", "output postings per tile of an index update (finch_index_add, finch_index_keep), 1..2048 (default 2048, the sort's tile; small values are for tests on small libraries only: a keep holds 4 bytes per tile beside old + new and scans the tiles in one workgroup)"},
+    // --- finch_index_cluster ---
+    {"index_cluster_margin", "m of finch_index_cluster's upper jaccard bound x / (2 - x) * (1 + m), above which the device unites a pair without the host's exact test: a number in [2^-20, 0.5] (default 2^-20; anything else is refused; tests: 0.25 = most pairs cross to the host)"},
     // --- finch_gather ---
     {"gather_slice", "query hashes per LDS slice of the gather's positions kernel, 1..4096 (default 4096; tests: many slices per query)"},
     {"gather_pos_bytes", "bytes of position arrays per chunk of queries of a gather (default 1 GiB; tests: one query per chunk, a query that does not fit)"},

@@ -149,6 +149,15 @@ _SYMS["finch_index_search_stats"] = (C.c_int, [_P, C.POINTER(C.c_uint64)])
 _SYMS["finch_index_free"] = (None, [_P])
 _SYMS["finch_index_dist"] = (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.POINTER(_P)])
 _SYMS["finch_index_dist_stats"] = (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+
+
+class CClusterStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double)] + [(f, C.c_uint64) for f in ("launches", "pairs_touched", "pairs_united", "pairs_copied",
+                                                                       "pairs_kept_host", "edges", "clusters")]
+
+
+_SYMS["finch_index_cluster"] = (C.c_int, [_P, _P, C.c_int, C.c_double, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(CClusterStats)])
+_SYMS["finch_cluster_host"] = (C.c_int, [_P, C.c_int, C.c_double, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)])
 _SYMS["finch_gather_query"] = (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)])
 _SYMS["finch_gather"] = (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P)])
 _SYMS["finch_gather_len"] = (C.c_uint64, [_P])
@@ -776,6 +785,28 @@ class LibraryIndex:
         """dist_json(queries, refs, max_distance, old_mode)'s text for a bound below 1"""
         return _dist_text(self._dist_result(queries, max_distance, old_mode))
 
+    def cluster(self, max_distance: float = 0.1, old_mode: bool = False, stats: Optional[dict] = None) -> np.ndarray:
+        """single-linkage clusters of the library at `max_distance` (finch_index_cluster): a uint32 array over self.refs,
+        labels[v] = the smallest index of v's component, where a and b are linked when dist(refs, refs, max_distance, old_mode)
+        has the row (a, b) or (b, a) -- cluster_host()'s answer for a bound below 1 (FinchError for one >= 1).  The device unites
+        the pairs that are surely within the bound and only a narrow band crosses to the host's exact test.  `stats` receives
+        finch_cluster_stats' fields"""
+        labels = np.empty(len(self.refs), np.uint32)
+        st = CClusterStats()
+        _check(lib().finch_index_cluster(self._handle(), self.refs._p, int(old_mode), float(max_distance),
+                                         labels.ctypes.data_as(C.POINTER(C.c_uint32)), len(labels), C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in CClusterStats._fields_})
+        return labels
+
+    def dereplicate(self, max_distance: float = 0.1, old_mode: bool = False) -> np.ndarray:
+        """cluster(), then keep(np.unique(labels)): self.refs is afterwards one sketch per cluster, its lowest-indexed member, in
+        library order -> the labels as they were before the keep.  Single linkage: a cluster's members are chained to its
+        survivor, not each within the bound of it"""
+        labels = self.cluster(max_distance, old_mode)
+        self.keep(np.unique(labels))
+        return labels
+
     def gather(self, queries: Sketches, min_overlap: int = 1, max_rounds: int = 0, stats: Optional[dict] = None):
         """gather(queries, refs, min_overlap, max_rounds)'s (offsets, rows), byte for byte, the rounds over the index's live
         counters (finch_index_gather); `stats` receives gather()'s figures and pairs_touched, the pairs the device counted"""
@@ -869,6 +900,18 @@ class LibraryIndex:
 GATHER_DTYPE = np.dtype([(f, np.uint64) for f in ("query", "reference", "round", "overlap", "common", "ref_len", "query_len", "abund",
                                                    "remaining")] +
                         [(f, np.float64) for f in ("f_unique_to_query", "f_orig_query", "f_match", "average_abund", "f_unique_weighted")])
+
+
+def cluster_host(sketches: Sketches, max_distance: float, old_mode: bool = False, edges: Optional[list] = None) -> np.ndarray:
+    """finch_cluster_host: the clustering contract on the host, every ordered pair -> labels (uint32, labels[v] = the smallest
+    index of v's component); `edges`, a list, is appended the number of ordered pairs q != r within the bound"""
+    labels = np.empty(len(sketches), np.uint32)
+    n = C.c_uint64()
+    _check(lib().finch_cluster_host(sketches._p, int(old_mode), float(max_distance), labels.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                    len(labels), C.byref(n)))
+    if edges is not None:
+        edges.append(n.value)
+    return labels
 
 
 def gather_query(refs: Sketches, queries: Sketches, iq: int, min_overlap: int = 1, max_rounds: int = 0) -> np.ndarray:

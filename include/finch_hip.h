@@ -97,8 +97,10 @@ const char *fh_last_error(void);
  * 18: fh_batch_new_wide and the rest of 17 unchanged, plus finch_index_attach_counts, finch_index_compare_counts and
  * finch_index_compare_counts_stats in finch_host.h;
  * 19: fh_batch_new_wide and the rest of 18 unchanged, plus finch_index_add and finch_index_keep in finch_host.h and the option
- * index_update_tile) */
-#define FH_ABI_VERSION 19
+ * index_update_tile;
+ * 20: fh_batch_new_wide and the rest of 19 unchanged, plus finch_index_cluster, finch_cluster_host and finch_cluster_stats in
+ * finch_host.h and the option index_cluster_margin) */
+#define FH_ABI_VERSION 20
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---

@@ -280,6 +280,51 @@ int finch_index_dist(const finch_index *ix, const finch_sketches *refs, const fi
                      int old_mode, double max_distance, finch_dist_result **out);
 int finch_index_dist_stats(const finch_dist_result *r, uint64_t *pairs_touched, uint64_t *pairs_copied);
 
+/* single-linkage clusters of a library: what follows `finch dist --pairwise -d D` in a dereplication, and what finch_index_keep
+ * ends one with.  Not in the reference; the contract is this comment (tests/index_cluster_model.py states it in Python).
+ *   Edges.  For an ordered pair (q, r) of library sketches, q != r, let (c, i, j) be the counts finch_dist makes for query q and
+ *     reference r.  The pair PASSES when distance_from_counts(old_mode, c, old_mode ? |r| : i, j, kmer_length of q) gives
+ *     mash_distance <= max_distance: finch_dist's function and comparison.  a and b are LINKED when (a, b) or (b, a) passes --
+ *     both orders count: old mode is not symmetric, and kmer_length is the query's.  No name-based self-skip: two entries with
+ *     equal names and content are linked like any pair at distance 0.  For a library of distinct names the ordered pairs that pass
+ *     are exactly the rows of a finch_dist call of the library against itself with the same mode and bound.
+ *   Result.  labels[v] = the smallest index of v's connected component: deterministic, whatever happens in whatever order on
+ *     the device.
+ * finch_cluster_host: the contract as written, on the host: every ordered pair through finch_dist's own counting and distance
+ *   functions -- O(R^2) merge walks --, then a union-find; no device.  *edges (may be NULL) = the ordered pairs q != r that pass.
+ *   Any bound: NaN or max_distance < 0 links nothing (labels[v] = v), a bound >= 1 links everything.  FH_ERR_INVALID for a null
+ *   argument, n_labels other than the library's size, hashes that do not ascend strictly, old mode with an empty sketch next to a
+ *   non-empty one (pairwise makes it a query).
+ * finch_index_cluster: the same labels through the index, and stats->edges == finch_cluster_host's edges.  The device counts the
+ *   pairs that share a hash as finch_index_dist's pairwise form does, completes each one's jaccard -- the host's division, bit for
+ *   bit -- and sorts it by two bounds per query, x = exp(-kmer_length(q) * max_distance), m = option index_cluster_margin:
+ *     jaccard >= jhi[q] = x / (2 - x) * (1 + m), or jaccard == 1 (distance exactly 0 at every k): SURE -- q and r are united on
+ *       the device, in a lock-free union-find of one word per reference, and nothing crosses (where jhi is no normal positive
+ *       number it is +inf: only jaccard 1 is sure);
+ *     jaccard < jlo[q] = x / (2 - x) * (1 - 2^-20), finch_index_dist's jmin: DROPPED;
+ *     between: (q, r, c, i, j) crosses and the host decides with distance_from_counts, as finch_index_dist does.
+ *   Each device entry ends with a label per reference (4 bytes each cross); the host merges them with the band's kept pairs and
+ *   with the pairs that have an empty side, which it makes itself exactly as finch_index_dist does.
+ *   Refusals and trivial cases, as finch_index_dist's: max_distance >= 1: FH_ERR_INVALID (every pair is within such a bound: the
+ *   library is one cluster); NaN or max_distance < 0: FH_OK, labels[v] = v, no device touched (-0.0 is 0); FH_ERR_INVALID for a
+ *   `refs` that is not the library of the index (sketch count and total hash count are checked), hashes that do not ascend
+ *   strictly, old mode with an empty sketch next to a non-empty one (before any launch), n_labels other than the library's size,
+ *   option index_cluster_margin outside [2^-20, 0.5] (default 2^-20; nothing sweeps the bands' soundness below it; tests use 0.25
+ *   so that most pairs cross).  An index of a library without a hash has no device entries: the whole call runs on the host.
+ *   One call at a time runs on an index; FH_ERR_STATE as for finch_index_search.  labels[] is unspecified after a failure.
+ *   stats (may be NULL): kernel_ms = the count, finish and labels kernels; launches = the launches of chunks of queries;
+ *   pairs_touched as in finch_index_dist_stats; pairs_united = ordered pairs q != r the device decided by itself; pairs_copied =
+ *   entries that crossed; pairs_kept_host = of those, the ones with q != r the exact test kept; edges = pairs_united +
+ *   pairs_kept_host + the host-made empty-side pairs that pass; clusters = distinct labels. */
+typedef struct {
+    double kernel_ms;
+    uint64_t launches, pairs_touched, pairs_united, pairs_copied, pairs_kept_host, edges, clusters;
+} finch_cluster_stats;
+int finch_index_cluster(const finch_index *ix, const finch_sketches *refs, int old_mode, double max_distance, uint32_t *labels,
+                        uint64_t n_labels, finch_cluster_stats *stats /* may be NULL */);
+int finch_cluster_host(const finch_sketches *refs, int old_mode, double max_distance, uint32_t *labels, uint64_t n_labels,
+                       uint64_t *edges /* may be NULL */);
+
 /* gather: the greedy decomposition of a query sketch over a library -- what follows a search whose best-first list is full of
  * near-duplicates.  Not in the reference; the contract is this comment (tests/gather_model.py states it twice in Python).
  *   gather(Q, refs, min_overlap, max_rounds) for one query sketch Q and the library refs[0 .. R):
