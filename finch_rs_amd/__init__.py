@@ -6,5 +6,5 @@ that path.  Importing this package never falls back to a CPU implementation.
 """
 from ._lib import (FinchHipError, SO_PATH, debug_env, debug_set, get_option, load, option_list,  # noqa: F401
                    set_option)
-from .sketch_schemes import (BatchSketcher, DeviceBuffer, FinchError, HipSketcher, KmerCount, SketchParams,  # noqa: F401
-                             device_count)
+from .sketch_schemes import (BatchSketcher, DeviceBuffer, FinchError, HipSketcher, KmerCount, RecordSketcher,  # noqa: F401
+                             SketchParams, device_count)

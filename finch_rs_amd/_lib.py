@@ -94,6 +94,17 @@ SYMBOLS = {
     "fh_batch_set_profiling": (C.c_int, [_P, C.c_int]),
     "fh_batch_kernel_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P, _U64P]),
     "fh_batch_counters": (C.c_int, [_P, _U64P, _U64P]),
+    "fh_records_new": (_P, [C.POINTER(FhParams), C.c_int, C.c_uint32, C.c_uint64]),
+    "fh_records_free": (None, [_P]),
+    "fh_records_max_positions": (C.c_uint32, []),
+    "fh_records_rows_cap": (C.c_uint64, [_P]),
+    "fh_records_stage": (C.c_int, [_P, C.c_int, C.POINTER(_P), _U64P]),
+    "fh_records_submit_packed": (C.c_int, [_P, C.c_int, _P, _P, C.c_uint32]),
+    "fh_records_wait": (C.c_int, [_P, C.c_int, _P]),
+    "fh_records_result": (C.c_int, [_P, C.c_int, C.c_uint32, _U64P, _U64P]),
+    "fh_records_copy_out_records": (C.c_int, [_P, C.c_int, C.c_uint32, _P, _P]),
+    "fh_records_kernel_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P, _U64P]),
+    "fh_records_counters": (C.c_int, [_P, _U64P, _U64P]),
     "fh_set_profiling": (C.c_int, [_P, C.c_int]),
     "fh_kernel_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P, _U64P]),
     "fh_debug_counters": (C.c_int, [_P, _U64P, _U64P, _U64P]),

@@ -1617,6 +1617,7 @@ void fh_release_cached(void) {
     }
     for (fh_sketcher *s : victims) destroy_handle(s);
     fh::batch_release_cached(); // (parked batch handles, fh_batch.hip)
+    fh::records_release_cached(); // (parked record sketchers, fh_records.hip)
 }
 
 static fh_sketcher *new_handle(const fh_params *params, int device);

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "fh_batch_plan.h"
+#include "fh_records_plan.h"
 #include "fh_host_model.h"
 #include "fh_options.h"
 #include "fh_inflate.h"
@@ -4328,6 +4329,379 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
     *out = res.release();
     return FH_OK;
 } FINCH_CATCH
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// finch_sketch_records: one Sketch per RECORD of a FASTA input (mash sketch -i, sourmash --singleton).  The call reads every
+// input once through the ByteSources (so every compression the host reader opens is free), splits the text at its header lines
+// (fh_records_plan.h: split_records, split_header) and deals the records to workers.  A record the record sketcher serves
+// (fh_records.hip: Mash and Scaled, k <= 32, no more than FH_RECORDS_MAX_POS positions) is packed into a slot of the worker's
+// handle in the two-bit form, side by side with the others of its group, and sketched in a workgroup's LDS -- one launch per
+// group, while the worker packs the next group into the other slot.  Every other record, and every record the device reports as
+// not taken, goes one by one through sketch_stream over its own text: the contract's right-hand side, exact for any parameters.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+namespace rp = fh::rplan;
+
+struct RecordsStats {
+    uint64_t records = 0, in_lds = 0, one_by_one = 0, launches = 0;
+    double kernel_ms = 0;
+};
+thread_local RecordsStats g_records_stats;
+
+struct RecordsInput {
+    std::string name;          // the file's name (messages)
+    std::vector<uint8_t> text; // decompressed
+};
+struct RecordRef {
+    uint32_t input;
+    rp::Record r;
+};
+
+// what the workers of one call share
+struct RecordsCall {
+    const finch_sketch_params &sp;
+    finch_filter_params filters; // filter_on = 0
+    const std::vector<RecordsInput> &inputs;
+    const std::vector<RecordRef> &recs;
+    std::vector<Sketch> &out;
+    bool lds_on = true;
+    uint64_t group_n = 0;
+    uint32_t handle_records = 1; // the sizes the workers' handles are made for
+    uint64_t handle_stage = 4096;
+    std::atomic<uint64_t> in_lds{0}, one_by_one{0}, launches{0}, kernel_us{0};
+    std::mutex err_mu;
+    int first_err_code = FH_OK;
+    uint64_t first_err_idx = UINT64_MAX;
+    std::string first_err_msg;
+    void record_error(uint64_t j, int rc, const std::string &msg) {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (j < first_err_idx) {
+            first_err_idx = j;
+            first_err_code = rc;
+            first_err_msg = msg;
+        }
+    }
+    const uint8_t *text(const RecordRef &q) const { return inputs[q.input].text.data(); }
+    std::string name_of(const RecordRef &q, std::string *comment) const {
+        const uint8_t *h = text(q) + q.r.hdr0;
+        const rp::HeaderSplit s = rp::split_header(h, (size_t)(q.r.hdr1 - q.r.hdr0));
+        if (comment) comment->assign((const char *)h + s.comment_off, s.comment_len);
+        return std::string((const char *)h, s.name_len);
+    }
+};
+
+class RecordWorker {
+public:
+    RecordWorker(RecordsCall &call, const fh_params &full, int device) : c_(call) {
+        handles_.full = full;
+        handles_.final_size = call.sp.final_size;
+        handles_.device = device;
+    }
+    ~RecordWorker() {
+        if (h_) fh_records_free(h_); // (left by an exception only)
+    }
+
+    void take(uint64_t j) {
+        const rp::Record &r = c_.recs[j].r;
+        if (rp::route(c_.sp.kind, c_.sp.kmer_length, r.positions, c_.lds_on) == rp::Route::OneByOne || !stage(j)) one_by_one(j);
+    }
+
+    void finish() {
+        if (!h_) return;
+        submit_cur();
+        collect(0);
+        collect(1);
+        double ms = 0;
+        uint64_t nl = 0;
+        if (fh_records_kernel_time(h_, &ms, &nl, nullptr) == FH_OK) {
+            c_.kernel_us += (uint64_t)(ms * 1000.0 + 0.5);
+            c_.launches += nl;
+        }
+        fh_records_free(h_);
+        h_ = nullptr;
+    }
+
+private:
+    struct Group {
+        std::vector<uint64_t> idx, off, len;
+        uint64_t fill = 0, rows = 0;
+        bool in_flight = false;
+        void clear() {
+            idx.clear(), off.clear(), len.clear();
+            fill = rows = 0;
+        }
+    };
+
+    void one_by_one(uint64_t j) { // the record's own text through its own sketcher (sketch_stream, lib.rs:51-94)
+        const RecordRef &q = c_.recs[j];
+        std::string comment;
+        const std::string name = c_.name_of(q, &comment);
+        const int rc = sketch_stream(std::make_unique<MemSource>(c_.text(q) + q.r.text0, (size_t)(q.r.text1 - q.r.text0)), name, c_.sp, c_.filters, handles_, c_.out[j]);
+        if (rc != FH_OK) c_.record_error(j, rc, g_host_err);
+        else c_.out[j].comment = comment;
+        c_.one_by_one++;
+    }
+
+    bool open_handle() {
+        fh_params bp = to_fh(c_.sp, 0);
+        bp.size = c_.group_n;
+        h_ = fh_records_new(&bp, handles_.device, c_.handle_records, c_.handle_stage);
+        if (h_ && (fh_records_stage(h_, 0, &stage_[0], &stage_cap_) != FH_OK || fh_records_stage(h_, 1, &stage_[1], &stage_cap_) != FH_OK)) {
+            fh_records_free(h_);
+            h_ = nullptr;
+        }
+        if (!h_) {
+            failed_ = true; // (no memory for it, say: every record one by one)
+            return false;
+        }
+        rows_cap_ = fh_records_rows_cap(h_);
+        return true;
+    }
+
+    bool stage(uint64_t j) { // true: record j is part of the current group
+        if (failed_ || (!h_ && !open_handle())) return false;
+        const RecordRef &q = c_.recs[j];
+        const uint64_t need = rp::region_bytes(q.r.positions);
+        const uint64_t rows = rp::row_bound(c_.sp.kind, c_.group_n, c_.sp.kmer_length, q.r.positions);
+        if (need > stage_cap_ || rows > rows_cap_) return false;
+        if (grp_[cur_].idx.size() >= c_.handle_records || grp_[cur_].fill + need > stage_cap_ || grp_[cur_].rows + rows > rows_cap_) submit_cur();
+        Group &g = grp_[cur_];
+        if (!packer_) {
+            packer_.reset(new fh_pack2::Packer);
+            packer_->force_form((unsigned)cfg_u64("pack_scalar", 0));
+        }
+        packer_->begin(stage_[cur_] + g.fill);
+        packer_->text(c_.text(q) + q.r.seq0, (size_t)(q.r.text1 - q.r.seq0));
+        if (packer_->finish() != q.r.positions) return false; // (cannot happen: split_records counts what the packer keeps)
+        g.idx.push_back(j);
+        g.off.push_back(g.fill);
+        g.len.push_back(q.r.positions);
+        g.fill = (g.fill + need + 63) & ~63ull;
+        g.rows += rows;
+        return true;
+    }
+
+    void submit_cur() { // hand the current group to the device, go on in the other slot (its previous group collected)
+        Group &g = grp_[cur_];
+        if (g.idx.empty()) return;
+        if (fh_records_submit_packed(h_, cur_, g.off.data(), g.len.data(), (uint32_t)g.idx.size()) != FH_OK) {
+            for (uint64_t j : g.idx) one_by_one(j);
+            g.clear();
+            return;
+        }
+        g.in_flight = true;
+        cur_ ^= 1;
+        collect(cur_);
+    }
+
+    void collect(int slot) { // wait for the group in `slot`, turn its results into Sketches
+        Group &g = grp_[slot];
+        if (!g.in_flight) return;
+        g.in_flight = false;
+        const finch_sketch_params &sp = c_.sp;
+        const bool whole_rows = sp.kind == 1; // Scaled: no cut to final_size, no strict error (mod.rs:115-128)
+        status_.assign(g.idx.size() + 1, 1);
+        const int rc = fh_records_wait(h_, slot, status_.data());
+        const uint32_t k = sp.kmer_length;
+        for (size_t i = 0; i < g.idx.size(); ++i) {
+            const uint64_t j = g.idx[i];
+            if (rc != FH_OK || status_[i] != 0) { // not taken (or the submit failed as a whole)
+                one_by_one(j);
+                continue;
+            }
+            uint64_t n = 0, tk = 0;
+            int r2 = fh_records_result(h_, slot, (uint32_t)i, &n, &tk);
+            const size_t keep = whole_rows ? (size_t)n : (size_t)std::min<uint64_t>(n, sp.final_size); // process_post_filter
+            recs_.resize(n + 1);
+            km_.resize(n * (size_t)k + 1);
+            if (r2 == FH_OK) r2 = fh_records_copy_out_records(h_, slot, (uint32_t)i, recs_.data(), km_.data());
+            if (r2 != FH_OK) {
+                c_.record_error(j, r2, fh_last_error());
+                continue;
+            }
+            c_.in_lds++;
+            const RecordRef &q = c_.recs[j];
+            Sketch &out = c_.out[j];
+            out.name = c_.name_of(q, &out.comment);
+            if (!whole_rows && !sp.no_strict && keep < sp.final_size) {
+                char buf[512];
+                snprintf(buf, sizeof buf, "%s had too few kmers (%zu) to sketch", out.name.c_str(), keep);
+                c_.record_error(j, FH_ERR_INVALID, buf);
+                continue;
+            }
+            out.seq_length = q.r.seq_length;
+            out.num_valid_kmers = tk;
+            out.hashes.resize(keep);
+            for (size_t t = 0; t < keep; ++t)
+                out.hashes[t] = KmerCount{recs_[t].hash, KmerBytes((const char *)km_.data() + t * (size_t)k, (size_t)k), recs_[t].count, recs_[t].extra_count};
+            out.filter_params = c_.filters;
+            out.sketch_params = sp;
+        }
+        g.clear();
+    }
+
+    RecordsCall &c_;
+    HandleSet handles_;
+    fh_records *h_ = nullptr;
+    bool failed_ = false;
+    Group grp_[2];
+    int cur_ = 0;
+    uint8_t *stage_[2] = {nullptr, nullptr};
+    uint64_t stage_cap_ = 0, rows_cap_ = 0;
+    std::vector<uint8_t> status_, km_;
+    std::vector<fh_kmer_count> recs_;
+    std::unique_ptr<fh_pack2::Packer> packer_;
+};
+
+// the whole decompressed input
+int read_all(std::unique_ptr<ByteSource> raw, std::vector<uint8_t> &text) {
+    std::unique_ptr<ByteSource> src;
+    if (int rc = open_source(std::move(raw), src)) return rc;
+    size_t n = 0;
+    text.resize(1u << 20);
+    for (;;) {
+        if (n == text.size()) text.resize(text.size() * 2);
+        const size_t g = src->read(text.data() + n, text.size() - n);
+        if (g == 0) break;
+        n += g;
+    }
+    if (src->failed()) return hfail(FH_ERR_INVALID, "corrupt compressed stream");
+    text.resize(n);
+    return FH_OK;
+}
+
+// what the two entry points refuse before anything is read, and nothing of it touches a device
+int records_refusals(bool null_arg, const finch_filter_params *filters, uint32_t n_devices) {
+    if (null_arg) return hfail(FH_ERR_INVALID, "null argument");
+    if (n_devices > 16) return hfail(FH_ERR_INVALID, "more than 16 device entries");
+    if (filters->filter_on == 1)
+        return hfail(FH_ERR_UNSUPPORTED, "finch_sketch_records: filtering a single record's sketch is not offered (filter_on must be 0 or -1)");
+    return FH_OK;
+}
+int records_input_check(const RecordsInput &in) {
+    if (in.text.empty()) return hfail(FH_ERR_INVALID, "empty input: not a FASTA/FASTQ file");
+    if (in.text[0] == '@')
+        return hfail(FH_ERR_UNSUPPORTED, "%s: a FASTQ input (first byte '@'): finch_sketch_records makes one sketch per FASTA record, one sketch per read is not offered",
+                     in.name.c_str());
+    if (in.text[0] != '>') return hfail(FH_ERR_INVALID, "not a FASTA/FASTQ file (first byte 0x%02x)", in.text[0]);
+    return FH_OK;
+}
+
+int sketch_records_core(const std::vector<RecordsInput> &inputs, const finch_sketch_params *sp, const finch_filter_params *filters, const int *devices,
+                        uint32_t n_devices, uint32_t n_threads, finch_sketches **out) {
+    g_records_stats = RecordsStats{};
+    std::vector<int> devs;
+    if (devices && n_devices) devs.assign(devices, devices + n_devices);
+    else devs.push_back(0);
+    std::vector<RecordRef> recs;
+    {
+        std::vector<rp::Record> one;
+        for (uint32_t f = 0; f < inputs.size(); ++f) {
+            one.clear();
+            rp::split_records(inputs[f].text.data(), inputs[f].text.size(), one);
+            for (const rp::Record &r : one) recs.push_back(RecordRef{f, r});
+        }
+    }
+    auto res = std::make_unique<finch_sketches>();
+    res->v.resize(recs.size());
+    RecordsCall call{*sp, *filters, inputs, recs, res->v};
+    call.filters.filter_on = 0; // lib.rs:70-76: FASTA defaults to no filtering, and filtering was not asked for
+    call.lds_on = cfg_u64("records_lds", 1) != 0;
+    call.group_n = rp::group_n(sp->kind, sp->kmers_to_sketch, sp->final_size);
+    // the workers' handles: no larger than the call's records need
+    uint64_t lds_records = 0, lds_bytes = 0;
+    for (const RecordRef &q : recs)
+        if (rp::route(sp->kind, sp->kmer_length, q.r.positions, call.lds_on) == rp::Route::Lds) lds_records++, lds_bytes += rp::region_bytes(q.r.positions) + 64;
+    // (... rounded up to powers of two, so that calls of about one size find each other's parked handles)
+    call.handle_records = (uint32_t)std::min<uint64_t>(rp::GROUP_RECORDS, rp::pow2_at_least(std::max<uint64_t>(16, lds_records)));
+    call.handle_stage = std::min<uint64_t>(rp::GROUP_STAGE, rp::pow2_at_least(std::max<uint64_t>(64u << 10, lds_bytes)));
+    // records are dealt in runs: long enough that a worker's groups fill, short enough that every worker gets some
+    if (n_threads == 0) n_threads = std::min<uint32_t>(16u, std::max<uint32_t>(4u, usable_cpus() / (uint32_t)devs.size())) * (uint32_t)devs.size();
+    const uint64_t total = recs.size();
+    const uint64_t run = std::max<uint64_t>(16, std::min<uint64_t>(2048, total / ((uint64_t)n_threads * 4) + 1));
+    n_threads = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_threads, (total + run - 1) / run));
+    const uint64_t ml = env_max_launch() ? env_max_launch() : (2ull << 20);
+    std::atomic<uint64_t> next{0};
+    auto worker = [&](uint32_t w) {
+        RecordWorker rw(call, to_fh(*sp, ml, 16ull << 20), devs[w % devs.size()]);
+        for (;;) {
+            const uint64_t a = next.fetch_add(run);
+            if (a >= total) break;
+            for (uint64_t j = a; j < std::min(total, a + run); ++j) rw.take(j);
+        }
+        rw.finish();
+    };
+    {
+        std::vector<std::thread> th;
+        th.reserve(n_threads);
+        std::atomic<bool> worker_threw{false};
+        auto guarded = [&](uint32_t w) {
+            try {
+                worker(w);
+            } catch (...) {
+                worker_threw = true;
+            }
+        };
+        try {
+            for (uint32_t w = 0; w < n_threads; ++w) th.emplace_back(guarded, w);
+        } catch (...) { // fewer workers than asked for: the runs are pulled from one counter, those that started take them all
+        }
+        if (th.empty()) guarded(0u);
+        for (auto &t : th) t.join();
+        if (worker_threw) return hfail(FH_ERR_CAPACITY, "out of host memory");
+    }
+    if (call.first_err_code != FH_OK) return hfail(call.first_err_code, "%s", call.first_err_msg.c_str());
+    g_records_stats.records = total;
+    g_records_stats.in_lds = call.in_lds;
+    g_records_stats.one_by_one = call.one_by_one;
+    g_records_stats.kernel_ms = (double)call.kernel_us / 1000.0;
+    g_records_stats.launches = call.launches;
+    *out = res.release();
+    return FH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int finch_sketch_records(const char *const *filenames, uint32_t n_files, const finch_sketch_params *sp, const finch_filter_params *filters,
+                         const int *devices, uint32_t n_devices, uint32_t n_threads, finch_sketches **out) try {
+    if (int rc = records_refusals((!filenames && n_files) || !sp || !filters || !out, filters, n_devices)) return rc;
+    std::vector<RecordsInput> inputs(n_files);
+    const unsigned read_threads = read_threads_total(cfg("read_threads"));
+    for (uint32_t f = 0; f < n_files; ++f) {
+        if (!filenames[f]) return hfail(FH_ERR_INVALID, "null argument");
+        inputs[f].name = filenames[f];
+        FILE *fp = inputs[f].name == "-" ? stdin : fopen(filenames[f], "rb");
+        if (!fp) return hfail(FH_ERR_INVALID, "%s: %s (os error %d)", filenames[f], strerror(errno), errno);
+        if (int rc = read_all(std::make_unique<FileSource>(fp, fp != stdin, read_threads), inputs[f].text)) return rc;
+        if (int rc = records_input_check(inputs[f])) return rc;
+    }
+    return sketch_records_core(inputs, sp, filters, devices, n_devices, n_threads, out);
+} FINCH_CATCH
+
+int finch_sketch_records_buffer(const uint8_t *data, uint64_t len, const finch_sketch_params *sp, const finch_filter_params *filters,
+                                const int *devices, uint32_t n_devices, uint32_t n_threads, finch_sketches **out) try {
+    if (int rc = records_refusals((!data && len) || !sp || !filters || !out, filters, n_devices)) return rc;
+    std::vector<RecordsInput> inputs(1);
+    inputs[0].name = "the buffer";
+    if (int rc = read_all(std::make_unique<MemSource>(data, (size_t)len, read_threads_total(cfg("read_threads"))), inputs[0].text)) return rc;
+    if (int rc = records_input_check(inputs[0])) return rc;
+    return sketch_records_core(inputs, sp, filters, devices, n_devices, n_threads, out);
+} FINCH_CATCH
+
+int finch_sketch_records_stats(uint64_t *records, uint64_t *in_lds, uint64_t *one_by_one, double *kernel_ms, uint64_t *launches) {
+    const RecordsStats &s = g_records_stats;
+    if (records) *records = s.records;
+    if (in_lds) *in_lds = s.in_lds;
+    if (one_by_one) *one_by_one = s.one_by_one;
+    if (kernel_ms) *kernel_ms = s.kernel_ms;
+    if (launches) *launches = s.launches;
+    return FH_OK;
+}
 
 static int sharded_devices(const int *devices, uint32_t n_devices, std::vector<int> &devs) {
     if (devices && n_devices) devs.assign(devices, devices + n_devices);

@@ -17,5 +17,7 @@ void api_kmer_ascii(uint64_t m, uint64_t mhi, int k, uint8_t *out);
 uint64_t api_scaled_max_hash(double scale);
 // fh_batch.hip: free the parked batch handles (fh_release_cached)
 void batch_release_cached();
+// fh_records.hip: free the parked record sketchers (fh_release_cached)
+void records_release_cached();
 
 } // namespace fh

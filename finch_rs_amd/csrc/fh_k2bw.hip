@@ -55,14 +55,7 @@ __device__ __forceinline__ void classify_tile_b(const uint8_t *seq, u64 len, u64
     good_ring[par * 64u + (u32)lane] = g0 | (g1 << 16);
 }
 
-__device__ __forceinline__ void load_tile_two_bit(const uint8_t *region, u64 tile, int lane, u32 *codes_ring, u32 *good_ring) {
-    const uint8_t *const tb = region + tile * (u64)TWO_BIT_TILE_BYTES; // wave-uniform
-    const uint2 q = *reinterpret_cast<const uint2 *>(tb + 8u * (u32)lane);
-    const u32 g = *reinterpret_cast<const u32 *>(tb + TWO_BIT_CODES_BYTES + 4u * (u32)lane);
-    const u32 par = (u32)(tile & 1u);
-    *reinterpret_cast<uint2 *>(&codes_ring[par * 128u + 2u * (u32)lane]) = q;
-    good_ring[par * 64u + (u32)lane] = g;
-}
+// (the two-bit form: load_tile_two_bit, fh_k2_common.h)
 
 template <int K>
 __global__ __launch_bounds__(256, 2) void k2_batch_w(const BatchArgs a) {

@@ -104,6 +104,8 @@ const OptDef DEFS[] = {
     // --- finch_merge_groups ---
     {"merge_tile", "output positions per tile of a merge step, 1..4096 (default 1024; tests: many tiles per step)"},
     {"merge_chunk_records", "accumulator records per merge launch, at most 2^31 (default 4 M; tests: many launches)"},
+    // --- finch_sketch_records ---
+    {"records_lds", "1 (the default): finch_sketch_records sketches the records the record sketcher serves in a workgroup's LDS, many per launch; 0: every record one by one through its own sketcher (tests, A/B)"},
 };
 constexpr int N_OPTS = (int)(sizeof(DEFS) / sizeof(DEFS[0]));
 

@@ -65,6 +65,12 @@ _SYMS = {
                                      C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "finch_sketch_buffer": (C.c_int, [_P, C.c_uint64, C.c_char_p, C.POINTER(CSketchParams), C.POINTER(CFilterParams),
                                       C.c_int, C.POINTER(_P)]),
+    "finch_sketch_records": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(CSketchParams), C.POINTER(CFilterParams),
+                                       C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "finch_sketch_records_buffer": (C.c_int, [_P, C.c_uint64, C.POINTER(CSketchParams), C.POINTER(CFilterParams),
+                                              C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "finch_sketch_records_stats": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_uint64)]),
     "finch_sketch_file_sharded": (C.c_int, [C.c_char_p, C.POINTER(CSketchParams), C.POINTER(CFilterParams), C.POINTER(C.c_int),
                                             C.c_uint32, C.c_uint64, C.POINTER(_P)]),
     "finch_sketch_buffer_sharded": (C.c_int, [_P, C.c_uint64, C.c_char_p, C.POINTER(CSketchParams), C.POINTER(CFilterParams),
@@ -296,6 +302,10 @@ class Sketches:
     def append(self, other: "Sketches") -> None:
         _check(lib().finch_sketches_append(self._p, other._p))
 
+    def comment(self, i: int) -> str:
+        """sketch i's comment (sketch_records: the rest of the record's header line behind its name)"""
+        return lib().finch_sketch_comment(self._p, i).decode(errors="replace")
+
     def set_comment(self, i: int, comment: str) -> None:
         _check(lib().finch_sketch_set_comment(self._p, i, comment.encode()))
 
@@ -345,6 +355,33 @@ def sketch_files(filenames: Sequence[str], sketch_params: SketchParams, filters:
     out = _P()
     _check(lib().finch_sketch_files(arr, len(filenames), C.byref(sp), C.byref(fp), darr, len(devs), n_threads, C.byref(out)))
     return Sketches(out, sketch_params)
+
+
+def sketch_records(inputs, sketch_params: SketchParams, filters: Optional[FilterParams] = None, devices: Sequence[int] = (0,),
+                   n_threads: int = 0, stats: Optional[dict] = None) -> Sketches:
+    """one Sketch per record of FASTA inputs (finch_sketch_records): `inputs` is a path, a sequence of paths, or the bytes of
+    one input; `stats`, if given, receives records / in_lds / one_by_one / kernel_ms / launches of this call"""
+    if filters is None:
+        dflt = CFilterParams()
+        lib().finch_default_filter_params(C.byref(dflt))
+        filters = FilterParams.from_c(dflt)
+    devs = list(devices) if devices else [0]
+    darr = (C.c_int * len(devs))(*devs)
+    sp, fp = _params_c(sketch_params), filters.to_c()
+    out = _P()
+    if isinstance(inputs, (bytes, bytearray, memoryview)):
+        buf = np.frombuffer(inputs, dtype=np.uint8)
+        _check(lib().finch_sketch_records_buffer(buf.ctypes.data, len(buf), C.byref(sp), C.byref(fp), darr, len(devs), n_threads, C.byref(out)))
+    else:
+        paths = [inputs] if isinstance(inputs, str) else list(inputs)
+        arr = (C.c_char_p * len(paths))(*[f.encode() for f in paths])
+        _check(lib().finch_sketch_records(arr, len(paths), C.byref(sp), C.byref(fp), darr, len(devs), n_threads, C.byref(out)))
+    res = Sketches(out, sketch_params)
+    if stats is not None:
+        a, b, c, ms, nl = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double(), C.c_uint64()
+        _check(lib().finch_sketch_records_stats(C.byref(a), C.byref(b), C.byref(c), C.byref(ms), C.byref(nl)))
+        stats.update(records=a.value, in_lds=b.value, one_by_one=c.value, kernel_ms=ms.value, launches=nl.value)
+    return res
 
 
 def sketch_stream(data: bytes, name: str, sketch_params: SketchParams, filters: FilterParams, device: int = 0) -> Sketches:

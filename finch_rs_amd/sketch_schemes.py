@@ -415,6 +415,117 @@ class BatchSketcher:
         return ms.value, n.value, pos.value
 
 
+class RecordSketcher:
+    """One sketch per record, many records per launch (include/finch_hip.h, fh_records_*): a record of at most `max_positions`
+    positions is hashed, sorted, folded into counts and cut to its sketch in ONE workgroup's LDS, exactly.  Mash (size >= 1) or
+    Scaled (kind=KIND_SCALED, any size, scale in (0, 1]), k <= 32, any seed.
+    `sketch_many(blocks)` -> per block (a packed one-record stream) either (records, kmers, total_kmers) or None ("not taken":
+    longer than `max_positions`, a 64-bit collision, or a hash of 2^64 - 1 -- sketch that block through a HipSketcher)."""
+
+    def __init__(self, size: int, kmer_length: int, seed: int = 0, device: int = 0, max_records: int = 1024,
+                 stage_bytes: int = 8 << 20, kind: int = KIND_MASH, scale: float = 0.0):
+        self._L = _lib.load()
+        self.size, self.kmer_length, self.seed, self.device = size, kmer_length, seed, device
+        self.max_records = max_records
+        self.kind, self.scale = kind, scale
+        self.max_positions = int(self._L.fh_records_max_positions())
+        p = FhParams(kind, kmer_length, size, seed, scale, 0, 0, 0)
+        self._h = self._L.fh_records_new(C.byref(p), device, max_records, stage_bytes)
+        if not self._h:
+            raise FinchHipError(-1, (self._L.fh_last_error() or b"").decode(errors="replace"))
+        self.rows_cap = int(self._L.fh_records_rows_cap(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.fh_records_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def stage(self, slot: int) -> np.ndarray:
+        """the pinned staging buffer of `slot` as a writable uint8 array"""
+        buf, cap = C.c_void_p(), C.c_uint64()
+        check(self._L.fh_records_stage(self._h, slot, C.byref(buf), C.byref(cap)))
+        return np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_uint8)), shape=(cap.value,))
+
+    def packed_bytes(self, n_positions: int) -> int:
+        """bytes a record of n_positions occupies in the two-bit form"""
+        return int(self._L.fh_batch_packed_bytes(n_positions))
+
+    def pack(self, block: np.ndarray, region: np.ndarray) -> None:
+        """write a packed byte stream's two-bit form into `region` (a slice of the staging buffer)"""
+        block = np.ascontiguousarray(block, dtype=np.uint8)
+        check(self._L.fh_batch_pack(block.ctypes.data, len(block), region.ctypes.data, len(region)))
+
+    def row_bound(self, n_positions: int) -> int:
+        """rows a record of n_positions may need in a slot's result (a submit's sum stays within `rows_cap`)"""
+        if n_positions > self.max_positions:
+            return 0
+        w = max(0, n_positions - self.kmer_length + 1)
+        return min(self.size, w) if self.kind == KIND_MASH else w
+
+    def submit(self, slot: int, offsets, lens) -> None:
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = np.ascontiguousarray(lens, dtype=np.uint64)
+        check(self._L.fh_records_submit_packed(self._h, slot, o.ctypes.data, n.ctypes.data, len(o)))
+
+    def wait(self, slot: int, n_records: int) -> np.ndarray:
+        st = np.zeros(max(n_records, 1), dtype=np.uint8)
+        check(self._L.fh_records_wait(self._h, slot, st.ctypes.data))
+        return st[:n_records]
+
+    def result(self, slot: int, i: int):
+        n, tk = C.c_uint64(), C.c_uint64()
+        check(self._L.fh_records_result(self._h, slot, i, C.byref(n), C.byref(tk)))
+        kc = np.empty(n.value, dtype=KC_DTYPE)
+        km = np.empty((n.value, self.kmer_length), dtype=np.uint8)
+        check(self._L.fh_records_copy_out_records(self._h, slot, i, kc.ctypes.data, km.ctypes.data))
+        return kc, km, tk.value
+
+    def sketch_many(self, blocks, slot: int = 0):
+        """blocks: packed one-record streams (bytes / uint8 arrays) -> list of (records, kmers, total_kmers) / None, in order; as
+        many submits as it takes, alternating between the two slots from `slot` on (the next group is packed while the device
+        works on the one before)"""
+        blocks = [np.frombuffer(b, dtype=np.uint8) if not isinstance(b, np.ndarray) else b for b in blocks]
+        out, pending, i = [], None, 0
+        while i < len(blocks) or pending:
+            group = None
+            if i < len(blocks):
+                buf = self.stage(slot)
+                offs, lens, pos, rows = [], [], 0, 0
+                while i < len(blocks) and len(offs) < self.max_records:
+                    need, bound = self.packed_bytes(len(blocks[i])), self.row_bound(len(blocks[i]))
+                    if pos + need > len(buf) or rows + bound > self.rows_cap:
+                        break
+                    self.pack(blocks[i], buf[pos:pos + need])
+                    offs.append(pos)
+                    lens.append(len(blocks[i]))
+                    pos = (pos + need + 63) & ~63
+                    rows += bound
+                    i += 1
+                if not offs:
+                    raise ValueError("block %d does not fit a slot" % i)
+                self.submit(slot, offs, lens)
+                group = (slot, len(offs))
+                slot ^= 1
+            if pending:
+                s, n = pending
+                st = self.wait(s, n)
+                out += [self.result(s, j) if st[j] == 0 else None for j in range(n)]
+            pending = group
+        return out
+
+    def counters(self):
+        a, b = C.c_uint64(), C.c_uint64()
+        check(self._L.fh_records_counters(self._h, C.byref(a), C.byref(b)))
+        return {"taken": a.value, "not_taken": b.value}
+
+    def kernel_time(self):
+        ms, n, pos = C.c_double(), C.c_uint64(), C.c_uint64()
+        check(self._L.fh_records_kernel_time(self._h, C.byref(ms), C.byref(n), C.byref(pos)))
+        return ms.value, n.value, pos.value
+
+
 class DeviceBuffer:
     """device memory through the C ABI (no torch needed)"""
 

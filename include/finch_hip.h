@@ -99,8 +99,11 @@ const char *fh_last_error(void);
  * 19: fh_batch_new_wide and the rest of 18 unchanged, plus finch_index_add and finch_index_keep in finch_host.h and the option
  * index_update_tile;
  * 20: fh_batch_new_wide and the rest of 19 unchanged, plus finch_index_cluster, finch_cluster_host and finch_cluster_stats in
- * finch_host.h and the option index_cluster_margin) */
-#define FH_ABI_VERSION 20
+ * finch_host.h and the option index_cluster_margin;
+ * 21: fh_batch_new_wide and the rest of 20 unchanged, plus the record sketcher (fh_records_new and the fh_records_* functions
+ * below), finch_sketch_records, finch_sketch_records_buffer and finch_sketch_records_stats in finch_host.h and the option
+ * records_lds) */
+#define FH_ABI_VERSION 21
 int fh_abi_version(void);
 
 /* --- configuration: ONE surface ---
@@ -460,6 +463,44 @@ fh_batch *fh_batch_new_wide(const fh_params *params, int device, uint32_t max_fi
 #define FH_BATCH_LARGE_MAX_N 16384u /* hashes of a Mash sketch the batch path serves (what the large epilogue sorts through one workgroup's LDS) */
 fh_batch *fh_batch_new_large(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes);
 int fh_batch_parked(uint64_t *handles, uint64_t *large_handles, uint64_t *large_device_bytes);
+
+/* --- one sketch per RECORD: short records sketched in a workgroup's LDS (fh_records.hip; finch_sketch_records is built on it) ---
+ * A record of a multi-FASTA (a plasmid, a 16S sequence, a contig) is too short for the batch sketcher's machinery -- a table
+ * partition, shard lists and an epilogue workgroup per file -- and needs none of it: all its hashes fit one workgroup's LDS,
+ * where they are sorted, folded into counts and cut to the sketch EXACTLY.  One launch sketches every record of a submit; a
+ * persistent workgroup takes a contiguous run of them.
+ *
+ * Served: FH_KIND_MASH (size >= 1) and FH_KIND_SCALED (any size, scale in (0, 1]), k = 1..32, any size (a record's rows are
+ * bounded by its windows), any seed, no test mask.  Refused with FH_ERR_UNSUPPORTED and a message that names the cause, before
+ * the device is looked at: AllCounts, k > 32, a test mask.
+ *
+ * The verbs are the batch sketcher's.  A handle has two slots; a record crosses the link in the TWO-BIT form
+ * (fh_batch_packed_bytes / fh_batch_pack: its tiles and the zero tile behind the last one), 64-byte aligned in the slot's
+ * staging buffer, offsets ascending.  lens[i] = the record's positions (bytes of its packed stream).
+ *   fh_records_wait's status[i] = 0: sketch i is ready; 1: NOT TAKEN -- the record has more than fh_records_max_positions()
+ *   positions, two of its k-mers share a 64-bit hash, or one of its hashes is 2^64 - 1: sketch it through an fh_sketcher.
+ *   There is no other outcome: the door never answers with anything but the exact sketch.
+ *   fh_records_submit_packed refuses (FH_ERR_CAPACITY) a submit whose rows -- the sum over its records of min(size [Mash],
+ *   positions - k + 1) -- exceed what fh_records_rows_cap reports for the handle: submit fewer records.
+ *   fh_records_result: the sketch's rows and the record's valid k-mers; fh_records_copy_out_records: the rows, ascending by
+ *   hash, and their k-mers' bytes (k per row).
+ *   fh_records_kernel_time: event-measured milliseconds, launches and positions of the record kernel since the last call;
+ *   fh_records_counters: records taken / not taken since fh_records_new.
+ *   fh_records_free parks an idle handle as fh_batch_free does (pinning its buffers takes longer than sketching a thousand
+ *   records); fh_records_new hands a parked one back for the same parameters, device and sizes; fh_release_cached frees them. */
+#define FH_RECORDS_MAX_POS 8192u /* positions of a record one workgroup's LDS holds (fh_records_plan.h) */
+typedef struct fh_records fh_records;
+fh_records *fh_records_new(const fh_params *params, int device, uint32_t max_records, uint64_t stage_bytes);
+void fh_records_free(fh_records *r);
+uint32_t fh_records_max_positions(void);
+uint64_t fh_records_rows_cap(fh_records *r);
+int fh_records_stage(fh_records *r, int slot, uint8_t **buf, uint64_t *cap);
+int fh_records_submit_packed(fh_records *r, int slot, const uint64_t *offsets, const uint64_t *lens, uint32_t n_records);
+int fh_records_wait(fh_records *r, int slot, uint8_t *status);
+int fh_records_result(fh_records *r, int slot, uint32_t i, uint64_t *n_out, uint64_t *total_kmers);
+int fh_records_copy_out_records(fh_records *r, int slot, uint32_t i, fh_kmer_count *records, uint8_t *kmers);
+int fh_records_kernel_time(fh_records *r, double *total_ms, uint64_t *launches, uint64_t *positions);
+int fh_records_counters(fh_records *r, uint64_t *taken, uint64_t *not_taken);
 
 /* --- measurement support (bench.py) --- */
 /* when enabled, every sketch-kernel launch is bracketed by HIP events on the handle's stream */

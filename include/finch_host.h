@@ -64,6 +64,36 @@ void finch_default_filter_params(finch_filter_params *out);
 int finch_sketch_files(const char *const *filenames, uint32_t n_files, const finch_sketch_params *sketch_params,
                        const finch_filter_params *filters, const int *devices, uint32_t n_devices, uint32_t n_threads,
                        finch_sketches **out);
+/* ONE SKETCH PER RECORD of FASTA inputs (mash sketch -i, sourmash --singleton): `out` holds one sketch per record of every
+ * input, in file order and then record order.  Let text_j be the bytes of record j as they stand in the decompressed input,
+ * from the record's '>' up to, not including, the '>' that begins the next header line (a '>' at a line start), or to the end
+ * of input.  Sketch j is, field for field, what finch_sketch_buffer(text_j, len_j, name_j, sketch_params, filters with
+ * filter_on = 0, ...) returns -- hashes, k-mer bytes, counts, extra_counts, seq_length (internal line ends count, one trailing
+ * line end is trimmed), num_valid_kmers, sketch_params, filter_params, the Mash cut to final_size and the strict error
+ * "<name> had too few kmers (<n>) to sketch" unless no_strict -- except that name_j is the header up to its first blank or tab,
+ * without the '>', and the comment is the rest of the header line behind that run of blanks and tabs, without the line end
+ * (empty if there is none).  A header without sequence is a record of no bases.  The first failing record wins.
+ * Any parameters are accepted and the result is always exact: records the record sketcher serves (include/finch_hip.h,
+ * fh_records_new: Mash and Scaled, kmer_length <= 32, at most FH_RECORDS_MAX_POS positions) are sketched many per launch in a
+ * workgroup's LDS; every other record -- kmer_length 33..64, AllCounts, longer records, all of them with the option
+ * records_lds=0 -- and every record the device reports as not taken goes one by one through its own sketcher.
+ * Input: whatever the host reader opens (plain, gzip, BGZF, bz2, xz, "-" for stdin); each input is held decompressed in host
+ * memory while the call runs.  devices: at most 16 entries (an entry may repeat; NULL / 0 = device 0); n_threads workers
+ * (0 = finch_sketch_files' rule), worker w on device w mod n_devices.
+ * Refused before any device is touched: FH_ERR_INVALID for a null argument or more than 16 device entries;
+ * FH_ERR_UNSUPPORTED for filters->filter_on == 1 (filtering a single record's sketch is not offered; -1 and 0 mean off) and
+ * for an input whose first byte is '@' (one sketch per read is not offered; the message names the file); an empty input is
+ * the error finch_sketch_files gives for it.
+ * finch_sketch_records_stats: the last call of the calling thread -- its records, how many were sketched in LDS and how many
+ * one by one (in_lds + one_by_one == records), the record kernel's event-measured milliseconds and its launches (any pointer
+ * may be NULL). */
+int finch_sketch_records(const char *const *filenames, uint32_t n_files, const finch_sketch_params *sketch_params,
+                         const finch_filter_params *filters, const int *devices, uint32_t n_devices, uint32_t n_threads,
+                         finch_sketches **out);
+int finch_sketch_records_buffer(const uint8_t *data, uint64_t len, const finch_sketch_params *sketch_params,
+                                const finch_filter_params *filters, const int *devices, uint32_t n_devices, uint32_t n_threads,
+                                finch_sketches **out);
+int finch_sketch_records_stats(uint64_t *records, uint64_t *in_lds, uint64_t *one_by_one, double *kernel_ms, uint64_t *launches);
 /* sketch_stream over an in-memory file image */
 int finch_sketch_buffer(const uint8_t *data, uint64_t len, const char *name, const finch_sketch_params *sketch_params,
                         const finch_filter_params *filters, int device, finch_sketches **out);
