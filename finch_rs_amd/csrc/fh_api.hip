@@ -2490,9 +2490,12 @@ int fh_push_bgzf_fastq(fh_sketcher *s, uint64_t bytes, uint32_t n_members, uint3
             HIP_TRY(hipStreamWaitEvent(s->stream, s->bz_done[q], 0));
             s->bz_used[q] = false;
         }
-    if (total == 0) return FH_OK;
-    s->bz_next = t ^ 1;
-    HIP_TRY(launch_fastq_cut(s->bz_text[t], (uint32_t)total, (flags & FH_BGZF_LAST) ? 1u : 0u, s->d_bz_status + 1, s->stream));
+    // (a batch whose members announce no text at all -- an end-of-file marker, or damage that says ISIZE 0 -- has still been
+    // judged by the inflate kernel: its verdict is read like any other)
+    if (total) {
+        s->bz_next = t ^ 1;
+        HIP_TRY(launch_fastq_cut(s->bz_text[t], (uint32_t)total, (flags & FH_BGZF_LAST) ? 1u : 0u, s->d_bz_status + 1, s->stream));
+    }
     HIP_TRY(hipMemcpyAsync(s->h_bz_status, s->d_bz_status, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (const uint32_t st = s->h_bz_status[0]) {
@@ -2500,6 +2503,7 @@ int fh_push_bgzf_fastq(fh_sketcher *s, uint64_t bytes, uint32_t n_members, uint3
                                           "stream longer or shorter than the member", "CRC-32 differs"};
         return fail(FH_ERR_INVALID, "BGZF member %u of the batch: %s", st >> 8, (st & 255u) < 7u ? why[st & 255u] : "corrupt");
     }
+    if (total == 0) return FH_OK;
     if (s->h_bz_status[2]) return fail(FH_ERR_INVALID, "no FASTQ record boundary at the end of a batch of BGZF text");
     const uint64_t cut = s->h_bz_status[1];
     s->bgzf_left_ptr = s->bz_text[t] + cut;

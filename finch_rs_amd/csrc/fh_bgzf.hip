@@ -112,7 +112,8 @@ extern "C" __device__ int fh_llvm_writelane(int, int, int) __asm("llvm.amdgcn.wr
 __device__ __forceinline__ u32 writelane(u32 value, u32 lane_idx, u32 vec) { return (u32)fh_llvm_writelane((int)value, (int)lane_idx, (int)vec); }
 
 // Huffman table of the n code lengths at `lens`: root table of 2^R entries (codes longer than R bits: KIND_LONG, decoded
-// from `cs`).  false: over-subscribed lengths.
+// from `cs`).  false: a set of lengths zlib refuses -- over-subscribed, or incomplete; the one incomplete set DEFLATE
+// allows is a literal/length or distance code (never the code-length code, which = 2) of one code of length 1, or of none.
 // *unused: code space left over, in units of 2^-15 (0 = complete code, 16384 = one code of length 1, 32768 = no code).
 __device__ bool build_table(const uint8_t *lens, u32 n, int R, u32 *table, CodeSet &cs, int which, u32 lane, int *unused = nullptr) {
     if (lane < 16u) cs.count[lane] = 0u;
@@ -138,6 +139,7 @@ __device__ bool build_table(const uint8_t *lens, u32 n, int R, u32 *table, CodeS
             left = left * 2 - (int)c;
             if (left < 0) ok = false;
         }
+        if (left > 0 && !(which != 2 && (left == 32768 || (left == 16384 && cs.count[1] == 1u)))) ok = false;
         if (unused) *unused = left;
     }
     __syncthreads();
@@ -258,6 +260,7 @@ __device__ __forceinline__ u32 read_dynamic_header(LDS &L, Reader &r, u32 lane, 
     hlit = rd_take(r, 5) + 257u;
     hdist = rd_take(r, 5) + 1u;
     const u32 hclen = rd_take(r, 4) + 4u;
+    if (hlit > 286u || hdist > 30u) return BZ_BAD_BLOCK_; // (the fields could say 288 / 32: zlib refuses, and so does the host side)
     if (lane < 32u) L.cl_lens[lane] = 0;
     __syncthreads();
     // the order the code-length code's own lengths come in: 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
@@ -643,7 +646,7 @@ __device__ u32 block_symbols_parallel(LDS &L, const uint8_t *mbase, u64 in_bits,
 
 // status[0]: 0, or (member index << 8 | reason) of a failed member (the largest such word wins)
 enum BgzfFail : u32 {
-    BZ_BAD_BLOCK = 1,  // block type 3, stored length check, code lengths that over-subscribe or repeat from nothing
+    BZ_BAD_BLOCK = 1,  // block type 3, stored length check, HLIT / HDIST above 286 / 30, code lengths that over-subscribe, leave code space unused or repeat from nothing
     BZ_BAD_CODE = 2,   // a bit pattern no code of the block's tables has, or an undefined symbol
     BZ_BAD_MATCH = 3,  // distance reaches before the member's first byte
     BZ_BAD_SIZE = 4,   // the text is not `isize` bytes long

@@ -148,11 +148,12 @@ static inline uint32_t dist_entry(int sym) {
     return ((uint32_t)DIST_BASE[sym] << 16) | K_LEN | ((uint32_t)DIST_EXTRA[sym] << 8) | DIST_EXTRA[sym];
 }
 
-// Canonical code from lengths[0, n) (RFC 1951 3.2.2) into a two-level table.  Returns false for an over-subscribed set of
-// lengths; an incomplete set leaves invalid entries behind (decoding one is an error), which covers the single-code
-// distance trees encoders do emit.
+// Canonical code from lengths[0, n) (RFC 1951 3.2.2) into a two-level table.  Returns false for the sets of lengths zlib
+// refuses: an over-subscribed one, and an incomplete one -- unless `may_be_single` (the literal/length and the distance
+// code, never the code-length code) and the set is one code of length 1, which encoders do emit for a block with one
+// distance, or no code at all (a block without matches).  Such a set leaves invalid entries behind; decoding one is an error.
 template <class EntryFn>
-static inline bool build_table(const uint8_t *lengths, int n, int primary_bits, uint32_t *table, int table_cap, EntryFn entry_of) {
+static inline bool build_table(const uint8_t *lengths, int n, int primary_bits, uint32_t *table, int table_cap, bool may_be_single, EntryFn entry_of) {
     int count[16] = {0};
     for (int i = 0; i < n; ++i) count[lengths[i]]++;
     count[0] = 0;
@@ -161,6 +162,7 @@ static inline bool build_table(const uint8_t *lengths, int n, int primary_bits, 
         left = (left << 1) - count[l];
         if (left < 0) return false; // over-subscribed
     }
+    if (left > 0 && !(may_be_single && (left == 1 << 15 || (left == 1 << 14 && count[1] == 1)))) return false; // incomplete
     uint32_t next[16];
     uint32_t code = 0;
     for (int l = 1; l <= 15; ++l) {
@@ -390,7 +392,7 @@ struct Decoder {
                 bitcnt -= 3;
             }
             uint32_t cltab[128];
-            if (!build_table(cl, 19, 7, cltab, 128, [](int s) { return ((uint32_t)s << 16) | K_LITERAL; })) return BAD;
+            if (!build_table(cl, 19, 7, cltab, 128, false, [](int s) { return ((uint32_t)s << 16) | K_LITERAL; })) return BAD;
             int i = 0;
             while (i < hlit + hdist) {
                 // (a code is <= 7 bits, its extra bits <= 7.  With fewer than 14 bits left -- the last block of a member may end
@@ -432,9 +434,9 @@ struct Decoder {
             memmove(lens + 288, lens + hlit, (size_t)hdist);
             memset(lens + hlit, 0, (size_t)(288 - hlit));
         }
-        if (!build_table(lens, hlit, LIT_BITS, lit, LIT_TABLE_MAX, litlen_entry)) return BAD;
+        if (!build_table(lens, hlit, LIT_BITS, lit, LIT_TABLE_MAX, true, litlen_entry)) return BAD;
         pair_literals(lit);
-        if (!build_table(lens + 288, hdist, DIST_BITS, dist, DIST_TABLE_MAX, dist_entry)) return BAD;
+        if (!build_table(lens + 288, hdist, DIST_BITS, dist, DIST_TABLE_MAX, true, dist_entry)) return BAD;
         state = CODES;
         return OK;
     }

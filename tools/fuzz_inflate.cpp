@@ -2,6 +2,7 @@
 // marker decode from arbitrary bit offsets, window resolution), meant to run under ASan + UBSan:
 //   g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Ifinch_rs_amd/csrc tools/fuzz_inflate.cpp -lz -o /tmp/fuzz_inflate
 //   /tmp/fuzz_inflate [iterations [seed]]
+//   /tmp/fuzz_inflate --corpus DIR      hand-made streams instead of mutated ones (tests/test_inflate_shapes_host.py dumps them)
 // Every input buffer is allocated at exactly the size the decoders are promised (payload + their padding), every output
 // buffer at exactly its capacity, so a read or write beyond either is an ASan report.  Undamaged streams must reproduce
 // the text (that is checked); damaged ones may fail in any way but a crash.
@@ -191,7 +192,68 @@ static void run_parallel(std::mt19937_64 &rng, const std::vector<uint8_t> &comp,
     }
 }
 
+static bool read_file(const std::string &path, std::vector<uint8_t> &out) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    out.clear();
+    uint8_t buf[65536];
+    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) out.insert(out.end(), buf, buf + n);
+    fclose(f);
+    return true;
+}
+
+// --corpus DIR: hand-made streams (tests/deflate_writer.py).  NAME.deflate with NAME.txt beside it must give that text through
+// all three decoders; NAME.deflate alone is a stream zlib refuses, and none of the three may accept it.
+static int run_corpus(const std::string &dir) {
+    std::vector<std::string> names;
+    {
+        const std::string cmd = "ls -1 '" + dir + "'";
+        FILE *p = popen(cmd.c_str(), "r");
+        if (!p) return 2;
+        char line[4096];
+        while (fgets(line, sizeof line, p)) {
+            std::string s(line);
+            while (!s.empty() && (s.back() == '\n' || s.back() == '\r')) s.pop_back();
+            const std::string ext = ".deflate";
+            if (s.size() > ext.size() && s.compare(s.size() - ext.size(), ext.size(), ext) == 0) names.push_back(s.substr(0, s.size() - ext.size()));
+        }
+        pclose(p);
+    }
+    std::mt19937_64 rng(1);
+    size_t n_good = 0, n_refused = 0;
+    for (const std::string &name : names) {
+        std::vector<uint8_t> comp, text;
+        if (!read_file(dir + "/" + name + ".deflate", comp)) return 2;
+        const bool good = read_file(dir + "/" + name + ".txt", text);
+        if (good) {
+            run_exact(comp, text, true);
+            for (int rep = 0; rep < 4; ++rep) run_stream(rng, comp, text, true); // (four output buffer sizes)
+            if (comp.size() > 4096)
+                for (int rep = 0; rep < 4; ++rep) run_parallel(rng, comp, text, true);
+            n_good++;
+            continue;
+        }
+        // refused: whatever size the one-shot decoder is promised, and however the output is cut up
+        const uint64_t e0 = n_exact_ok, s0 = n_stream_ok, p0 = n_par_ok;
+        for (size_t isize : {(size_t)0, (size_t)1, (size_t)100, (size_t)1000, (size_t)40000}) {
+            text.assign(isize, 0);
+            run_exact(comp, text, false);
+        }
+        for (int rep = 0; rep < 4; ++rep) run_stream(rng, comp, text, false);
+        if (comp.size() > 4096) run_parallel(rng, comp, text, false);
+        if (n_exact_ok != e0 || n_stream_ok != s0 || n_par_ok != p0) {
+            fprintf(stderr, "corpus: %s is refused by zlib and was accepted here (one-shot %d, streaming %d, parallel %d)\n", name.c_str(),
+                    (int)(n_exact_ok - e0), (int)(n_stream_ok - s0), (int)(n_par_ok - p0));
+            return 1;
+        }
+        n_refused++;
+    }
+    printf("corpus: %zu streams reproduced, %zu refused, by all three decoders\n", n_good, n_refused);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 2 && std::string(argv[1]) == "--corpus") return run_corpus(argv[2]);
     const uint64_t iters = argc > 1 ? strtoull(argv[1], nullptr, 10) : 20000;
     const uint64_t seed = argc > 2 ? strtoull(argv[2], nullptr, 10) : 1;
     std::mt19937_64 rng(seed);
