@@ -33,8 +33,8 @@
 // place.  Every partition owns the high k-mer words of its table (PART_CAP u64, Ctl::kmer_hi), the epilogue writes them as a
 // column of their own (EpiArgs::wide: 40 bytes per row) and the copy-outs decode a row's k bases from both words.  The rule
 // for "taken" is unchanged; what is new is that the collision log also receives occurrences that are no collision
-// (wide_kmer_update, fh_k2_common.h: one that raced the claimer's high word, and the 64-mers whose low word is all ones), and
-// any record sends the file the long way, where fh_finish resolves it.
+// (wide_kmer_update, fh_k2_common.h: the 64-mers with a word of all ones, the value that doubles as "not written"), and any
+// record sends the file the long way, where fh_finish resolves it.  A k-mer that repeats inside one drain leaves none.
 //
 // Mash sizes 3001..FH_BATCH_LARGE_MAX_N, k = 1..32 (fh_batch_new_large): the same handle and the same k2_batch -- which takes a
 // partition's geometry from its control block at run time -- over LARGER partitions, sized for the handle's n (geometry,

@@ -72,25 +72,34 @@ __device__ __forceinline__ void g_store(ull *p, ull v) {
 
 // K > 32 (fh_k2w.hip): the k-mer of an occurrence is two words, the table entry holds the low one, kmer_hi[slot] the
 // high one.  Which k-mer bytes a sketch reports is decided at fh_finish: the table's, unless the collision log holds a
-// record with the entry's final (smallest) position -- then that record's.  So the rule here is: the occurrence that
-// claims the entry writes both words; every other occurrence whose k-mer differs from what it can see, OR cannot be
-// compared yet (the claimer's high word has not landed; the low word is the one value that doubles as "unclaimed",
-// which only the 64-mers ...T^32 can have), logs itself if it lowered the entry's first position -- an occurrence that
-// did not is not the first one and its bytes cannot matter.
+// record with the entry's final (smallest) position -- then that record's.  So the rule here is: each word goes
+// "not written" -> value ONCE, by compare-and-swap -- the low word to the first occurrence that asks, the high word to
+// the first occurrence with that low word that finds it unwritten (the claimer of the low word or not: an occurrence of
+// the same k-mer that runs in the claimer's own drain does not wait for the claimer's high word, it writes its own, which
+// is the same) -- so the table holds the two words of ONE occurrence, and every occurrence whose k-mer differs from them
+// logs itself.  A word that is all ones doubles as "not written" (the low word of the 64-mers ...T^32, the high word of the
+// 64-mers T^32...): an occurrence that cannot tell for that reason logs itself if it lowered the entry's first position
+// -- one that did not is not the first one and its bytes cannot matter.
+// (Until the high word was a compare-and-swap too, the claimer stored it and an occurrence that read it before the store
+// landed logged itself: a k-mer met twice in one drain -- A^k in a run of A -- sent a batch file the long way.)
 __device__ __forceinline__ void wide_kmer_update(const TableRef a, Entry *e, ull *khi, u32 slot, u64 h, u64 kmer, u64 kmer_hi,
                                                  u64 pos, ull seen_kmer) {
     const bool lowered = g_fetch_min((ull *)&e->pos, (ull)pos) > (ull)pos;
     ull oldk = seen_kmer;
     if (oldk == EMPTY64) oldk = g_cas((ull *)&e->kmer, (ull)EMPTY64, (ull)kmer);
-    if (oldk == EMPTY64) {
-        g_store(&khi[slot], (ull)kmer_hi);
-        if (kmer == EMPTY64 && lowered) log_collision(a, h, kmer, pos, kmer_hi); // (the claim left the low word "unclaimed")
-    } else if (oldk != kmer) {
+    if (oldk != EMPTY64 && oldk != kmer) { // another k-mer's low word
         log_collision(a, h, kmer, pos, kmer_hi);
-    } else {
-        const ull oh = g_load(&khi[slot]);
-        if (oh != (ull)kmer_hi && (oh != EMPTY64 || lowered)) log_collision(a, h, kmer, pos, kmer_hi);
+        return;
     }
+    // the low word is this occurrence's (claimed just now, or found equal)
+    ull oh = oldk == EMPTY64 ? (ull)EMPTY64 : g_load(&khi[slot]);
+    if (oh == EMPTY64 && kmer_hi != EMPTY64) {
+        oh = g_cas(&khi[slot], (ull)EMPTY64, (ull)kmer_hi);
+        if (oh == EMPTY64) oh = kmer_hi; // (this occurrence's own, now the table's)
+    }
+    // what could not be compared: a claim that left the low word "unclaimed", a high word that reads as "not written"
+    const bool unsure = (oldk == EMPTY64 && kmer == EMPTY64) || (oh == EMPTY64 && kmer_hi == EMPTY64);
+    if (oh != (ull)kmer_hi || (unsure && lowered)) log_collision(a, h, kmer, pos, kmer_hi);
 }
 
 template <bool WIDE>

@@ -435,8 +435,9 @@ fh_batch *fh_batch_new_counts(uint32_t k, int device, uint32_t max_files, uint64
  * before the device check.  On top of a partition the handle owns the high k-mer words of its table (256 KiB per file),
  * and a result row is 40 bytes instead of 32.
  * One more way for a file to be NOT TAKEN: with two-word k-mers the collision log also receives occurrences that are no
- * collision -- one that raced the first occurrence's high word, and the 64-mers whose last 32 bases are all T -- and any
- * record sends the file through an fh_sketcher (which resolves them).  That costs time, never a wrong sketch.
+ * collision -- the 64-mers whose first or last 32 bases are all T, whose word doubles as "not written" -- and any
+ * record sends the file through an fh_sketcher (which resolves them).  That costs time, never a wrong sketch.  (A k-mer
+ * that merely repeats, however closely, leaves no record.)
  * A parked handle is handed out again by fh_batch_new_wide only. */
 fh_batch *fh_batch_new_wide(const fh_params *params, int device, uint32_t max_files, uint64_t stage_bytes);
 /* Batches of files at Mash sizes above 3000 (`mash sketch -s 10000`): 3000 < size <= FH_BATCH_LARGE_MAX_N, k = 1..32, any seed.
