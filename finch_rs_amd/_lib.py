@@ -105,6 +105,10 @@ SYMBOLS = {
     "fh_records_copy_out_records": (C.c_int, [_P, C.c_int, C.c_uint32, _P, _P]),
     "fh_records_kernel_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P, _U64P]),
     "fh_records_counters": (C.c_int, [_P, _U64P, _U64P]),
+    "fh_records_new_stream": (_P, [C.POINTER(FhParams), C.c_int, C.c_uint32, C.c_uint64]),
+    "fh_records_max_positions_of": (C.c_uint32, [_P]),
+    "fh_records_stream_cap": (C.c_uint32, []),
+    "fh_records_stream_folds": (C.c_uint64, [_P]),
     "fh_set_profiling": (C.c_int, [_P, C.c_int]),
     "fh_kernel_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P, _U64P]),
     "fh_debug_counters": (C.c_int, [_P, _U64P, _U64P, _U64P]),

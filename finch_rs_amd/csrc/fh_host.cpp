@@ -4340,6 +4340,9 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
 // handle in the two-bit form, side by side with the others of its group, and sketched in a workgroup's LDS -- one launch per
 // group, while the worker packs the next group into the other slot.  Every other record, and every record the device reports as
 // not taken, goes one by one through sketch_stream over its own text: the contract's right-hand side, exact for any parameters.
+// With the option records_stream a worker owns a second handle, of the streamed form (fh_records_new_stream), and packs into it
+// the records rplan::route3 sends there -- longer than the LDS form takes, no longer than records_stream_max_pos; the two
+// handles fill, launch and are collected independently, and a result is placed by its record's index in the call either way.
 // ---------------------------------------------------------------------------------------------
 namespace {
 
@@ -4348,6 +4351,8 @@ namespace rp = fh::rplan;
 struct RecordsStats {
     uint64_t records = 0, in_lds = 0, one_by_one = 0, launches = 0;
     double kernel_ms = 0;
+    uint64_t streamed = 0, stream_launches = 0; // (of in_lds / launches / kernel_ms: the streamed form's share)
+    double stream_kernel_ms = 0;
 };
 thread_local RecordsStats g_records_stats;
 
@@ -4371,7 +4376,11 @@ struct RecordsCall {
     uint64_t group_n = 0;
     uint32_t handle_records = 1; // the sizes the workers' handles are made for
     uint64_t handle_stage = 4096;
-    std::atomic<uint64_t> in_lds{0}, one_by_one{0}, launches{0}, kernel_us{0};
+    bool stream_on = false; // the option records_stream
+    uint64_t stream_max_pos = 0;
+    uint32_t stream_records = 1; // ... and the stream handles'
+    uint64_t stream_stage = 4096;
+    std::atomic<uint64_t> in_lds{0}, one_by_one{0}, launches{0}, kernel_us{0}, streamed{0}, stream_launches{0}, stream_kernel_us{0};
     std::mutex err_mu;
     int first_err_code = FH_OK;
     uint64_t first_err_idx = UINT64_MAX;
@@ -4399,29 +4408,35 @@ public:
         handles_.full = full;
         handles_.final_size = call.sp.final_size;
         handles_.device = device;
+        lanes_[1].stream = true;
     }
     ~RecordWorker() {
-        if (h_) fh_records_free(h_); // (left by an exception only)
+        for (Lane &l : lanes_)
+            if (l.h) fh_records_free(l.h); // (left by an exception only)
     }
 
     void take(uint64_t j) {
         const rp::Record &r = c_.recs[j].r;
-        if (rp::route(c_.sp.kind, c_.sp.kmer_length, r.positions, c_.lds_on) == rp::Route::OneByOne || !stage(j)) one_by_one(j);
+        const rp::Route3 rt = rp::route3(c_.sp.kind, c_.sp.kmer_length, r.positions, c_.lds_on, c_.stream_on, c_.stream_max_pos, c_.group_n);
+        if (rt == rp::Route3::OneByOne || !stage(lanes_[rt == rp::Route3::Stream ? 1 : 0], j)) one_by_one(j);
     }
 
     void finish() {
-        if (!h_) return;
-        submit_cur();
-        collect(0);
-        collect(1);
-        double ms = 0;
-        uint64_t nl = 0;
-        if (fh_records_kernel_time(h_, &ms, &nl, nullptr) == FH_OK) {
-            c_.kernel_us += (uint64_t)(ms * 1000.0 + 0.5);
-            c_.launches += nl;
+        for (Lane &l : lanes_) {
+            if (!l.h) continue;
+            submit_cur(l);
+            collect(l, 0);
+            collect(l, 1);
+            double ms = 0;
+            uint64_t nl = 0;
+            if (fh_records_kernel_time(l.h, &ms, &nl, nullptr) == FH_OK) {
+                c_.kernel_us += (uint64_t)(ms * 1000.0 + 0.5);
+                c_.launches += nl;
+                if (l.stream) c_.stream_kernel_us += (uint64_t)(ms * 1000.0 + 0.5), c_.stream_launches += nl;
+            }
+            fh_records_free(l.h);
+            l.h = nullptr;
         }
-        fh_records_free(h_);
-        h_ = nullptr;
     }
 
 private:
@@ -4434,6 +4449,16 @@ private:
             fill = rows = 0;
         }
     };
+    // a handle and the two groups that alternate through its slots: lanes_[0] the LDS form, lanes_[1] the streamed form
+    struct Lane {
+        bool stream = false;
+        fh_records *h = nullptr;
+        bool failed = false;
+        Group grp[2];
+        int cur = 0;
+        uint8_t *stage[2] = {nullptr, nullptr};
+        uint64_t stage_cap = 0, rows_cap = 0;
+    };
 
     void one_by_one(uint64_t j) { // the record's own text through its own sketcher (sketch_stream, lib.rs:51-94)
         const RecordRef &q = c_.recs[j];
@@ -4445,35 +4470,37 @@ private:
         c_.one_by_one++;
     }
 
-    bool open_handle() {
+    bool open_handle(Lane &l) {
         fh_params bp = to_fh(c_.sp, 0);
         bp.size = c_.group_n;
-        h_ = fh_records_new(&bp, handles_.device, c_.handle_records, c_.handle_stage);
-        if (h_ && (fh_records_stage(h_, 0, &stage_[0], &stage_cap_) != FH_OK || fh_records_stage(h_, 1, &stage_[1], &stage_cap_) != FH_OK)) {
-            fh_records_free(h_);
-            h_ = nullptr;
+        l.h = l.stream ? fh_records_new_stream(&bp, handles_.device, c_.stream_records, c_.stream_stage) : fh_records_new(&bp, handles_.device, c_.handle_records, c_.handle_stage);
+        if (l.h && (fh_records_stage(l.h, 0, &l.stage[0], &l.stage_cap) != FH_OK || fh_records_stage(l.h, 1, &l.stage[1], &l.stage_cap) != FH_OK)) {
+            fh_records_free(l.h);
+            l.h = nullptr;
         }
-        if (!h_) {
-            failed_ = true; // (no memory for it, say: every record one by one)
+        if (!l.h) {
+            l.failed = true; // (no memory for it, say: every record one by one)
             return false;
         }
-        rows_cap_ = fh_records_rows_cap(h_);
+        l.rows_cap = fh_records_rows_cap(l.h);
         return true;
     }
 
-    bool stage(uint64_t j) { // true: record j is part of the current group
-        if (failed_ || (!h_ && !open_handle())) return false;
+    bool stage(Lane &l, uint64_t j) { // true: record j is part of the lane's current group
+        if (l.failed || (!l.h && !open_handle(l))) return false;
         const RecordRef &q = c_.recs[j];
         const uint64_t need = rp::region_bytes(q.r.positions);
-        const uint64_t rows = rp::row_bound(c_.sp.kind, c_.group_n, c_.sp.kmer_length, q.r.positions);
-        if (need > stage_cap_ || rows > rows_cap_) return false;
-        if (grp_[cur_].idx.size() >= c_.handle_records || grp_[cur_].fill + need > stage_cap_ || grp_[cur_].rows + rows > rows_cap_) submit_cur();
-        Group &g = grp_[cur_];
+        const uint64_t rows = l.stream ? rp::stream_row_bound(c_.sp.kind, c_.group_n, c_.sp.kmer_length, q.r.positions)
+                                       : rp::row_bound(c_.sp.kind, c_.group_n, c_.sp.kmer_length, q.r.positions);
+        const uint32_t max_records = l.stream ? c_.stream_records : c_.handle_records;
+        if (need > l.stage_cap || rows > l.rows_cap) return false;
+        if (l.grp[l.cur].idx.size() >= max_records || l.grp[l.cur].fill + need > l.stage_cap || l.grp[l.cur].rows + rows > l.rows_cap) submit_cur(l);
+        Group &g = l.grp[l.cur];
         if (!packer_) {
             packer_.reset(new fh_pack2::Packer);
             packer_->force_form((unsigned)cfg_u64("pack_scalar", 0));
         }
-        packer_->begin(stage_[cur_] + g.fill);
+        packer_->begin(l.stage[l.cur] + g.fill);
         packer_->text(c_.text(q) + q.r.seq0, (size_t)(q.r.text1 - q.r.seq0));
         if (packer_->finish() != q.r.positions) return false; // (cannot happen: split_records counts what the packer keeps)
         g.idx.push_back(j);
@@ -4484,27 +4511,27 @@ private:
         return true;
     }
 
-    void submit_cur() { // hand the current group to the device, go on in the other slot (its previous group collected)
-        Group &g = grp_[cur_];
+    void submit_cur(Lane &l) { // hand the current group to the device, go on in the other slot (its previous group collected)
+        Group &g = l.grp[l.cur];
         if (g.idx.empty()) return;
-        if (fh_records_submit_packed(h_, cur_, g.off.data(), g.len.data(), (uint32_t)g.idx.size()) != FH_OK) {
+        if (fh_records_submit_packed(l.h, l.cur, g.off.data(), g.len.data(), (uint32_t)g.idx.size()) != FH_OK) {
             for (uint64_t j : g.idx) one_by_one(j);
             g.clear();
             return;
         }
         g.in_flight = true;
-        cur_ ^= 1;
-        collect(cur_);
+        l.cur ^= 1;
+        collect(l, l.cur);
     }
 
-    void collect(int slot) { // wait for the group in `slot`, turn its results into Sketches
-        Group &g = grp_[slot];
+    void collect(Lane &l, int slot) { // wait for the group in `slot`, turn its results into Sketches
+        Group &g = l.grp[slot];
         if (!g.in_flight) return;
         g.in_flight = false;
         const finch_sketch_params &sp = c_.sp;
         const bool whole_rows = sp.kind == 1; // Scaled: no cut to final_size, no strict error (mod.rs:115-128)
         status_.assign(g.idx.size() + 1, 1);
-        const int rc = fh_records_wait(h_, slot, status_.data());
+        const int rc = fh_records_wait(l.h, slot, status_.data());
         const uint32_t k = sp.kmer_length;
         for (size_t i = 0; i < g.idx.size(); ++i) {
             const uint64_t j = g.idx[i];
@@ -4513,16 +4540,17 @@ private:
                 continue;
             }
             uint64_t n = 0, tk = 0;
-            int r2 = fh_records_result(h_, slot, (uint32_t)i, &n, &tk);
+            int r2 = fh_records_result(l.h, slot, (uint32_t)i, &n, &tk);
             const size_t keep = whole_rows ? (size_t)n : (size_t)std::min<uint64_t>(n, sp.final_size); // process_post_filter
             recs_.resize(n + 1);
             km_.resize(n * (size_t)k + 1);
-            if (r2 == FH_OK) r2 = fh_records_copy_out_records(h_, slot, (uint32_t)i, recs_.data(), km_.data());
+            if (r2 == FH_OK) r2 = fh_records_copy_out_records(l.h, slot, (uint32_t)i, recs_.data(), km_.data());
             if (r2 != FH_OK) {
                 c_.record_error(j, r2, fh_last_error());
                 continue;
             }
             c_.in_lds++;
+            if (l.stream) c_.streamed++;
             const RecordRef &q = c_.recs[j];
             Sketch &out = c_.out[j];
             out.name = c_.name_of(q, &out.comment);
@@ -4545,12 +4573,7 @@ private:
 
     RecordsCall &c_;
     HandleSet handles_;
-    fh_records *h_ = nullptr;
-    bool failed_ = false;
-    Group grp_[2];
-    int cur_ = 0;
-    uint8_t *stage_[2] = {nullptr, nullptr};
-    uint64_t stage_cap_ = 0, rows_cap_ = 0;
+    Lane lanes_[2];
     std::vector<uint8_t> status_, km_;
     std::vector<fh_kmer_count> recs_;
     std::unique_ptr<fh_pack2::Packer> packer_;
@@ -4618,6 +4641,17 @@ int sketch_records_core(const std::vector<RecordsInput> &inputs, const finch_ske
     // (... rounded up to powers of two, so that calls of about one size find each other's parked handles)
     call.handle_records = (uint32_t)std::min<uint64_t>(rp::GROUP_RECORDS, rp::pow2_at_least(std::max<uint64_t>(16, lds_records)));
     call.handle_stage = std::min<uint64_t>(rp::GROUP_STAGE, rp::pow2_at_least(std::max<uint64_t>(64u << 10, lds_bytes)));
+    // ... and the stream handles, if the option asks for them (off: route3 is route, and nothing below differs from it)
+    call.stream_on = cfg_u64("records_stream", 0) != 0;
+    call.stream_max_pos = std::min<uint64_t>(cfg_u64("records_stream_max_pos", rp::STREAM_DEFAULT_MAX_POS), rp::STREAM_MAX_POS);
+    if (call.stream_on) {
+        uint64_t n = 0, bytes = 0;
+        for (const RecordRef &q : recs)
+            if (rp::route3(sp->kind, sp->kmer_length, q.r.positions, call.lds_on, true, call.stream_max_pos, call.group_n) == rp::Route3::Stream)
+                n++, bytes += rp::region_bytes(q.r.positions) + 64;
+        call.stream_records = (uint32_t)std::min<uint64_t>(rp::STREAM_GROUP_RECORDS, rp::pow2_at_least(std::max<uint64_t>(16, n)));
+        call.stream_stage = std::min<uint64_t>(rp::STREAM_GROUP_STAGE, rp::pow2_at_least(std::max<uint64_t>(64u << 10, bytes)));
+    }
     // records are dealt in runs: long enough that a worker's groups fill, short enough that every worker gets some
     if (n_threads == 0) n_threads = std::min<uint32_t>(16u, std::max<uint32_t>(4u, usable_cpus() / (uint32_t)devs.size())) * (uint32_t)devs.size();
     const uint64_t total = recs.size();
@@ -4659,6 +4693,9 @@ int sketch_records_core(const std::vector<RecordsInput> &inputs, const finch_ske
     g_records_stats.one_by_one = call.one_by_one;
     g_records_stats.kernel_ms = (double)call.kernel_us / 1000.0;
     g_records_stats.launches = call.launches;
+    g_records_stats.streamed = call.streamed;
+    g_records_stats.stream_kernel_ms = (double)call.stream_kernel_us / 1000.0;
+    g_records_stats.stream_launches = call.stream_launches;
     *out = res.release();
     return FH_OK;
 }
@@ -4700,6 +4737,14 @@ int finch_sketch_records_stats(uint64_t *records, uint64_t *in_lds, uint64_t *on
     if (one_by_one) *one_by_one = s.one_by_one;
     if (kernel_ms) *kernel_ms = s.kernel_ms;
     if (launches) *launches = s.launches;
+    return FH_OK;
+}
+
+int finch_sketch_records_stream_stats(uint64_t *streamed, double *kernel_ms, uint64_t *launches) {
+    const RecordsStats &s = g_records_stats;
+    if (streamed) *streamed = s.streamed;
+    if (kernel_ms) *kernel_ms = s.stream_kernel_ms;
+    if (launches) *launches = s.stream_launches;
     return FH_OK;
 }
 

@@ -106,6 +106,9 @@ const OptDef DEFS[] = {
     {"merge_chunk_records", "accumulator records per merge launch, at most 2^31 (default 4 M; tests: many launches)"},
     // --- finch_sketch_records ---
     {"records_lds", "1 (the default): finch_sketch_records sketches the records the record sketcher serves in a workgroup's LDS, many per launch; 0: every record one by one through its own sketcher (tests, A/B)"},
+    {"records_stream", "1: finch_sketch_records streams a record of more than 8192 positions through one workgroup (the streamed record sketcher: Mash up to 1024 hashes, Scaled, k <= 32), many per launch; 0 (the default): such a record goes one by one through its own sketcher"},
+    {"records_stream_max_pos", "positions of the longest record records_stream=1 streams, at most 2^24 (default 200000: the largest measured length at which streaming was not slower, docs/MEASUREMENTS_records_stream.md)"},
+    {"records_stream_fold", "the streamed record sketcher folds its pending keys into the running list whenever at least this many are pending behind a round, read when a handle is made (default 0: only when the key array could not take another round; tests: 1 = a fold after every round)"},
 };
 constexpr int N_OPTS = (int)(sizeof(DEFS) / sizeof(DEFS[0]));
 

@@ -111,6 +111,77 @@ inline uint64_t group_n(uint32_t kind, uint64_t kmers_to_sketch, uint64_t final_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// The STREAMED record sketcher (fh_records_new_stream, k_record_stream of fh_records.hip): a record of any length up to
+// STREAM_MAX_POS goes through one workgroup piece by piece; what survives the falling threshold is folded into a running
+// sorted list of at most STREAM_CAP distinct hashes in LDS.  Of the 128 KiB the tables and tile rings leave a workgroup, the key
+// array takes 96 KiB (8192 keys of 8 + 4 bytes: STREAM_CAP list entries and the 4096 keys eight waves may append between two
+// decision points need more than 4096, and the sort wants a power of two) and the list's side arrays 24 KiB (position | strand,
+// count and reverse-strand count, 12 bytes an entry, twice: a fold reads the old list while it writes the new one).  An entry
+// names its k-mer by a position of the record, not by the k-mer's word: with the word (16 bytes an entry, twice) the list would
+// end at 1024 entries with nothing to spare, and the word is read once per kept row.  The compiler agrees (fh_records.hip).
+constexpr uint32_t STREAM_CAP = 1024;
+// A payload's top bit tells a list entry from a window, the next one is the strand, so a position has 30 bits; the bound is
+// lower still: a 16 Mi-position record keeps ONE workgroup busy for tens of milliseconds, by then a sketcher of its own (every
+// CU on that record) is the faster route.
+constexpr uint32_t STREAM_MAX_POS = 1u << 24;
+static_assert(STREAM_MAX_POS <= (1u << 30), "a window's payload: 30 bits of position, the strand, the list flag");
+
+// What fh_records_new_stream says: check()'s rules, then the one of its own.
+inline Verdict check_stream(const fh_params *p, uint32_t max_records, uint64_t stage_bytes) {
+    const Verdict v = check(p, max_records, stage_bytes);
+    if (v.code != FH_OK) return v;
+    if (p->kind == FH_KIND_MASH && p->size > STREAM_CAP)
+        return refuse(FH_ERR_UNSUPPORTED, "the streamed record sketcher keeps at most %u hashes of a record in LDS: a Mash sketch of %llu goes through an fh_sketcher",
+                      STREAM_CAP, (unsigned long long)p->size);
+    return Verdict{};
+}
+
+// Rows of a record on a stream handle: a Scaled record's kept list is bounded by STREAM_CAP (beyond: not taken)
+inline uint64_t stream_row_bound(uint32_t kind, uint64_t size, uint32_t k, uint64_t positions) {
+    const uint64_t w = windows(positions, k);
+    return kind == FH_KIND_MASH ? std::min(size, w) : std::min<uint64_t>(w, STREAM_CAP);
+}
+inline uint64_t stream_assign_rows(uint32_t kind, uint64_t size, uint32_t k, const uint64_t *positions, uint32_t n, uint64_t *row0) {
+    uint64_t sum = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+        row0[j] = sum;
+        sum += positions[j] > STREAM_MAX_POS ? 0 : stream_row_bound(kind, size, k, positions[j]);
+    }
+    return sum;
+}
+// The sizes of a stream handle that passed check_stream(): no record has more than STREAM_CAP rows, whatever the stage holds
+inline Geometry stream_geometry(const fh_params &p, uint32_t max_records, uint64_t stage_bytes) {
+    Geometry g;
+    g.header_bytes = ((uint64_t)max_records * DESC_BYTES + 4095) & ~4095ull;
+    g.data_bytes = bplan::stage_rounded(stage_bytes);
+    const uint64_t per_record = p.kind == FH_KIND_MASH ? std::min<uint64_t>(p.size, STREAM_CAP) : STREAM_CAP;
+    g.rows_cap = std::max<uint64_t>(STREAM_CAP, std::min<uint64_t>(ROWS_BUDGET, (uint64_t)max_records * per_record));
+    return g;
+}
+
+// finch_sketch_records' stream handles.  Long records are few and large: a 1 Mi-position record occupies 394 KB staged, so
+// 8 MiB hold about 20 of them -- fewer than the CUs, so a group of such records never queues two on a workgroup -- while
+// 50 kb records (19 968 bytes staged) come 420 to a group, under two per CU.  A group closes at 512 records: beyond that a
+// launch only grows longer, and the other slot waits.
+constexpr uint64_t STREAM_GROUP_STAGE = 8ull << 20;
+constexpr uint32_t STREAM_GROUP_RECORDS = 512;
+// records_stream_max_pos when it is not set: the largest measured length at which streaming was not slower than one by one
+// (docs/MEASUREMENTS_records_stream.md: ahead at 50 kb and 200 kb, behind at 1 Mb and 5 Mb)
+constexpr uint64_t STREAM_DEFAULT_MAX_POS = 200000;
+
+// The route of a record with the streamed sketcher beside the LDS one.  stream_on: the option records_stream; stream_max_pos:
+// records_stream_max_pos, capped by STREAM_MAX_POS; group_n: the size the handles are made for.  With stream_on false this is
+// route(), name for name.
+enum class Route3 { Lds, Stream, OneByOne };
+inline Route3 route3(uint32_t kind, uint32_t k, uint64_t positions, bool lds_on, bool stream_on, uint64_t stream_max_pos, uint64_t group_n) {
+    if (route(kind, k, positions, lds_on) == Route::Lds) return Route3::Lds;
+    const bool served = (kind == FH_KIND_MASH || kind == FH_KIND_SCALED) && k >= 1 && k <= 32;
+    const uint64_t bound = std::min<uint64_t>(stream_max_pos, STREAM_MAX_POS);
+    const bool fits = kind != FH_KIND_MASH || (group_n >= 1 && group_n <= STREAM_CAP);
+    return stream_on && served && fits && positions > MAX_POS && positions <= bound ? Route3::Stream : Route3::OneByOne;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // The header rule.  h[0, n): a header line behind its '>' and without its line end.  The name is what stands in front of the
 // first blank or tab, the comment what follows that run of blanks and tabs (empty if nothing does).
 struct HeaderSplit {

@@ -71,6 +71,7 @@ _SYMS = {
                                               C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
     "finch_sketch_records_stats": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                              C.POINTER(C.c_uint64)]),
+    "finch_sketch_records_stream_stats": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "finch_sketch_file_sharded": (C.c_int, [C.c_char_p, C.POINTER(CSketchParams), C.POINTER(CFilterParams), C.POINTER(C.c_int),
                                             C.c_uint32, C.c_uint64, C.POINTER(_P)]),
     "finch_sketch_buffer_sharded": (C.c_int, [_P, C.c_uint64, C.c_char_p, C.POINTER(CSketchParams), C.POINTER(CFilterParams),
@@ -360,7 +361,7 @@ def sketch_files(filenames: Sequence[str], sketch_params: SketchParams, filters:
 def sketch_records(inputs, sketch_params: SketchParams, filters: Optional[FilterParams] = None, devices: Sequence[int] = (0,),
                    n_threads: int = 0, stats: Optional[dict] = None) -> Sketches:
     """one Sketch per record of FASTA inputs (finch_sketch_records): `inputs` is a path, a sequence of paths, or the bytes of
-    one input; `stats`, if given, receives records / in_lds / one_by_one / kernel_ms / launches of this call"""
+    one input; `stats`, if given, receives records / in_lds / one_by_one / kernel_ms / launches / streamed of this call"""
     if filters is None:
         dflt = CFilterParams()
         lib().finch_default_filter_params(C.byref(dflt))
@@ -381,7 +382,16 @@ def sketch_records(inputs, sketch_params: SketchParams, filters: Optional[Filter
         a, b, c, ms, nl = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double(), C.c_uint64()
         _check(lib().finch_sketch_records_stats(C.byref(a), C.byref(b), C.byref(c), C.byref(ms), C.byref(nl)))
         stats.update(records=a.value, in_lds=b.value, one_by_one=c.value, kernel_ms=ms.value, launches=nl.value)
+        stats.update(streamed=records_stream_stats()[0])
     return res
+
+
+def records_stream_stats():
+    """(streamed records, the streamed kernel's milliseconds, its launches) of this thread's last sketch_records call
+    (finch_sketch_records_stream_stats)"""
+    a, ms, nl = C.c_uint64(), C.c_double(), C.c_uint64()
+    _check(lib().finch_sketch_records_stream_stats(C.byref(a), C.byref(ms), C.byref(nl)))
+    return a.value, ms.value, nl.value
 
 
 def sketch_stream(data: bytes, name: str, sketch_params: SketchParams, filters: FilterParams, device: int = 0) -> Sketches:

@@ -420,19 +420,24 @@ class RecordSketcher:
     positions is hashed, sorted, folded into counts and cut to its sketch in ONE workgroup's LDS, exactly.  Mash (size >= 1) or
     Scaled (kind=KIND_SCALED, any size, scale in (0, 1]), k <= 32, any seed.
     `sketch_many(blocks)` -> per block (a packed one-record stream) either (records, kmers, total_kmers) or None ("not taken":
-    longer than `max_positions`, a 64-bit collision, or a hash of 2^64 - 1 -- sketch that block through a HipSketcher)."""
+    longer than `max_positions`, a 64-bit collision, or a hash of 2^64 - 1 -- sketch that block through a HipSketcher).
+    `stream=True`: the streamed form (fh_records_new_stream) -- records up to its own, far larger `max_positions` go through a
+    workgroup piece by piece, a running list of at most `stream_cap` hashes in LDS; a Mash size above `stream_cap` is refused,
+    a Scaled record that keeps more hashes than that is not taken."""
 
     def __init__(self, size: int, kmer_length: int, seed: int = 0, device: int = 0, max_records: int = 1024,
-                 stage_bytes: int = 8 << 20, kind: int = KIND_MASH, scale: float = 0.0):
+                 stage_bytes: int = 8 << 20, kind: int = KIND_MASH, scale: float = 0.0, stream: bool = False):
         self._L = _lib.load()
         self.size, self.kmer_length, self.seed, self.device = size, kmer_length, seed, device
         self.max_records = max_records
-        self.kind, self.scale = kind, scale
-        self.max_positions = int(self._L.fh_records_max_positions())
+        self.kind, self.scale, self.stream = kind, scale, stream
+        self.stream_cap = int(self._L.fh_records_stream_cap())
         p = FhParams(kind, kmer_length, size, seed, scale, 0, 0, 0)
-        self._h = self._L.fh_records_new(C.byref(p), device, max_records, stage_bytes)
+        new = self._L.fh_records_new_stream if stream else self._L.fh_records_new
+        self._h = new(C.byref(p), device, max_records, stage_bytes)
         if not self._h:
             raise FinchHipError(-1, (self._L.fh_last_error() or b"").decode(errors="replace"))
+        self.max_positions = int(self._L.fh_records_max_positions_of(self._h))
         self.rows_cap = int(self._L.fh_records_rows_cap(self._h))
 
     def close(self):
@@ -462,7 +467,13 @@ class RecordSketcher:
         if n_positions > self.max_positions:
             return 0
         w = max(0, n_positions - self.kmer_length + 1)
-        return min(self.size, w) if self.kind == KIND_MASH else w
+        if self.kind == KIND_MASH:
+            return min(self.size, w)
+        return min(w, self.stream_cap) if self.stream else w
+
+    def folds(self) -> int:
+        """folds of the streamed form over the records taken since the handle was made (measurement)"""
+        return int(self._L.fh_records_stream_folds(self._h))
 
     def submit(self, slot: int, offsets, lens) -> None:
         o = np.ascontiguousarray(offsets, dtype=np.uint64)

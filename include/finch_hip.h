@@ -102,7 +102,10 @@ const char *fh_last_error(void);
  * finch_host.h and the option index_cluster_margin;
  * 21: fh_batch_new_wide and the rest of 20 unchanged, plus the record sketcher (fh_records_new and the fh_records_* functions
  * below), finch_sketch_records, finch_sketch_records_buffer and finch_sketch_records_stats in finch_host.h and the option
- * records_lds) */
+ * records_lds; additions that change nothing of 21: fh_records_new_stream, fh_records_max_positions_of, fh_records_stream_cap,
+ * fh_records_stream_folds,
+ * finch_sketch_records_stream_stats in finch_host.h and the options records_stream, records_stream_max_pos,
+ * records_stream_fold) */
 #define FH_ABI_VERSION 21
 int fh_abi_version(void);
 
@@ -502,6 +505,22 @@ int fh_records_result(fh_records *r, int slot, uint32_t i, uint64_t *n_out, uint
 int fh_records_copy_out_records(fh_records *r, int slot, uint32_t i, fh_kmer_count *records, uint8_t *kmers);
 int fh_records_kernel_time(fh_records *r, double *total_ms, uint64_t *launches, uint64_t *positions);
 int fh_records_counters(fh_records *r, uint64_t *taken, uint64_t *not_taken);
+/* The STREAMED form of the record sketcher: records of any length up to fh_records_max_positions_of(handle) (2^24 on such a
+ * handle, 8192 on one of fh_records_new).  A workgroup hashes the record piece by piece, drops every hash above a threshold
+ * that only falls -- the size-th smallest distinct hash so far, for a Scaled sketch never below max_hash -- and folds what
+ * survives into a running sorted list of at most fh_records_stream_cap() distinct hashes in its LDS: exact, like the form above,
+ * and served by the same verbs.  What differs:
+ *   fh_records_new_stream refuses (FH_ERR_UNSUPPORTED) a Mash size above fh_records_stream_cap();
+ *   NOT TAKEN also: a Scaled record whose kept hashes outgrow fh_records_stream_cap();
+ *   a record's rows in a submit are min(size, positions - k + 1) [Mash] and min(positions - k + 1, fh_records_stream_cap())
+ *   [Scaled];
+ *   the records of a submit are dealt to the workgroups one at a time, so they may differ in length by orders of magnitude.
+ * The option records_stream_fold (read by fh_records_new_stream) makes a workgroup fold earlier than it must (tests);
+ * fh_records_stream_folds: the folds of the records taken since fh_records_new_stream (measurement). */
+fh_records *fh_records_new_stream(const fh_params *params, int device, uint32_t max_records, uint64_t stage_bytes);
+uint32_t fh_records_max_positions_of(fh_records *r);
+uint32_t fh_records_stream_cap(void);
+uint64_t fh_records_stream_folds(fh_records *r);
 
 /* --- measurement support (bench.py) --- */
 /* when enabled, every sketch-kernel launch is bracketed by HIP events on the handle's stream */

@@ -86,7 +86,12 @@ int finch_sketch_files(const char *const *filenames, uint32_t n_files, const fin
  * the error finch_sketch_files gives for it.
  * finch_sketch_records_stats: the last call of the calling thread -- its records, how many were sketched in LDS and how many
  * one by one (in_lds + one_by_one == records), the record kernel's event-measured milliseconds and its launches (any pointer
- * may be NULL). */
+ * may be NULL).
+ * With the option records_stream = 1 (default 0) a record of more than FH_RECORDS_MAX_POS and no more than
+ * records_stream_max_pos positions goes through the streamed record sketcher (fh_records_new_stream: Mash up to
+ * fh_records_stream_cap() hashes, Scaled, kmer_length <= 32) instead of one by one; such records count in in_lds, and
+ * kernel_ms / launches cover both kernels.  finch_sketch_records_stream_stats: the streamed records of the calling thread's last
+ * call, the streamed kernel's milliseconds and its launches. */
 int finch_sketch_records(const char *const *filenames, uint32_t n_files, const finch_sketch_params *sketch_params,
                          const finch_filter_params *filters, const int *devices, uint32_t n_devices, uint32_t n_threads,
                          finch_sketches **out);
@@ -94,6 +99,7 @@ int finch_sketch_records_buffer(const uint8_t *data, uint64_t len, const finch_s
                                 const finch_filter_params *filters, const int *devices, uint32_t n_devices, uint32_t n_threads,
                                 finch_sketches **out);
 int finch_sketch_records_stats(uint64_t *records, uint64_t *in_lds, uint64_t *one_by_one, double *kernel_ms, uint64_t *launches);
+int finch_sketch_records_stream_stats(uint64_t *streamed, double *kernel_ms, uint64_t *launches);
 /* sketch_stream over an in-memory file image */
 int finch_sketch_buffer(const uint8_t *data, uint64_t len, const char *name, const finch_sketch_params *sketch_params,
                         const finch_filter_params *filters, int device, finch_sketches **out);

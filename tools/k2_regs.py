@@ -3,6 +3,7 @@
 
     python tools/k2_regs.py                 # every K = 1..64 as the library is built (table -> stdout)
     python tools/k2_regs.py --objects       # the same from the objects the shipped library was linked from (csrc/obj/*.o)
+    python tools/k2_regs.py --records       # the record sketcher's kernels (k_record_sketch, k_record_stream) from csrc/obj/fh_records_*.o
     python tools/k2_regs.py --k 31 [--asm out.s] [--flags "..."] [-D NAME=V ...]   # one K, development build
 
 Prints per kernel: VGPRs, spilled VGPRs, scratch bytes per lane, SGPRs, LDS bytes (llvm-readelf --notes of the unbundled
@@ -105,6 +106,9 @@ def pretty(name):
     m = re.match(r"_ZN2fh12k2_sketch_wsILi(\d+)EEE", name)
     if m:
         return "k2_sketch_ws<%s>" % m.group(1)
+    m = re.match(r"_ZN2fh\d+(k_record_\w+?)ILi(\d+)ELb(\d)EEE", name)
+    if m:
+        return "%s<%s,%s>" % (m.group(1), m.group(2), "S0" if m.group(3) == "1" else "--")
     m = re.match(r"_ZN2fh11k2_sketch_wILi(\d+)EEE", name)
     if m:
         return "k2_sketch_w<%s>" % m.group(1)
@@ -124,6 +128,7 @@ def main():
     ap.add_argument("-D", action="append", default=[])
     ap.add_argument("--all-variants", action="store_true", help="list the masked / seeded / re-read variants too")
     ap.add_argument("--objects", action="store_true", help="read finch_rs_amd/csrc/obj/fh_k2*.o (what libfinch_hip.so was linked from) instead of compiling")
+    ap.add_argument("--records", action="store_true", help="the record sketcher's kernels from finch_rs_amd/csrc/obj/fh_records_*.o: any spill fails")
     ap.add_argument("--seg", action="store_true", help="the segment form of the kernel (fh_k2s.hip) instead of fh_k2.hip")
     ap.add_argument("--mix", action="store_true", help="with --k: VALU instruction classes per position of the hot loop (static, from the ISA)")
     args = ap.parse_args()
@@ -131,7 +136,14 @@ def main():
     rows = []
     if args.k is not None and args.mix and not args.asm:
         args.asm = os.path.join(tempfile.mkdtemp(prefix="k2mix_"), "k.s")
-    if args.objects:
+    if args.records:
+        import glob
+        objs = sorted(glob.glob(os.path.join(CSRC, "obj", "fh_records_*.o")))
+        if len(objs) != B.NPARTS:
+            sys.exit("expected %d record-sketcher objects under csrc/obj, found %d: build the library first" % (B.NPARTS, len(objs)))
+        for o in objs:
+            rows += unbundle_object(o)
+    elif args.objects:
         import glob
         objs = sorted(glob.glob(os.path.join(CSRC, "obj", "fh_k2_*.o")) + glob.glob(os.path.join(CSRC, "obj", "fh_k2w_*.o")) +
                       glob.glob(os.path.join(CSRC, "obj", "fh_k2s_*.o")) + glob.glob(os.path.join(CSRC, "obj", "fh_k2ws_*.o")) +
@@ -152,8 +164,8 @@ def main():
         with ThreadPoolExecutor(max_workers=4) as ex:
             for r in ex.map(lambda j: compile_one(*j), jobs):
                 rows += r
-    rows = [r for r in rows if "k2_sketch" in r["name"] or "k2_batch" in r["name"]]
-    if not args.all_variants:
+    rows = [r for r in rows if "k2_sketch" in r["name"] or "k2_batch" in r["name"] or (args.records and "k_record_" in r["name"])]
+    if not args.all_variants and not args.records:
         rows = [r for r in rows if "k2_sketch_w" in r["name"] or "k2_sketch_seg" in r["name"] or "k2_batch" in r["name"] or "ELb0ELb1ELb0E" in r["name"]]
 
     def key(r):
