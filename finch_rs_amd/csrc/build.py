@@ -45,7 +45,7 @@ if "FH_OUT" in os.environ:  # an A/B build: its objects must not replace those l
 K2WS_FLAGS = os.environ["FH_K2WS_FLAGS"].split() if "FH_K2WS_FLAGS" in os.environ else ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # ... and the two-word tile kernels: k = 33 / 48 / 64 +3.2 / 2.9 / 3.7 % (FH_NO_SEG=1, profiles/r05W_ab_k2ws_sched.txt), no spills
 K2W_FLAGS = os.environ["FH_K2W_FLAGS"].split() if "FH_K2W_FLAGS" in os.environ else ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
-SOURCES = ["fh_core.h", "fh_device.h", "fh_kernels.h", "fh_k2_common.h", "fh_k2_lds.h", "fh_internal.h", "fh_options.h", "fh_options.cpp", "fh_k2b.hip", "fh_k2bw.hip", "fh_batch.hip", "fh_batch_plan.h", "fh_batch_large.hip", "fh_records.hip", "fh_records_plan.h", "fh_epilogue_dev.h", "fh_k2w.hip", "fh_k2.hip", "fh_k2s.hip", "fh_k2ws.hip", "fh_kernels.hip", "fh_big.hip", "fh_text.hip", "fh_bgzf.hip", "fh_api.hip", "fh_dist.hip", "fh_dist.h", "fh_dist_dev.h", "fh_index.hip", "fh_index.h", "fh_cluster.h", "fh_merge_path.h", "fh_gather.hip", "fh_matrix.hip", "fh_matrix.h", "fh_moments.hip", "fh_moments.h", "fh_merge_lib.hip", "fh_merge_lib.h", "fh_counts.hip", "fh_counts.h", "fh_host.cpp", "fh_library.cpp",
+SOURCES = ["fh_core.h", "fh_device.h", "fh_kernels.h", "fh_k2_common.h", "fh_k2_lds.h", "fh_internal.h", "fh_options.h", "fh_options.cpp", "fh_k2b.hip", "fh_k2bw.hip", "fh_batch.hip", "fh_batch_plan.h", "fh_batch_large.hip", "fh_records.hip", "fh_records_plan.h", "fh_screen.hip", "fh_screen.h", "fh_epilogue_dev.h", "fh_k2w.hip", "fh_k2.hip", "fh_k2s.hip", "fh_k2ws.hip", "fh_kernels.hip", "fh_big.hip", "fh_text.hip", "fh_bgzf.hip", "fh_api.hip", "fh_dist.hip", "fh_dist.h", "fh_dist_dev.h", "fh_index.hip", "fh_index.h", "fh_cluster.h", "fh_merge_path.h", "fh_gather.hip", "fh_matrix.hip", "fh_matrix.h", "fh_moments.hip", "fh_moments.h", "fh_merge_lib.hip", "fh_merge_lib.h", "fh_counts.hip", "fh_counts.h", "fh_host.cpp", "fh_library.cpp",
            "fh_host_model.h", "fh_inflate.h", "fh_pargz.h", "fh_slot_pipe.h", "fh_entries.h", "fh_serial.cpp", os.path.join("..", "..", "include", "finch_host.h"),
            os.path.join("..", "..", "include", "finch_hip.h")]
 
@@ -118,6 +118,8 @@ def _build_locked(verbose):
         jobs.append([HIPCC] + FLAGS + K2W_FLAGS + ["-DFH_PART=%d" % part, "-c", "fh_k2bw.hip", "-o", os.path.join(OBJ, "fh_k2bw_%d.o" % part)])
     for part in range(NPARTS):  # one sketch per record, in a workgroup's LDS (part 0 also holds the handle and the C ABI)
         jobs.append([HIPCC] + FLAGS + K2_FLAGS + ["-DFH_PART=%d" % part, "-c", "fh_records.hip", "-o", os.path.join(OBJ, "fh_records_%d.o" % part)])
+    for part in range(NPARTS):  # the screen of a library in raw reads (part 0 also holds the table, the finish and the host side)
+        jobs.append([HIPCC] + FLAGS + K2_FLAGS + ["-DFH_PART=%d" % part, "-c", "fh_screen.hip", "-o", os.path.join(OBJ, "fh_screen_%d.o" % part)])
     jobs.append([HIPCC] + FLAGS + ["-c", "fh_kernels.hip", "-o", os.path.join(OBJ, "fh_kernels.o")])
     jobs.append([HIPCC] + FLAGS + ["-c", "fh_big.hip", "-o", os.path.join(OBJ, "fh_big.o")])
     jobs.append([HIPCC] + FLAGS + ["-c", "fh_text.hip", "-o", os.path.join(OBJ, "fh_text.o")])

@@ -44,6 +44,7 @@
 #include "fh_fqstrip.h"
 #include "fh_pack2.h"
 #include "fh_entries.h"
+#include "fh_screen.h"
 #include "fh_slot_pipe.h"
 
 namespace fh {
@@ -5137,5 +5138,379 @@ int finch_fasta_count_chunked(const uint8_t *data, uint64_t len, uint64_t chunk,
     if (total_bases) *total_bases = fc.total_bases;
     return FH_OK;
 } FINCH_CATCH
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// screen: containment of a library's references in raw reads (include/finch_host.h).  finch_screen_host is
+// the contract in plain host code with a hash map; finch_index_screen packs the sample's records into two-bit pieces on a
+// producer thread and hands them through two slots to the device side (fh_screen.hip), which holds the table and the kernels.
+// ---------------------------------------------------------------------------------------------
+struct finch_screen_result {
+    std::vector<finch_screen_row> rows;
+    uint64_t positions = 0;
+    fh::ScreenStats st;
+};
+
+namespace {
+
+// murmurhash3_x64_128(key, seed).0 (murmurhash3 0.0.5, hashing.rs:10-12) over the bytes as they come: the host statement of
+// the hash, independent of the device's table forms
+uint64_t screen_rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
+uint64_t screen_fmix(uint64_t k) {
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+uint64_t screen_murmur_h1(const uint8_t *key, size_t len, uint64_t seed) {
+    const uint64_t c1 = 0x87c37b91114253d5ull, c2 = 0x4cf5ad432745937full;
+    uint64_t h1 = seed, h2 = seed;
+    const size_t nblocks = len / 16;
+    for (size_t i = 0; i < nblocks; ++i) {
+        uint64_t k1, k2;
+        memcpy(&k1, key + 16 * i, 8);
+        memcpy(&k2, key + 16 * i + 8, 8);
+        k1 *= c1, k1 = screen_rotl(k1, 31), k1 *= c2, h1 ^= k1;
+        h1 = screen_rotl(h1, 27), h1 += h2, h1 = h1 * 5 + 0x52dce729;
+        k2 *= c2, k2 = screen_rotl(k2, 33), k2 *= c1, h2 ^= k2;
+        h2 = screen_rotl(h2, 31), h2 += h1, h2 = h2 * 5 + 0x38495ab5;
+    }
+    const uint8_t *tail = key + 16 * nblocks;
+    const size_t rest = len & 15;
+    uint64_t k1 = 0, k2 = 0;
+    for (size_t i = rest; i > 8; --i) k2 |= (uint64_t)tail[i - 1] << (8 * (i - 9));
+    for (size_t i = std::min<size_t>(rest, 8); i > 0; --i) k1 |= (uint64_t)tail[i - 1] << (8 * (i - 1));
+    if (rest > 8) k2 *= c2, k2 = screen_rotl(k2, 33), k2 *= c1, h2 ^= k2;
+    if (rest > 0) k1 *= c1, k1 = screen_rotl(k1, 31), k1 *= c2, h1 ^= k1;
+    h1 ^= (uint64_t)len, h2 ^= (uint64_t)len;
+    h1 += h2, h2 += h1;
+    h1 = screen_fmix(h1), h2 = screen_fmix(h2);
+    return h1 + h2;
+}
+
+// every window of every record, counted where its hash is a library hash
+struct HostScreenSink : RecordSink {
+    const uint32_t k;
+    const uint64_t seed, mask;
+    std::unordered_map<uint64_t, uint64_t> &mult; // the library's distinct hashes, each from 0
+    uint64_t positions = 0, kmers = 0, hits = 0;
+    uint64_t fwd = 0, rev = 0; // the last k bases, first base most significant / their reverse complement
+    uint32_t run = 0;          // bases since the last breaker
+    HostScreenSink(uint32_t k_, uint64_t seed_, std::unordered_map<uint64_t, uint64_t> &m)
+        : k(k_), seed(seed_), mask(k_ == 32 ? ~0ull : (1ull << (2 * k_)) - 1), mult(m) {}
+    int piece(const uint8_t *p, size_t n) override {
+        uint8_t ascii[32];
+        for (size_t i = 0; i < n; ++i) {
+            const uint8_t b = p[i];
+            if (b == ' ' || b == '\t' || b == '\r' || b == '\n') continue; // (normalize(false) drops blanks, mash.rs:73)
+            ++positions;
+            uint64_t code;
+            uint32_t good;
+            fh_pack2::classify1(b, code, good);
+            if (!good) {
+                run = 0;
+                continue;
+            }
+            fwd = ((fwd << 2) | code) & mask;
+            rev = (rev >> 2) | ((3 - code) << (2 * (k - 1)));
+            if (++run < k) continue;
+            ++kmers;
+            const uint64_t canon = fwd < rev ? fwd : rev;
+            for (uint32_t j = 0; j < k; ++j) ascii[j] = "ACGT"[(canon >> (2 * (k - 1 - j))) & 3];
+            auto it = mult.find(screen_murmur_h1(ascii, k, seed));
+            if (it != mult.end()) ++it->second, ++hits;
+        }
+        return FH_OK;
+    }
+    int end_record() override {
+        run = 0;
+        return FH_OK;
+    }
+};
+
+// what both forms refuse before anything is read
+int screen_refusals(const char *call, bool null_arg, uint32_t k) {
+    if (null_arg) return hfail(FH_ERR_INVALID, "null argument");
+    if (k == 0 || k > 64) return hfail(FH_ERR_INVALID, "%s: kmer_length %u (1..32)", call, k);
+    if (k > 32) return hfail(FH_ERR_UNSUPPORTED, "%s: kmer_length %u: the screen serves kmer_length <= 32", call, k);
+    return FH_OK;
+}
+
+// the rows of the references with shared >= max(1, min_shared), in reference order
+void screen_rows(const std::vector<uint32_t> &shared, const std::vector<uint64_t> &sum, const std::vector<uint64_t> &median,
+                 const std::vector<uint32_t> &rlen, uint32_t min_shared, std::vector<finch_screen_row> &rows) {
+    const uint32_t floor_ = std::max(1u, min_shared);
+    for (size_t r = 0; r < shared.size(); ++r) {
+        if (shared[r] < floor_) continue;
+        finch_screen_row row{};
+        row.reference = (uint32_t)r, row.shared = shared[r], row.ref_len = rlen[r];
+        row.median_mult = median[r], row.sum_mult = sum[r];
+        row.containment = (double)shared[r] / (double)rlen[r];
+        rows.push_back(row);
+    }
+}
+
+struct ScreenJob {
+    int slot;
+    uint64_t positions;
+};
+
+// the sample's records into two-bit pieces of at most `cap` positions (fh_pack2.h), one not-a-base position behind every record;
+// a record that a piece cuts continues in the next one behind its last k - 1 positions, so that every window lies whole in
+// exactly one piece.  Runs on the producer thread; touches no device.
+struct ScreenSink : RecordSink {
+    SlotPipe<ScreenJob> &pipe;
+    fh::ScreenDevice *dev;
+    const uint32_t k;
+    const uint64_t cap;
+    std::unique_ptr<fh_pack2::Packer> packer{new fh_pack2::Packer};
+    std::vector<uint8_t> stripped;
+    int slot = 0;
+    bool have = false, carry = false;
+    uint64_t pos = 0, positions = 0;
+    uint8_t tail[32];
+    uint32_t tail_n = 0;
+    ScreenSink(SlotPipe<ScreenJob> &p, fh::ScreenDevice *d, uint32_t k_, uint64_t cap_) : pipe(p), dev(d), k(k_), cap(cap_), stripped((64u << 10) + 64) {
+        packer->force_form((unsigned)cfg_u64("pack_scalar", 0));
+    }
+    int begin_slot() {
+        if (!pipe.acquire(slot)) return hfail(FH_ERR_STATE, "finch_index_screen: the call was abandoned");
+        packer->begin(fh::screen_slot(dev, slot));
+        have = true;
+        pos = 0;
+        if (carry && tail_n) { // (tail_n <= 31 < cap)
+            packer->text(tail, tail_n);
+            pos = tail_n;
+        }
+        carry = false;
+        return FH_OK;
+    }
+    void flush(bool mid_record) {
+        const uint64_t len = packer->finish();
+        pipe.publish(ScreenJob{slot, len});
+        slot ^= 1;
+        have = false;
+        carry = mid_record;
+    }
+    void remember(const uint8_t *q, size_t t) { // the record's last k - 1 stripped bytes
+        const size_t keep = k - 1;
+        if (t >= keep) {
+            memcpy(tail, q + t - keep, keep);
+            tail_n = (uint32_t)keep;
+            return;
+        }
+        const size_t from_old = std::min<size_t>(tail_n, keep - t);
+        memmove(tail, tail + tail_n - from_old, from_old);
+        memcpy(tail + from_old, q, t);
+        tail_n = (uint32_t)(from_old + t);
+    }
+    int piece(const uint8_t *p, size_t n) override {
+        const size_t step = stripped.size() - 64;
+        for (size_t o = 0; o < n; o += step) {
+            const uint8_t *q = stripped.data();
+            size_t m = strip_copy(stripped.data(), p + o, std::min(step, n - o));
+            while (m) {
+                if (!have)
+                    if (int rc = begin_slot()) return rc;
+                const size_t t = (size_t)std::min<uint64_t>(cap - pos, m);
+                packer->text(q, t);
+                remember(q, t);
+                pos += t, positions += t, q += t, m -= t;
+                if (pos == cap) flush(true);
+            }
+        }
+        return FH_OK;
+    }
+    int end_record() override {
+        tail_n = 0;
+        carry = false;
+        if (!have) return FH_OK; // (nothing of the record in the open piece: nothing to part it from)
+        packer->byte(0);
+        if (++pos == cap) flush(false);
+        return FH_OK;
+    }
+    void finish() {
+        if (have && pos) flush(false);
+    }
+};
+
+struct ScreenInput { // a file name, or the buffer
+    const char *name = nullptr;
+    const uint8_t *data = nullptr;
+    uint64_t len = 0;
+};
+
+int index_screen_core(const finch_index *ix, const std::vector<ScreenInput> &inputs, uint32_t k, uint64_t seed, uint32_t min_shared,
+                      uint32_t n_threads, finch_screen_result **out) {
+    std::lock_guard<std::mutex> one_call(fh::index_mutex_of(ix)); // (finch_index_add / finch_index_keep wait)
+    auto res = std::make_unique<finch_screen_result>();
+    fh::IndexDevice *entry = fh::index_first_entry(ix);
+    bool any = false;
+    for (const ScreenInput &in : inputs) any = any || in.name || in.len;
+    if (!entry || !any) { // no reference has a hash, or there is no sample: no row, no device
+        *out = res.release();
+        return FH_OK;
+    }
+    const std::vector<uint32_t> &rlen = fh::index_ref_lengths(ix);
+    fh::ScreenView view;
+    fh::index_screen_view(entry, &view);
+    uint64_t piece = std::min<uint64_t>(std::max<uint64_t>(cfg_u64("screen_piece", fh::SCREEN_PIECE_DEFAULT), fh::SCREEN_PIECE_MIN), fh::SCREEN_PIECE_MAX);
+    piece -= piece % fh_pack2::TILE_POS;
+    const int dir_bits = cfg("screen_dir_bits") ? (int)std::min<uint64_t>(cfg_u64("screen_dir_bits", 0), fh::SCREEN_DIR_BITS_MAX) : -1;
+    fh::ScreenDevice *dev = nullptr;
+    if (int rc = fh::screen_open(view, k, seed, dir_bits, piece, &dev)) return hfail(rc, "%s", fh_last_error());
+    fh::Finally close_dev{[&] { fh::screen_close(dev); }};
+
+    const unsigned read_threads = n_threads ? n_threads : read_threads_total(cfg("read_threads"));
+    int prod_rc = FH_OK; // the producer's error: its message is thread-local there, so it is carried over
+    std::string prod_msg;
+    uint64_t positions = 0;
+    int launch_rc = FH_OK;
+    {
+        SlotPipe<ScreenJob> pipe([&](SlotPipe<ScreenJob> &p) {
+            ScreenSink sink(p, dev, k, piece);
+            int rc = FH_OK;
+            try {
+                for (const ScreenInput &in : inputs) {
+                    std::unique_ptr<ByteSource> raw, src;
+                    if (in.name) {
+                        FILE *fp = strcmp(in.name, "-") == 0 ? stdin : fopen(in.name, "rb");
+                        if (!fp) {
+                            rc = hfail(FH_ERR_INVALID, "%s: %s (os error %d)", in.name, strerror(errno), errno);
+                            break;
+                        }
+                        raw = std::make_unique<FileSource>(fp, fp != stdin, read_threads);
+                    } else {
+                        raw = std::make_unique<MemSource>(in.data, (size_t)in.len, read_threads);
+                    }
+                    FastxStats st;
+                    if ((rc = open_source(std::move(raw), src)) != FH_OK || (rc = parse_fastx(*src, sink, st)) != FH_OK) break;
+                }
+                if (rc == FH_OK) sink.finish();
+            } catch (const std::bad_alloc &) {
+                rc = hfail(FH_ERR_CAPACITY, "out of host memory");
+            }
+            positions = sink.positions;
+            prod_rc = rc;
+            if (rc != FH_OK) prod_msg = g_host_err;
+        });
+        ScreenJob job;
+        while (pipe.next(job)) {
+            launch_rc = fh::screen_launch(dev, job.slot, job.positions);
+            pipe.release(job.slot);
+            if (launch_rc != FH_OK) {
+                pipe.abort();
+                break;
+            }
+        }
+        // (next() has returned false: the producer is done.  An exception other than the one it catches closed the pipe: the sample
+        // was not read to its end)
+        if (launch_rc == FH_OK && pipe.producer_threw()) prod_rc = FH_ERR_CAPACITY, prod_msg = "out of host memory";
+    } // (the producer has joined)
+    if (launch_rc != FH_OK) return hfail(launch_rc, "%s", fh_last_error());
+    if (prod_rc != FH_OK) return hfail(prod_rc, "%s", prod_msg.c_str());
+
+    std::vector<uint32_t> shared(view.nr);
+    std::vector<uint64_t> sum(view.nr), median(view.nr);
+    if (int rc = fh::screen_finish(dev, shared.data(), sum.data(), median.data(), &res->st)) return hfail(rc, "%s", fh_last_error());
+    res->positions = positions;
+    screen_rows(shared, sum, median, rlen, min_shared, res->rows);
+    *out = res.release();
+    return FH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int finch_index_screen(const finch_index *ix, const char *const *filenames, uint32_t n_files, uint32_t kmer_length, uint64_t hash_seed,
+                       uint32_t min_shared, uint32_t n_threads, finch_screen_result **out) try {
+    if (int rc = screen_refusals("finch_index_screen", !ix || !out || (!filenames && n_files), kmer_length)) return rc;
+    std::vector<ScreenInput> inputs(n_files);
+    for (uint32_t f = 0; f < n_files; ++f) {
+        if (!filenames[f]) return hfail(FH_ERR_INVALID, "null argument");
+        inputs[f].name = filenames[f];
+        if (strcmp(filenames[f], "-") != 0) { // a file that cannot be opened is refused before anything is read or launched
+            FILE *fp = fopen(filenames[f], "rb");
+            if (!fp) return hfail(FH_ERR_INVALID, "%s: %s (os error %d)", filenames[f], strerror(errno), errno);
+            fclose(fp);
+        }
+    }
+    return index_screen_core(ix, inputs, kmer_length, hash_seed, min_shared, n_threads, out);
+} FINCH_CATCH
+
+int finch_index_screen_buffer(const finch_index *ix, const uint8_t *data, uint64_t len, uint32_t kmer_length, uint64_t hash_seed,
+                              uint32_t min_shared, uint32_t n_threads, finch_screen_result **out) try {
+    if (int rc = screen_refusals("finch_index_screen_buffer", !ix || !out || (!data && len), kmer_length)) return rc;
+    std::vector<ScreenInput> inputs(1);
+    inputs[0].data = data, inputs[0].len = len;
+    return index_screen_core(ix, inputs, kmer_length, hash_seed, min_shared, n_threads, out);
+} FINCH_CATCH
+
+int finch_screen_host(const finch_sketches *refs, const uint8_t *data, uint64_t len, uint32_t kmer_length, uint64_t hash_seed,
+                      uint32_t min_shared, finch_screen_result **out) try {
+    if (int rc = screen_refusals("finch_screen_host", !refs || !out || (!data && len), kmer_length)) return rc;
+    auto res = std::make_unique<finch_screen_result>();
+    const std::vector<Sketch> &Rs = refs->v;
+    std::unordered_map<uint64_t, uint64_t> mult;
+    for (const Sketch &s : Rs)
+        for (const KmerCount &h : s.hashes) mult.emplace(h.hash, 0);
+    if (mult.empty() || len == 0) {
+        *out = res.release();
+        return FH_OK;
+    }
+    HostScreenSink sink(kmer_length, hash_seed, mult);
+    std::unique_ptr<ByteSource> src;
+    if (int rc = open_source(std::make_unique<MemSource>(data, (size_t)len), src)) return rc;
+    FastxStats st;
+    if (int rc = parse_fastx(*src, sink, st)) return rc;
+    const size_t nr = Rs.size();
+    std::vector<uint32_t> shared(nr, 0), rlen(nr);
+    std::vector<uint64_t> sum(nr, 0), median(nr, 0), ms;
+    for (size_t r = 0; r < nr; ++r) {
+        rlen[r] = (uint32_t)Rs[r].hashes.size();
+        ms.clear();
+        for (const KmerCount &h : Rs[r].hashes) {
+            const uint64_t m = mult.find(h.hash)->second;
+            if (m) ms.push_back(m), sum[r] += m;
+        }
+        shared[r] = (uint32_t)ms.size();
+        if (ms.empty()) continue;
+        std::sort(ms.begin(), ms.end());
+        median[r] = ms[(ms.size() - 1) / 2];
+    }
+    screen_rows(shared, sum, median, rlen, min_shared, res->rows);
+    res->positions = sink.positions;
+    res->st.kmers = sink.kmers, res->st.hits = sink.hits, res->st.distinct = mult.size();
+    *out = res.release();
+    return FH_OK;
+} FINCH_CATCH
+
+uint64_t finch_screen_len(const finch_screen_result *r) { return r ? r->rows.size() : 0; }
+
+int finch_screen_copy(const finch_screen_result *r, finch_screen_row *rows) try {
+    if (!r || (!rows && !r->rows.empty())) return hfail(FH_ERR_INVALID, "null argument");
+    if (!r->rows.empty()) memcpy(rows, r->rows.data(), r->rows.size() * sizeof(finch_screen_row));
+    return FH_OK;
+} FINCH_CATCH
+
+int finch_screen_stats(const finch_screen_result *r, uint64_t *positions, uint64_t *kmers, uint64_t *hits, uint64_t *distinct,
+                       uint64_t *table_bytes, double *table_ms, double *kernel_ms, uint64_t *launches) try {
+    if (!r) return hfail(FH_ERR_INVALID, "null argument");
+    if (positions) *positions = r->positions;
+    if (kmers) *kmers = r->st.kmers;
+    if (hits) *hits = r->st.hits;
+    if (distinct) *distinct = r->st.distinct;
+    if (table_bytes) *table_bytes = r->st.table_bytes;
+    if (table_ms) *table_ms = r->st.table_ms;
+    if (kernel_ms) *kernel_ms = r->st.kernel_ms;
+    if (launches) *launches = r->st.launches;
+    return FH_OK;
+} FINCH_CATCH
+
+void finch_screen_free(finch_screen_result *r) { delete r; }
 
 } // extern "C"

@@ -54,6 +54,7 @@
 #include "fh_kernels.h"
 #include "fh_merge_path.h"
 #include "fh_moments.h"
+#include "fh_screen.h"
 
 using namespace fh;
 
@@ -816,6 +817,15 @@ static void cluster_drop(IndexDevice *d) {
     if (d->labels) (void)hipFree(d->labels);
     if (d->united) (void)hipFree(d->united);
     d->jhi = nullptr, d->parent = d->labels = nullptr, d->united = nullptr;
+}
+
+// what finch_index_screen reads (fh_screen.h): the arrays in use now -- after an update, the updated library's
+void index_screen_view(IndexDevice *d, ScreenView *v) {
+    v->rh = (const uint64_t *)d->lib[0], v->roff = (const uint64_t *)d->lib[1];
+    v->keys = (const uint64_t *)d->lib[7], v->vals = (const uint32_t *)d->lib[8];
+    v->nr = d->nr, v->n_post = d->n_post;
+    v->device = d->device;
+    v->stream = (void *)d->stream;
 }
 
 void index_close(IndexDevice *d) {

@@ -27,6 +27,7 @@
 #include "fh_moments.h"
 #include "fh_merge_lib.h"
 #include "fh_entries.h"
+#include "fh_screen.h"
 
 namespace fh {
 uint64_t api_scaled_max_hash(double scale); // fh_internal.h (which needs the HIP headers): a ScaledSketcher's max_hash, scaled.rs:23,31
@@ -674,6 +675,13 @@ struct finch_index {
         fh::matrix_restore_device(prev);
     }
 };
+
+// what finch_index_screen (fh_host.cpp) needs of an index: fh_screen.h
+namespace fh {
+std::mutex &index_mutex_of(const finch_index *ix) { return ix->mu; }
+IndexDevice *index_first_entry(const finch_index *ix) { return ix->entries.empty() ? nullptr : ix->entries[0]; }
+const std::vector<uint32_t> &index_ref_lengths(const finch_index *ix) { return ix->rlen; }
+} // namespace fh
 
 namespace {
 

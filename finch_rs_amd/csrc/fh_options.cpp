@@ -109,6 +109,9 @@ const OptDef DEFS[] = {
     {"records_stream", "1: finch_sketch_records streams a record of more than 8192 positions through one workgroup (the streamed record sketcher: Mash up to 1024 hashes, Scaled, k <= 32), many per launch; 0 (the default): such a record goes one by one through its own sketcher"},
     {"records_stream_max_pos", "positions of the longest record records_stream=1 streams, at most 2^24 (default 200000: the largest measured length at which streaming was not slower, docs/MEASUREMENTS_records_stream.md)"},
     {"records_stream_fold", "the streamed record sketcher folds its pending keys into the running list whenever at least this many are pending behind a round, read when a handle is made (default 0: only when the key array could not take another round; tests: 1 = a fold after every round)"},
+    // --- finch_index_screen ---
+    {"screen_piece", "positions of the sample that finch_index_screen stages per launch, at least 2048 (one tile) and at most 2^30, rounded down to whole tiles (default 16 M = 6 MiB per slot; tests: 2048 = a record continues over many pieces)"},
+    {"screen_dir_bits", "b of finch_index_screen's directory of 2^b buckets over the library's distinct hashes, 1..28 (default ceil(log2 distinct) within that range: about one hash per bucket; tests: 1 = long buckets)"},
 };
 constexpr int N_OPTS = (int)(sizeof(DEFS) / sizeof(DEFS[0]));
 

@@ -165,6 +165,20 @@ class CClusterStats(C.Structure):
 
 _SYMS["finch_index_cluster"] = (C.c_int, [_P, _P, C.c_int, C.c_double, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(CClusterStats)])
 _SYMS["finch_cluster_host"] = (C.c_int, [_P, C.c_int, C.c_double, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)])
+
+
+class CScreenRow(C.Structure):
+    _fields_ = [("reference", C.c_uint32), ("shared", C.c_uint32), ("ref_len", C.c_uint32), ("reserved", C.c_uint32),
+                ("median_mult", C.c_uint64), ("sum_mult", C.c_uint64), ("containment", C.c_double)]
+
+
+_SYMS["finch_index_screen"] = (C.c_int, [_P, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_P)])
+_SYMS["finch_index_screen_buffer"] = (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(_P)])
+_SYMS["finch_screen_host"] = (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(_P)])
+_SYMS["finch_screen_len"] = (C.c_uint64, [_P])
+_SYMS["finch_screen_copy"] = (C.c_int, [_P, _P])
+_SYMS["finch_screen_stats"] = (C.c_int, [_P] + [C.POINTER(C.c_uint64)] * 5 + [C.POINTER(C.c_double)] * 2 + [C.POINTER(C.c_uint64)])
+_SYMS["finch_screen_free"] = (None, [_P])
 _SYMS["finch_gather_query"] = (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)])
 _SYMS["finch_gather"] = (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.c_uint32, C.POINTER(_P)])
 _SYMS["finch_gather_len"] = (C.c_uint64, [_P])
@@ -884,6 +898,38 @@ class LibraryIndex:
         _check(lib().finch_index_compare_counts(h, queries._p, min(int(min_common), 2 ** 64 - 1), C.byref(p)))
         return _counts_rows(p, stats, from_index=True)
 
+    def screen(self, inputs, kmer_length: Optional[int] = None, hash_seed: Optional[int] = None, min_shared: int = 1,
+               n_threads: int = 0, stats: Optional[dict] = None) -> np.ndarray:
+        """containment of every reference in RAW READS (finch_index_screen; what `mash screen` is reached for): `inputs` -- a
+        path, a sequence of paths, or the bytes of one input; FASTA or FASTQ, plain or compressed -- is read as one sample, every
+        k-mer of it is hashed and looked up among the library's hashes -> SCREEN_DTYPE rows, one per reference that holds at
+        least max(1, min_shared) hashes of the sample, in library order: shared, sum_mult, median_mult (the lower median of the
+        shared hashes' multiplicities), ref_len, containment = shared / ref_len; == screen_host(self.refs, data, ...), byte for
+        byte.  mash screen's identity is rows["containment"] ** (1 / kmer_length).  kmer_length / hash_seed default to those
+        of the library's sketches, which must then agree among themselves (FinchError).  `stats` receives finch_screen_stats'
+        figures"""
+        if kmer_length is None or hash_seed is None:
+            ps = {(q.kmer_length, q.hash_seed) for q in (self.refs.params_of(i) for i in range(len(self.refs)))}
+            if not ps:
+                raise FinchError("LibraryIndex.screen: the library has no sketches to take kmer_length and hash_seed from; name them")
+            if len(ps) != 1:
+                raise FinchError("LibraryIndex.screen: the library's sketches have %d different (kmer_length, hash_seed); name the "
+                                 "sample's" % len(ps))
+            k0, s0 = next(iter(ps))
+            kmer_length = k0 if kmer_length is None else kmer_length
+            hash_seed = s0 if hash_seed is None else hash_seed
+        p = _P()
+        if isinstance(inputs, (bytes, bytearray, memoryview)):
+            buf = np.frombuffer(inputs, dtype=np.uint8)
+            _check(lib().finch_index_screen_buffer(self._handle(), buf.ctypes.data if len(buf) else None, len(buf), int(kmer_length),
+                                                   int(hash_seed), int(min_shared), int(n_threads), C.byref(p)))
+        else:
+            paths = [inputs] if isinstance(inputs, str) else list(inputs)
+            arr = (C.c_char_p * len(paths))(*[f.encode() for f in paths])
+            _check(lib().finch_index_screen(self._handle(), arr, len(paths), int(kmer_length), int(hash_seed), int(min_shared),
+                                            int(n_threads), C.byref(p)))
+        return _screen_rows(p, stats)
+
     def add(self, more: Sketches, stats: Optional[dict] = None) -> None:
         """Multisketch.add (python.rs:191-194): the sketches of `more` after the library's last one, in the index
         (finch_index_add: a merge on the device, nothing of the old library crosses the link) and in self.refs, which grows
@@ -947,6 +993,39 @@ class LibraryIndex:
 GATHER_DTYPE = np.dtype([(f, np.uint64) for f in ("query", "reference", "round", "overlap", "common", "ref_len", "query_len", "abund",
                                                    "remaining")] +
                         [(f, np.float64) for f in ("f_unique_to_query", "f_orig_query", "f_match", "average_abund", "f_unique_weighted")])
+
+
+# one row of finch_index_screen / finch_screen_host: finch_screen_row
+SCREEN_DTYPE = np.dtype([("reference", np.uint32), ("shared", np.uint32), ("ref_len", np.uint32), ("reserved", np.uint32),
+                         ("median_mult", np.uint64), ("sum_mult", np.uint64), ("containment", np.float64)])
+assert SCREEN_DTYPE.itemsize == C.sizeof(CScreenRow)
+
+
+def _screen_rows(p, stats: Optional[dict]) -> np.ndarray:
+    L = lib()
+    try:
+        rows = np.zeros(L.finch_screen_len(p), SCREEN_DTYPE)
+        _check(L.finch_screen_copy(p, rows.ctypes.data if len(rows) else None))
+        if stats is not None:
+            u = [C.c_uint64() for _ in range(6)]
+            d = [C.c_double(), C.c_double()]
+            _check(L.finch_screen_stats(p, *[C.byref(x) for x in u[:5]], C.byref(d[0]), C.byref(d[1]), C.byref(u[5])))
+            stats.update(positions=u[0].value, kmers=u[1].value, hits=u[2].value, distinct=u[3].value, table_bytes=u[4].value,
+                         table_ms=d[0].value, kernel_ms=d[1].value, launches=u[5].value)
+        return rows
+    finally:
+        L.finch_screen_free(p)
+
+
+def screen_host(refs: Sketches, data: bytes, kmer_length: int, hash_seed: int = 0, min_shared: int = 1,
+                stats: Optional[dict] = None) -> np.ndarray:
+    """finch_screen_host: the screen's contract on the host with a hash map, no device -> SCREEN_DTYPE rows; `data` is the
+    image of one input, container included"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    p = _P()
+    _check(lib().finch_screen_host(refs._p, buf.ctypes.data if len(buf) else None, len(buf), int(kmer_length), int(hash_seed),
+                                   int(min_shared), C.byref(p)))
+    return _screen_rows(p, stats)
 
 
 def cluster_host(sketches: Sketches, max_distance: float, old_mode: bool = False, edges: Optional[list] = None) -> np.ndarray:

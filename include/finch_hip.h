@@ -105,7 +105,9 @@ const char *fh_last_error(void);
  * records_lds; additions that change nothing of 21: fh_records_new_stream, fh_records_max_positions_of, fh_records_stream_cap,
  * fh_records_stream_folds,
  * finch_sketch_records_stream_stats in finch_host.h and the options records_stream, records_stream_max_pos,
- * records_stream_fold) */
+ * records_stream_fold; and the screen of a library in raw reads: finch_index_screen, finch_index_screen_buffer,
+ * finch_screen_host, finch_screen_len, finch_screen_copy, finch_screen_stats, finch_screen_free and finch_screen_row in
+ * finch_host.h and the options screen_piece, screen_dir_bits) */
 #define FH_ABI_VERSION 21
 int fh_abi_version(void);
 

@@ -361,6 +361,66 @@ int finch_index_cluster(const finch_index *ix, const finch_sketches *refs, int o
 int finch_cluster_host(const finch_sketches *refs, int old_mode, double max_distance, uint32_t *labels, uint64_t n_labels,
                        uint64_t *edges /* may be NULL */);
 
+/* screen: which references of a library are IN a set of raw reads, and how deep -- the question `mash screen` answers.  Every
+ * other library call takes a sketch as the query; a bottom-1000 sketch of a metagenome shares next to nothing with any single
+ * member genome.  A screen does not sketch the sample: it hashes EVERY k-mer of it and looks each hash up among the library's.
+ * Not in the reference; the contract is this comment (tests/screen_model.py states it in Python).  Integers only:
+ *   The inputs are read as ONE sample.  For every record of every input, every window of kmer_length consecutive bases counts:
+ *     ACGT, acgt and U/u are bases, any other byte breaks k-mers (blanks and line ends inside a record's sequence are dropped
+ *     first, as everywhere in this library); no window spans two records.  The window's hash is hash_f(canonical k-mer,
+ *     hash_seed), as the sketchers compute it (mash.rs:73-79, hashing.rs:10-12).  mult(h) = the number of windows whose hash is
+ *     h -- the `count` a Mash sketcher holds for h when kmers_to_sketch is at least the sample's distinct k-mers.  Two k-mers
+ *     with one 64-bit hash count together, as in the reference's sketchers, which key by hash.
+ *   Per reference r:  ref_len = r's hashes;  shared = r's hashes h with mult(h) > 0;  sum_mult = the sum of mult(h) over those;
+ *     median_mult = with their multiplicities sorted ascending m[0 .. shared), m[(shared - 1) / 2]: the lower median, no
+ *     averaging;  containment = (double)shared / (double)ref_len, one IEEE division on the host.  Plain set semantics over the
+ *     hashes as stored: a Scaled reference is judged on the hashes it holds.  (mash screen's identity is
+ *     pow(containment, 1. / kmer_length); it is not part of a row.)
+ *   The result holds one row per reference with shared >= max(1, min_shared), in reference order.
+ * finch_screen_host: the contract as written, on the host with a hash map; `data` is the image of one input, container
+ *   included (plain, gzip, BGZF, bz2, xz; FASTA or FASTQ); no device.
+ * finch_index_screen / finch_index_screen_buffer: the same rows through the index.  Every container finch_sketch_files reads is
+ *   accepted, "-" is stdin.  The host packs the records into the two-bit form (one not-a-base position behind every record)
+ *   and stages pieces of at most `screen_piece` positions (option; default 16 M, at least one tile of 2048) through two slots; a
+ *   record longer than a piece continues in the next one with its last kmer_length - 1 positions repeated in front, so that no
+ *   window is lost and none counts twice.  On the device, per call: a table of the library's DISTINCT hashes made from the
+ *   index's current postings (a screen after finch_index_add / finch_index_keep sees the updated library) with a zeroed u64
+ *   multiplicity each and a directory of 2^b buckets over them (option screen_dir_bits, 1..28, default ceil(log2 distinct)) keyed by
+ *   the b bits from the highest set bit of the largest hash down; k_screen hashes every window of a piece (the sketch kernels'
+ *   own arithmetic) and adds 1 to the multiplicity of a hash it finds; a finish kernel, one wave per reference, makes shared,
+ *   sum_mult and the exact median (a bit-by-bit search over the reference's multiplicities: no sort, no bound on ref_len).
+ *   Only three arrays of one value per reference cross to the host.  Everything the call allocates is freed when it ends.
+ *   The call holds the index's lock for its whole length (finch_index_add / finch_index_keep wait), runs on the index's FIRST
+ *   device entry (dealing pieces over several entries is not offered) and neither uses nor changes the index's own counters.
+ *   n_threads is what the decompressors may use (0: as finch_sketch_files decides).
+ *   THE EMPTY CASES.  A library without a hash, n_files == 0 or len == 0: nothing is read and no device is touched; the result
+ *   has no rows and EVERY figure of finch_screen_stats is 0 (positions and distinct too).  finch_screen_host does the same
+ *   for a library without a hash or len == 0.  The index is as it was.
+ *   FH_ERR_INVALID: a null argument, kmer_length 0 or above 64, a file that cannot be opened, an input that is no FASTA/FASTQ.
+ *   FH_ERR_UNSUPPORTED: kmer_length 33..64 ("the screen serves kmer_length <= 32").
+ * finch_screen_stats (any pointer may be NULL): positions = sequence positions of the sample (breakers and repeated positions
+ *   not counted); kmers = valid windows; hits = windows whose hash is a library hash (= the sum of all mult); distinct = the
+ *   library's distinct hashes; table_bytes / table_ms = the per-call table (distinct hashes, multiplicities, directory) and the
+ *   kernels that build it -- what caching it across calls would save; kernel_ms = k_screen's launches and the finish kernel;
+ *   launches = k_screen's launches.  After finch_screen_host: table_bytes, table_ms, kernel_ms, launches are 0. */
+typedef struct finch_screen_row {
+    uint32_t reference, shared, ref_len, reserved;
+    uint64_t median_mult, sum_mult;
+    double containment;
+} finch_screen_row;
+typedef struct finch_screen_result finch_screen_result;
+int finch_index_screen(const finch_index *ix, const char *const *filenames, uint32_t n_files, uint32_t kmer_length, uint64_t hash_seed,
+                       uint32_t min_shared, uint32_t n_threads, finch_screen_result **out);
+int finch_index_screen_buffer(const finch_index *ix, const uint8_t *data, uint64_t len, uint32_t kmer_length, uint64_t hash_seed,
+                              uint32_t min_shared, uint32_t n_threads, finch_screen_result **out);
+int finch_screen_host(const finch_sketches *refs, const uint8_t *data, uint64_t len, uint32_t kmer_length, uint64_t hash_seed,
+                      uint32_t min_shared, finch_screen_result **out);
+uint64_t finch_screen_len(const finch_screen_result *r);
+int finch_screen_copy(const finch_screen_result *r, finch_screen_row *rows);
+int finch_screen_stats(const finch_screen_result *r, uint64_t *positions, uint64_t *kmers, uint64_t *hits, uint64_t *distinct,
+                       uint64_t *table_bytes, double *table_ms, double *kernel_ms, uint64_t *launches);
+void finch_screen_free(finch_screen_result *r);
+
 /* gather: the greedy decomposition of a query sketch over a library -- what follows a search whose best-first list is full of
  * near-duplicates.  Not in the reference; the contract is this comment (tests/gather_model.py states it twice in Python).
  *   gather(Q, refs, min_overlap, max_rounds) for one query sketch Q and the library refs[0 .. R):
