@@ -283,10 +283,13 @@ static int upload(void **dst, const void *src, size_t bytes) {
     return FH_OK;
 }
 
-static int zeros(void **dst, size_t bytes) {
+// zeroed in the handle's own stream, in front of every kernel that reads it: the stream is non-blocking, so a memset in the
+// null stream is not ordered before its launches, and the counting kernel follows a set flag bit to arrays this path does not
+// have (dist_counts_query_major: qscale, qmax) -- freshly allocated memory may hold anything another entry just freed
+static int zeros(void **dst, size_t bytes, hipStream_t stream) {
     const size_t b = std::max<size_t>(bytes, 8);
     GHIP_TRY(api_dev_malloc(dst, b));
-    GHIP_TRY(hipMemset(*dst, 0, b));
+    GHIP_TRY(hipMemsetAsync(*dst, 0, b, stream));
     return FH_OK;
 }
 
@@ -323,11 +326,11 @@ static int open_into(GatherDevice *d, const GatherSide &q, const GatherSide &r) 
     if (int rc = upload((void **)&d->qoff, q.offsets, ((size_t)q.n + 1) * sizeof(uint64_t))) return rc;
     if (int rc = upload((void **)&d->rh, r.hashes, r.offsets[r.n] * sizeof(uint64_t))) return rc;
     if (int rc = upload((void **)&d->roff, r.offsets, ((size_t)r.n + 1) * sizeof(uint64_t))) return rc;
-    if (int rc = zeros((void **)&d->qflag, q.n * sizeof(uint32_t))) return rc;
-    if (int rc = zeros((void **)&d->rflag, r.n * sizeof(uint32_t))) return rc;
+    if (int rc = zeros((void **)&d->qflag, q.n * sizeof(uint32_t), d->stream)) return rc;
+    if (int rc = zeros((void **)&d->rflag, r.n * sizeof(uint32_t), d->stream)) return rc;
     GHIP_TRY(api_dev_malloc((void **)&d->cnt, std::max<uint64_t>(d->max_pairs, 1) * 3 * sizeof(uint32_t)));
     GHIP_TRY(api_dev_malloc((void **)&d->list, std::max<uint64_t>(d->max_pairs, 1) * sizeof(GatherCand)));
-    if (int rc = zeros((void **)&d->words, 2 * sizeof(uint32_t))) return rc;
+    if (int rc = zeros((void **)&d->words, 2 * sizeof(uint32_t), d->stream)) return rc;
     GHIP_TRY(api_host_malloc((void **)&d->words_h, 2 * sizeof(uint32_t)));
     GHIP_TRY(hipEventCreate(&d->ev0));
     GHIP_TRY(hipEventCreate(&d->ev1));

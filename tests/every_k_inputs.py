@@ -7,6 +7,7 @@ generator to what the sweep relies on.
     parts(k)  -> {name: [records]}      the named pieces, every record a uint8 array without its breaker
     stream(k) -> (records, packed)      all records in order, and their concatenation with one \\0 breaker behind each
     small(k, limit) -> packed prefix    the longest prefix of whole records of `packed` with at most `limit` positions
+    stream_records(k) -> [records]      k <= 32: three records on the edges of the STREAMED record sketcher -- round seams, folds
 """
 import functools
 
@@ -111,6 +112,53 @@ def stream(k):
 def long_offset(k):
     """where the long record begins in stream(k)'s packed form"""
     return len(stream(k)[1]) - (3 * TILE + k + 1)
+
+
+ROUND = 4096            # window starts the streamed record sketcher takes between two decision points (eight waves, two tiles)
+STREAM_ROUNDS = 6       # rounds of the long streamed record, the last one partial
+STREAM_SCALE = 0.02     # the sweep's Scaled records: about 400 of the long record's 20 000 hashes, within the streamed form's cap
+COPIED = (1000, 600, 3 * ROUND + 1000)  # a block of the first round (start, length), and where its reverse complement lies
+
+
+def stream_long_n_positions(k):
+    """where the long streamed record holds N.  Behind an odd seam's N no window that spans the seam from the left is valid;
+    an even seam's N invalidates every window that starts at the seam or up to k - 1 behind it.  The N two in front of the
+    fourth seam closes a run of exactly k bases with that seam's N: see stream_seam_window"""
+    seams = [r * ROUND - 1 if r % 2 else r * ROUND + k - 1 for r in range(1, STREAM_ROUNDS)]
+    return sorted(seams + [4 * ROUND - 2])
+
+
+def stream_seam_window(k):
+    """the start of the one valid window between two N around the fourth seam: it begins in one round and (k >= 2) ends in the next"""
+    return 4 * ROUND - 1
+
+
+def stream_a_run(k):
+    """(start, length) of the run of A: it ends just in front of the second seam's N, so for k >= 2 k - 1 windows of A^k span the seam"""
+    return 2 * ROUND - 2 * k - 1, 3 * k
+
+
+@functools.lru_cache(maxsize=None)
+def stream_records(k):
+    """the three records of the streamed record sketcher's sweep, k = 1..32:
+    1. 5 x 4096 + k + 37 positions -- six rounds, the last partial and no whole tile -- with N around every round seam
+       (stream_long_n_positions), one window alone between two N across a seam, A^(3k) across a seam, a block of the first round
+       again as its reverse complement in the fourth (its k-mers are in the list when they recur behind at least one fold) and
+       about 2 % lower case;
+    2. 8193 random positions, one above the LDS form's bound;
+    3. k + 1 bases."""
+    rng = np.random.default_rng(96000 + k)
+    long = rng.choice(ACGT, size=(STREAM_ROUNDS - 1) * ROUND + k + 37)
+    src, n, dst = COPIED
+    long[dst:dst + n] = revcomp(long[src:src + n])
+    at, run = stream_a_run(k)
+    long[at:at + run] = ord("A")
+    long[rng.random(len(long)) > 0.98] |= 0x20
+    long[stream_long_n_positions(k)] = ord("N")
+    records = [long, rng.choice(ACGT, size=2 * ROUND + 1), rng.choice(ACGT, size=k + 1)]
+    for r in records:
+        r.setflags(write=False)
+    return records
 
 
 def small(k, limit):

@@ -10,6 +10,7 @@ bytes, total valid k-mers), and WHICH files a batch door takes is asserted from 
     batch / wide batch        fh_k2b.hip (k <= 32), fh_k2bw.hip (k >= 33)    F.BatchSketcher / .wide, bytes and two-bit form
     large batch               fh_k2b.hip + fh_batch_large.hip (k <= 32)      F.BatchSketcher.large, n = 3001
     record sketcher           fh_records.hip (k <= 32)                       F.RecordSketcher, seed 0 / seed != 0, Scaled
+    streamed record sketcher  fh_records.hip, k_record_stream (k <= 32)      F.RecordSketcher(stream=True), the same three; E.stream_records
 
 (fh_k2s.hip has its own sweep: test_gpu_segments.py, test_every_k_on_two_and_four_lanes.)
 
@@ -32,6 +33,7 @@ from oracle import oracle as O
 from test_gpu_batch_wide import same_as
 from test_gpu_parity import assert_same
 from test_gpu_records import run as run_records
+from test_gpu_records_stream import run as run_streamed
 from test_gpu_segments import fixed_reads, oracle_of, packed as pack_reads, sketch_on_device
 
 pytestmark = pytest.mark.gpu
@@ -173,3 +175,22 @@ def test_record_sketcher(k, kind, size, seed, scale):
     records = E.stream(k)[0]
     res = run_records(records, size, k, seed, kind=kind, scale=scale, ctx="k=%d" % k, max_records=512)
     assert len(res) == len(records) and all(r is not None for r in res)
+
+
+# --- the streamed record sketcher ---
+
+@pytest.mark.parametrize("kind,size,seed,scale", [(KIND_MASH, 1000, 0, 0.0), (KIND_MASH, 50, 42, 0.0), (KIND_SCALED, 10, 7, E.STREAM_SCALE)],
+                         ids=["mash-seed0", "mash-seed42", "scaled-seed7"])
+@pytest.mark.parametrize("k", K_ONE)
+def test_streamed_record_sketcher(k, kind, size, seed, scale):
+    """E.stream_records(k): a record of six rounds with N around every round seam, a window alone across one, a block that recurs
+    as its reverse complement behind a fold; one of 8193 positions; one of k + 1.  All three are taken (tests/test_every_k_inputs.py
+    holds the Scaled row counts within the cap) and each equals the oracle's sketch of that record; the counters say the same.
+    The other fold rule runs the same records in tests/test_gpu_records_stream.py's `every_k`."""
+    records = E.stream_records(k)
+    res, folds = run_streamed(records, size, k, seed, kind=kind, scale=scale, ctx="k=%d" % k, max_records=16)
+    assert len(res) == len(records) and all(r is not None for r in res)
+    if size == 1000:
+        # the long record folds behind its second round (the key array could not take a third) and at its end; for k <= 5 the
+        # list never fills, the threshold never falls and every round's keys survive: a fold behind every round from the second
+        assert folds >= 2, folds

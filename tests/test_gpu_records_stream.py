@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if __name__ == "__main__":
     sys.path.insert(0, ROOT)
 
+import every_k_inputs as E  # noqa: E402
 import finch_rs_amd as F  # noqa: E402
 from finch_rs_amd._lib import KIND_MASH, KIND_SCALED  # noqa: E402
 from oracle import oracle as O  # noqa: E402
@@ -198,7 +199,18 @@ def case_parked_handles_keep_their_form():
         rs.close()
 
 
+def case_every_k():
+    """every k-mer length through k_record_stream<K, SEED0> and <K, false>: the three records of tests/every_k_inputs.py's
+    stream_records (round seams, a recurring block behind a fold, 8193 positions, k + 1 bases), Mash 1000"""
+    for k in range(1, 33):
+        for seed in (0, 42):
+            res, folds = run(E.stream_records(k), 1000, k, seed, ctx="every_k k=%d seed=%d" % (k, seed), max_records=16, stage_bytes=1 << 20)
+            assert all(r is not None for r in res) and folds >= 2
+        F.load().fh_release_cached()  # (a parked handle per k and seed would add up)
+
+
 CASES = {
+    "every_k": (case_every_k, [()]),
     "handle": (case_handle, [()]),
     "parked_handles_keep_their_form": (case_parked_handles_keep_their_form, [()]),
     "positions": (case_positions, [(1, 0), (4, 42), (21, 0), (21, 42), (31, 0), (32, 42)]),
