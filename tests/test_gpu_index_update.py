@@ -13,8 +13,8 @@ import pytest
 import finch_rs_amd as F
 from finch_rs_amd import _lib
 from finch_rs_amd import host as H
-from finch_rs_amd.sketch_schemes import FinchError
-from index_update_cases import TINY, TOP, check_index, collect, index_built, queries_for, spec
+from finch_rs_amd.sketch_schemes import KC_DTYPE, FinchError, SketchParams
+from index_update_cases import BELOW_ONE, TINY, TOP, check_index, collect, index_built, queries_for, spec
 
 pytestmark = pytest.mark.gpu
 
@@ -252,6 +252,45 @@ def test_counts_never_attached_stay_unattached():
         # attached now, against the updated library
         now = [old[0], old[2], old[4], more[1]]
         assert ix.compare_counts(qs, 1).tobytes() == H.compare_counts(collect(now), qs, 1).tobytes()
+
+
+def test_an_add_and_a_keep_of_scaled_sketches():
+    """the added references bring their scale with them: a pair with an added Scaled reference takes raw_distance's scale step
+    (the cursors go on to the first hash >= M), on the device as in the dense call.  (Met by the library fuzz's mutant 4,
+    docs/MEASUREMENTS_library_fuzz.md: every other test here adds Mash sketches.)"""
+    m = (2 ** 64 - 1) // 2  # M of scale 0.5
+
+    def scaled(name, hashes):
+        kc = np.zeros(len(hashes), KC_DTYPE)
+        kc["hash"], kc["count"] = np.asarray(sorted(hashes), np.uint64), 1
+        return H.sketches_from_arrays(name, 100, 100, kc, np.zeros((len(hashes), 21), np.uint8), SketchParams.scaled(1000, 21, 0.5),
+                                      H.FilterParams(False))
+
+    def library(parts):
+        out = scaled(*parts[0])
+        for part in parts[1:]:
+            out.append(scaled(*part))
+        return out
+
+    old = [("r0", [10, 20, 30, m - 5, m + 7]), ("r1", [20, 40])]
+    more = [("a0", [10, 20, 25, 26, m - 9, m - 3, m + 1]), ("a1", [5, 20]), ("a2", [])]
+    qs = library([("q0", [10, 20]), ("q1", [20, 26, m - 3]), ("q2", [m + 1, m + 7])])
+    with H.LibraryIndex(library(old)) as ix:
+        ix.add(library(more))
+        now = library(old + more)
+        _, rows = ix.search(qs, TINY)
+        a0 = rows[(rows["query"] == 0) & (rows["reference"] == 2)][0]
+        # q0 = {10, 20} against a0: both shared, the walk stops at 20 with j = 2, the step takes j to #{r < M} = 6
+        assert (int(a0["common_hashes"]), int(a0["total_hashes"]), float(a0["containment"])) == (2, 6, 2 / 6)
+        for keep in (None, [0, 2, 3]):
+            if keep is not None:
+                ix.keep(keep)
+                now = H.select(now, keep)
+            assert [x.tobytes() for x in ix.search(qs, TINY)] == [x.tobytes() for x in H.search(qs, now, TINY)]
+            assert ix.dist(qs, BELOW_ONE).tobytes() == H.dist(qs, now, BELOW_ONE).tobytes()
+            assert ix.dist(None, BELOW_ONE).tobytes() == H.dist(now, now, BELOW_ONE).tobytes()
+            with H.LibraryIndex(now) as fresh:
+                assert [x.tobytes() for x in ix.search(qs, 0.3, 2)] == [x.tobytes() for x in fresh.search(qs, 0.3, 2)]
 
 
 # ---- 7. chunks and entries ------------------------------------------------------------------------------------------------
